@@ -70,8 +70,8 @@ static_assert(WSUM_BYTES >= (size_t)2 * MAXLW * MAX_JB, "window-sum buffer (pair
 constexpr int NSLOT = MSM_HIP_NUM_SLOTS;  // result slots
 constexpr int NREDUCE = 2;  // reduce streams (slot k uses stream k % NREDUCE): two bucket reduces may be in flight when the
                             // main-stream work of one MSM is shorter than its bucket reduce (few windows per GPU).  The context
-                            // then owns 3 streams; callers that add their own (copies, RCCL) should raise GPU_MAX_HW_QUEUES
-                            // above ROCm's default of 4 so that streams do not share hardware queues (bench.py does).
+                            // then owns 3 streams; streams beyond the process's hardware queues (GPU_MAX_HW_QUEUES) share
+                            // them: correct, with less overlap.
 
 struct Slot {
   uint8_t* h_wsums = nullptr;      // pinned: MAXLW x 96 B window sums + 4 B error word

@@ -207,7 +207,7 @@ class ShardedMsmPipeline:
         if w_local > 0:
             launch = self.ctx.launch_vwindows_batch if self.wide else self.ctx.launch_half_windows_batch if self.halves else self.ctx.launch_windows_batch
             launch(scalars_dev, n, self.w_begin, self.w_end, slot, self.padded[slot][: nvec * w_local * self.rec], inputs_complete=inputs_complete)
-            # gather + copies go to the CURRENT torch stream (normally the default stream): with GPU_MAX_HW_QUEUES=8 this
+            # gather + copies go to the CURRENT torch stream (normally the default stream): with a hardware queue per stream this
             # layout -- 3 engine streams, the default stream, RCCL's own -- keeps three launches in flight; a dedicated side
             # stream (or a 4th engine stream) was measured to collapse the pipeline to one at a time
             self.ctx.slot_wait_stream(slot)

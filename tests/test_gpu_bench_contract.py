@@ -78,3 +78,18 @@ def test_multi_rank_line_carries_the_native_c_abi_figure(built):
     e = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--logn", "14"], BENCH_ALL_ON_GPU0="1", BENCH_DIST_BACKEND="gloo", BENCH_STEADY_MSMS="4",
                BENCH_NATIVE_TIMEOUT_S="0.01")
     assert e["value"] > 0 and e["value_native_mgpu"] is None and e["native_rccl_ranks"] is None and "error" in e["native_mgpu"]
+
+
+def test_dump_outputs_is_the_checked_result_and_repeats(built, tmp_path):
+    """--dump-outputs DIR: the last timed step's result, the one the run checks bit-exactly against the CPU oracle, and the same file
+    from a second run with the same arguments (seeded inputs); --steps sets the timed steps."""
+    import numpy as np
+
+    args = ["--steps", "5", "--warmup", "2", "--logn", "12"]
+    env = dict(BENCH_STEADY_MSMS="4", BENCH_CONFIGS="0", BENCH_TABLES_WIDE="0")
+    d = _bench(args + ["--dump-outputs", str(tmp_path / "a")], **env)
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["verified_bit_exact_vs_cpu"] is True
+    a = np.load(tmp_path / "a" / "msm_result.npy")
+    assert a.dtype == np.float64 and a.shape == (1, 2, 8) and np.isfinite(a).all() and a.any()
+    _bench(args + ["--no-cpu-baseline", "--dump-outputs", str(tmp_path / "b")], **env)
+    assert np.array_equal(np.load(tmp_path / "b" / "msm_result.npy"), a)
