@@ -160,6 +160,19 @@ int msm_hip_set_bases_device(msm_hip_ctx* ctx, const void* xy_dev, size_t n, uin
  *      the whole MSM); the device converts them in a pre-pass (one extra read and write of the scalars). ---- */
 #define MSM_HIP_SCALARS_CANONICAL 0u
 #define MSM_HIP_SCALARS_MONT256 1u
+/* narrow scalars: n x 1 / 2 / 4 / 8 bytes of unsigned little-endian integers, packed (booleans are U8 with values 0 / 1).  Every value is below r
+ * on every curve, so none is rejected.  For witness columns -- bits, bytes, range-check limbs, counters -- whose values are small: the host
+ * copies n x width bytes (never widened), and the device runs only the windows such a value has -- U8 / U16: one window per byte (unsigned digits,
+ * 255 buckets, a one-level counting sort); U32 / U64: 3 / 5 signed C-bit windows (C = 16; C from n as for 32-byte scalars, msm_hip_set_window_bits
+ * overrides) -- over the plain records 0 .. n-1, which every base mode keeps (no endomorphism split: a small k splits into (k, 0)).  Applies to the whole-MSM entry points: run, run_device, launch,
+ * launch_device / finish, run_batch, run_batch_device (a vector's stride: n x width bytes); device scalars must be aligned to the width.
+ * The window-sharding entry points (*_windows_*, *_half_windows_*, *_vwindows_*) return MSM_HIP_ERR_INVALID_ARG under a narrow format.
+ * The format is read by each launch: changing it between the launch and the finish of a slot does not affect that slot.  Not combinable
+ * with MONT256 (there is nothing to convert). */
+#define MSM_HIP_SCALARS_U8 2u
+#define MSM_HIP_SCALARS_U16 3u
+#define MSM_HIP_SCALARS_U32 4u
+#define MSM_HIP_SCALARS_U64 5u
 int msm_hip_set_scalar_format(msm_hip_ctx* ctx, uint32_t format);
 
 /* ---- window size (the reference hard-codes chunk_size = 16 for n >= 2^16, src/cuzk/msm.rs:79-82).
@@ -369,6 +382,9 @@ int msm_hip_set_debug(msm_hip_ctx* ctx, int keep_digit_planes);
 /* from `n` points on, the fine sort gets the sub-range histograms of huge coarse bins from a separate pass (default 32769:
  * whenever such a bin can exist); tests raise it to drive the fallback in which every sharer of a bin histograms it itself */
 int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n);
+/* the number of coming launches for which the fine sort's sub-range histograms (k_fine_hist) run because an earlier launch met a huge coarse
+ * bin (skewed 32-byte scalars arm it for 64 launches; narrow-scalar launches neither arm nor consume it) */
+int msm_hip_test_skew_credit(const msm_hip_ctx* ctx);
 int msm_hip_read_digits(msm_hip_ctx* ctx, uint16_t* out, size_t cap_elems);
 int msm_hip_read_col_ptr(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems);
 int msm_hip_read_val_idxs(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems);

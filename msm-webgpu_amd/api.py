@@ -97,6 +97,7 @@ def lib():
         L.msm_hip_stream.restype = vp
         L.msm_hip_set_debug.argtypes = [vp, i]
         L.msm_hip_set_fine_hist_min_n.argtypes = [vp, sz]
+        L.msm_hip_test_skew_credit.argtypes = [vp]
         L.msm_hip_set_scalar_format.argtypes = [vp, C.c_uint32]
         L.msm_hip_set_stage_timing.argtypes = [vp, i]
         L.msm_hip_set_window_bits.argtypes = [vp, i]
@@ -231,6 +232,32 @@ def _as_device_u8(t, row, what):
     return t, t.numel() // row
 
 
+# narrow scalar formats (include/msm_hip.h: MSM_HIP_SCALARS_U8 .. U64): bytes per scalar -> format value, and the unsigned dtype of that width
+SCALAR_WIDTHS = {1: 2, 2: 3, 4: 4, 8: 5}
+_UNSIGNED_OF_WIDTH = {1: "uint8", 2: "uint16", 4: "uint32", 8: "uint64"}
+
+
+def _as_device_scalars(t, width, what="scalars"):
+    """A CUDA tensor of scalars of `width` bytes -> (uint8 view, number of scalars).  32: the 32-byte forms (uint8 only, as always); a narrow
+    width: uint8 (a multiple of `width` bytes) or the unsigned dtype of that width, read as its little-endian bytes."""
+    if width == 32:
+        return _as_device_u8(t, 32, what)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise TypeError("%s must be a CUDA(HIP) tensor" % what)
+    if t.dtype != torch.uint8:
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype.is_signed or t.dtype == torch.bool:
+            raise TypeError("%s: %s is not an unsigned integer dtype (narrow scalars are unsigned)" % (what, t.dtype))
+        if t.dtype != getattr(torch, _UNSIGNED_OF_WIDTH[width]):
+            raise ValueError("%s: dtype %s does not hold %d-byte scalars" % (what, t.dtype, width))
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % what)
+        t = t.reshape(-1).view(torch.uint8)
+    t, n = _as_device_u8(t, width, what)
+    if t.data_ptr() % width:
+        raise ValueError("%s must be aligned to %d bytes" % (what, width))
+    return t, n
+
+
 class MsmContext:
     """Persistent engine on one GPU: stream, pooled buffers, resident bases (include/msm_hip.h)."""
 
@@ -244,6 +271,7 @@ class MsmContext:
         self.device = int(device)
         self.n_bases = 0
         self.wide_bits_choice = 0
+        self.scalar_width = 32  # bytes per scalar of the following runs (set_scalar_format)
         self._keepalive = {}  # slot -> tensors the slot's launch still reads / writes; released when the slot is collected
 
     def _order_after_torch(self, *tensors):
@@ -293,32 +321,39 @@ class MsmContext:
         return n
 
     # -- whole MSM
+    def _host_scalars(self, scalars):
+        b = bytes(scalars)
+        w = self.scalar_width
+        if len(b) % w:
+            raise ValueError("scalars must be n x %d bytes" % w)
+        return b, len(b) // w
+
     def msm(self, scalars):
-        """sum_i scalars[i] * bases[i] -> G1.  scalars: bytes (n x 32 B) or CUDA uint8 tensor."""
+        """sum_i scalars[i] * bases[i] -> G1.  scalars: bytes (n x 32 B; n x width B under a narrow format) or a CUDA tensor (uint8; under a
+        narrow format also the unsigned dtype of its width)."""
         out = C.create_string_buffer(self.jb)
         if isinstance(scalars, torch.Tensor) and scalars.is_cuda:
-            t, n = _as_device_u8(scalars, 32, "scalars")
+            t, n = _as_device_scalars(scalars, self.scalar_width)
             self._order_after_torch(t)
             _check(lib().msm_hip_run_device(self._h, t.data_ptr(), n, out), "msm_hip_run_device")
         else:
-            b = bytes(scalars)
-            if len(b) % 32:
-                raise ValueError("scalars must be n x 32 bytes")
-            _check(lib().msm_hip_run(self._h, b, len(b) // 32, out), "msm_hip_run")
+            b, n = self._host_scalars(scalars)
+            _check(lib().msm_hip_run(self._h, b, n, out), "msm_hip_run")
         return G1(out.raw, self.modulus)
 
     def msm_batch(self, scalars_dev, n):
-        """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes (or host bytes
-        of the same layout) -> [G1, ...]."""
+        """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under
+        a narrow format, where the unsigned dtype of that width is accepted too -- or host bytes of the same layout -> [G1, ...]."""
+        w = self.scalar_width
         if isinstance(scalars_dev, (bytes, bytearray)):
             b = bytes(scalars_dev)
-            if n <= 0 or len(b) % (32 * n):
+            if n <= 0 or len(b) % (w * n):
                 raise ValueError("scalars must hold a whole number of n-element vectors")
-            batch = len(b) // (32 * n)
+            batch = len(b) // (w * n)
             out = C.create_string_buffer(self.jb * batch)
             _check(lib().msm_hip_run_batch(self._h, b, n, batch, out), "msm_hip_run_batch")
             return [G1(out.raw[self.jb * k:self.jb * (k + 1)], self.modulus) for k in range(batch)]
-        t, rows = _as_device_u8(scalars_dev, 32, "scalars")
+        t, rows = _as_device_scalars(scalars_dev, w)
         if n <= 0 or rows % n:
             raise ValueError("scalars must hold a whole number of n-element vectors")
         batch = rows // n
@@ -329,7 +364,7 @@ class MsmContext:
 
     def launch(self, scalars_dev, slot=0):
         """Enqueue the device work of one MSM into a result slot (0..3) and return at once."""
-        t, n = _as_device_u8(scalars_dev, 32, "scalars")
+        t, n = _as_device_scalars(scalars_dev, self.scalar_width)
         self._order_after_torch(t)
         _check(lib().msm_hip_launch_device(self._h, t.data_ptr(), n, slot), "msm_hip_launch_device")
         self._keepalive[slot] = t
@@ -337,10 +372,8 @@ class MsmContext:
     def launch_host(self, scalars_host, slot=0):
         """`launch` with the scalars in host memory (bytes, n x 32 B): copied on the engine's copy stream into the slot's own
         staging buffer, so the copy of the next MSM overlaps the device work of the current one when slots alternate."""
-        b = bytes(scalars_host)
-        if len(b) % 32:
-            raise ValueError("scalars must be n x 32 bytes")
-        _check(lib().msm_hip_launch(self._h, b, len(b) // 32, slot), "msm_hip_launch")
+        b, n = self._host_scalars(scalars_host)
+        _check(lib().msm_hip_launch(self._h, b, n, slot), "msm_hip_launch")
 
     def finish(self, slot=0):
         """Wait for the slot's device work, run the host window combine, return G1."""
@@ -549,9 +582,21 @@ class MsmContext:
         return lib().msm_hip_uses_endomorphism(self._h) == 1
 
     # -- stage read-back (parity tests)
-    def set_scalar_format(self, mont256):
-        """False: canonical little-endian scalars (default); True: s * 2^256 mod r words (R = 2^256 Montgomery limbs)."""
-        _check(lib().msm_hip_set_scalar_format(self._h, 1 if mont256 else 0), "msm_hip_set_scalar_format")
+    def set_scalar_format(self, mont256=False, width=32):
+        """mont256 False: canonical little-endian scalars (default); True: s * 2^256 mod r words (R = 2^256 Montgomery limbs).
+        width: bytes per scalar -- 32, or 1 / 2 / 4 / 8 for narrow unsigned scalars (MSM_HIP_SCALARS_U8 .. U64: witness columns of small
+        values; whole-MSM calls only).  A narrow width cannot be combined with mont256."""
+        if width not in (1, 2, 4, 8, 32):
+            raise ValueError("scalar width must be 1, 2, 4, 8 or 32 bytes, not %r" % (width,))
+        if mont256 and width != 32:
+            raise ValueError("mont256 scalars are 32 bytes wide")
+        fmt = SCALAR_WIDTHS[width] if width != 32 else (1 if mont256 else 0)
+        _check(lib().msm_hip_set_scalar_format(self._h, fmt), "msm_hip_set_scalar_format")
+        self.scalar_width = width
+
+    def skew_credit(self):
+        """launches left that run k_fine_hist because an earlier 32-byte launch met a huge coarse bin (test hook)"""
+        return lib().msm_hip_test_skew_credit(self._h)
 
     def set_fine_hist_min_n(self, n):
         _check(lib().msm_hip_set_fine_hist_min_n(self._h, n), "msm_hip_set_fine_hist_min_n")

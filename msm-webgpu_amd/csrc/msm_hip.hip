@@ -60,7 +60,19 @@ enum LaunchMode {
   MODE_HALVES = 2,  // endomorphism: 127-bit halves k1, k2 over the 2n points P_i, phi(P_i) (MSM_HIP_BASES_ENDOMORPHISM, csrc/glv.h)
   MODE_WIDE = 3,    // wide fixed-base tables: ceil(255 / C) digits of C = 16 .. 20 bits per scalar, one bucket set of 2^(C-1) slots run as 2^(C-16) virtual windows of 2^15
                     // (MSM_HIP_BASES_PRECOMPUTE_WIDE; msm_kernels.h: k_count_wide)
+  MODE_NARROW = 4,  // narrow scalars (MSM_HIP_SCALARS_U8 .. U64): the narrow_windows(C, bytes) windows of n x 1 .. 8 B unsigned integers over the
+                    // plain records 0 .. n-1, which every base mode keeps (msm_kernels.h: k_count<C, SW, false, NB>)
 };
+
+// bytes of a narrow scalar format (MSM_HIP_SCALARS_U8 .. U64); 0 for the 32-byte formats
+inline int narrow_bytes(uint32_t format) { return format >= MSM_HIP_SCALARS_U8 && format <= MSM_HIP_SCALARS_U64 ? 1 << (format - MSM_HIP_SCALARS_U8) : 0; }
+// U8 / U16 run as byte windows (one per byte, unsigned digits 1 .. 255, a one-level counting sort: msm_kernels.h, k_byte_count ...) on the 12-bit
+// bucket grid -- the smallest the reduce kernels have, 2^11 slots of which 255 can fill; U32 / U64 as truncated signed C-bit windows (C from n)
+// through the two-level sort
+inline bool byte_windows(int nb) { return nb == 1 || nb == 2; }
+constexpr int BYTE_WBITS = 12;
+inline int narrow_windows(int wbits, int nb) { return byte_windows(nb) ? nb : narrow_nwin_of(wbits, nb); }
+inline int narrow_max_windows(int nb) { return byte_windows(nb) ? BYTE_MAXLW : MAXLW; }  // local windows per launch (byte windows: 256 bins each)
 
 constexpr int N_MAIN_EVENTS = 7;  // boundaries of the 6 timed stages on the main stream
 constexpr uint32_t MAX_TILES = 1024;
@@ -99,6 +111,7 @@ struct Slot {
   int wide_bits = 0;                          // wide fixed-base launch (its digit width): h_wsums holds the bit-plane sums of the virtual windows (combine_wide)
   bool parts = false;                         // h_wsums holds the bit-plane sums of every window (k_bpr_planes): the host finishes the window sums
   bool pairs = false;                         // a share of the wide tables' virtual windows: the launch leaves (window sum, plain total) record pairs
+  int narrow = 0;                             // narrow-scalar launch: bytes per scalar (its windows: narrow_windows(wbits, narrow))
   int timing_level = 0;
   int w_begin = 0, w_count = 0, nvec = 1;  // windows [w_begin, w_begin + w_count) of nvec scalar vectors
   size_t n = 0;
@@ -170,7 +183,7 @@ struct msm_hip_ctx {
   size_t cap_list_len = 0;
   uint32_t* d_scalar_conv = nullptr;  // canonical copies of scalars handed over in R = 2^256 Montgomery form (one launch's worth)
   size_t cap_scalar_conv = 0;         // in scalars
-  uint32_t scalar_format = 0;         // MSM_HIP_SCALARS_CANONICAL / MSM_HIP_SCALARS_MONT256
+  uint32_t scalar_format = 0;         // MSM_HIP_SCALARS_CANONICAL / MSM_HIP_SCALARS_MONT256 / MSM_HIP_SCALARS_U8 .. U64 (read by each launch)
   int window_bits = 0;                // 0: chosen from n for whole-MSM launches (pick_window_bits); else 12 / 14 / 16
   uint32_t* d_part_hist = nullptr;  // [MAXLW][128][FINE_SPLIT][256] sub-range histograms of huge coarse bins (k_fine_hist), on first use
   size_t fine_hist_min_n = FINE_BIG + 1;  // any n that can produce a coarse bin beyond FINE_BIG: run k_fine_hist (3 us when none does)
@@ -494,11 +507,12 @@ int ensure_work(msm_hip_ctx* ctx, size_t n, int w_count, int wbits, int full_win
 // 2^16 +6 % with the endomorphism; +45 % / +50 % / +27 % plain; 16 bits from 2^17 up).
 // `nvec` whole MSMs must fit MAXLW local windows.  The window-sharding entry points always use 16-bit windows: their w_begin / w_end
 // index the reference's 16 windows.
-inline int pick_window_bits(const msm_hip_ctx* ctx, size_t n, int nvec, bool halves = false) {
+// (`nb`: narrow scalars of nb bytes -- the same choice, with their own window count)
+inline int pick_window_bits(const msm_hip_ctx* ctx, size_t n, int nvec, bool halves = false, int nb = 0) {
   static const int forced = [] { const char* e = getenv("MSM_HIP_WINDOW_BITS"); return e ? atoi(e) : 0; }();  // tuning aid
   int bits = ctx->window_bits ? ctx->window_bits : (forced == 12 || forced == 14 || forced == 16 ? forced : 0);
   if (!bits) bits = nvec > 1 ? (n <= ((size_t)1 << 16) ? 14 : 16) : (n <= ((size_t)1 << 12) ? 12 : 16);
-  while (bits < 16 && nvec * nwin_of(bits, halves) > MAXLW) bits += 2;
+  while (bits < 16 && nvec * (nb ? narrow_nwin_of(bits, nb) : nwin_of(bits, halves)) > MAXLW) bits += 2;
   return bits;
 }
 
@@ -538,7 +552,7 @@ int err_from_bits(uint32_t bits) {
 inline bool use_planes(const msm_hip_ctx* ctx, LaunchMode mode, int w_count_vec, int wbits) {
   static const int max_w = [] { const char* e = getenv("MSM_HIP_PLANES_MAX_W"); return e ? atoi(e) : 8; }();
   static const bool whole = [] { const char* e = getenv("MSM_HIP_PLANES_WHOLE"); return e && e[0] == '1'; }();  // A/B aid: whole MSMs too
-  if (mode == MODE_TABLES || mode == MODE_WIDE || ctx->debug) return false;
+  if (mode == MODE_TABLES || mode == MODE_WIDE || mode == MODE_NARROW || ctx->debug) return false;
   if (whole) return true;
   return w_count_vec <= max_w && w_count_vec < nwin_of(wbits, mode == MODE_HALVES);
 }
@@ -555,6 +569,8 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
             uint32_t* wsums_out, bool to_host, int v_begin = 0, int v_count = 0, int phase = 0) {
   const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
   const bool pairs = wide && v_count != 0;
+  const int nb = mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;  // (launch_impl admits MODE_NARROW only under a narrow format)
+  const bool bytes = byte_windows(nb);  // U8 / U16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
   if (wide && !pairs) v_count = wide_vwin_of(ctx->wide_bits);
   const uint32_t half = 1u << (wbits - 1);   // bucket slots per window
   const unsigned ncoarse = half / FINE;      // coarse bins that can hold entries
@@ -598,7 +614,7 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   const uint32_t chunks = wide ? ws.chunks : chunks_for(n_entries, chunk_len);
   const size_t stride = stride_for(n_entries);
   ctx->last_stride = stride;
-  uint16_t* digits = ctx->debug && !merge && !wide ? ctx->d_digits : nullptr;
+  uint16_t* digits = ctx->debug && !merge && !wide && !bytes ? ctx->d_digits : nullptr;
   uint32_t* d_err = reinterpret_cast<uint32_t*>(s.d_wsums + WSUM_BYTES);
   if (!wsums_out) wsums_out = reinterpret_cast<uint32_t*>(s.d_wsums);
   // the SMVP chunk length the device settles on for this launch (k_scatter_coarse -> fine sort, SMVP, stitch): a word of the slot
@@ -615,7 +631,7 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   if (phase != 2) {  // ---- recode + sort
   HIP_TRY(ctx, hipStreamWaitEvent(st, s.done, 0));
   HIP_TRY(ctx, mark(0, false));
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
+  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !nb) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
     const size_t count = (size_t)nvec * n;
     hipLaunchKernelGGL(ctx->ops->scalars_from_mont256, dim3(blocks_for(count, 256)), dim3(256), 0, st, d_scalars, ctx->d_scalar_conv, count, d_err);
     AFTER_KERNEL(ctx, "k_scalars_from_mont256", st);
@@ -651,6 +667,22 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
     }
 #undef LAUNCH_COUNT_WIDE
 #undef LAUNCH_COUNT_WIDE_LIST
+  } else if (bytes) {
+    if (nb == 1) hipLaunchKernelGGL(k_byte_count<1>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, tile_len, tiles, ctx->d_counts);
+    else hipLaunchKernelGGL(k_byte_count<2>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, tile_len, tiles, ctx->d_counts);
+  } else if (nb) {
+    // U32 / U64: vectors of n x nb bytes (vec_stride in bytes)
+#define LAUNCH_COUNT_NARROW(C, NB) hipLaunchKernelGGL((k_count<C, (NB + 3) / 4, false, NB>), dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, w_begin, \
+                       w_count_vec, nvec, n * NB, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, (size_t)0)
+#define LAUNCH_NARROW_BY_WBITS(L, NB) \
+  do {                                \
+    if (wbits == 16) L(16, NB);       \
+    else if (wbits == 14) L(14, NB);  \
+    else L(12, NB);                   \
+  } while (0)
+    if (nb == 4) LAUNCH_NARROW_BY_WBITS(LAUNCH_COUNT_NARROW, 4);
+    else LAUNCH_NARROW_BY_WBITS(LAUNCH_COUNT_NARROW, 8);
+#undef LAUNCH_COUNT_NARROW
   } else if (halves) {
     hipLaunchKernelGGL(ctx->ops->count_split[wbits == 16 ? 2 : wbits == 14 ? 1 : 0], dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, w_begin,
                        w_count_vec, nvec, n * 8, ctx->d_counts, plane_out, plane_mode, planes ? ctx->d_negbits : nullptr,
@@ -662,7 +694,8 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   }
   AFTER_KERNEL(ctx, "k_count", st);
   HIP_TRY(ctx, mark(1, false));
-  hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, w_count), dim3(256), 0, st, ctx->d_counts, tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
+  if (bytes) hipLaunchKernelGGL(k_byte_scan, dim3(BYTE_BINS / 4, w_count), dim3(256), 0, st, ctx->d_counts, tiles, ctx->d_bin_total);
+  else hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, w_count), dim3(256), 0, st, ctx->d_counts, tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
   AFTER_KERNEL(ctx, "k_scan_tiles", st);
   HIP_TRY(ctx, mark(2, false));
   if (wide) {
@@ -696,6 +729,20 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
     hipLaunchKernelGGL(k_scatter_planes, dim3(tiles), dim3(256), 0, st, ctx->d_digits, halves ? ctx->d_negbits : (const uint64_t*)nullptr, n_sc, stride, tile_len,
                        tiles, w_count, w_count_vec, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
                        (uint32_t)ctx->n_bases, chunks, chunk_len, d_chunk_len);
+  } else if (bytes) {
+#define LAUNCH_SCATTER_BYTES(NB) hipLaunchKernelGGL(k_byte_scatter<NB>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, stride, tile_len, tiles, \
+                       w_count, ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, half, ctx->d_val, chunks, chunk_len, d_chunk_len)
+    if (nb == 1) LAUNCH_SCATTER_BYTES(1);
+    else LAUNCH_SCATTER_BYTES(2);
+#undef LAUNCH_SCATTER_BYTES
+  } else if (nb) {
+#define LAUNCH_SCATTER_NARROW(C, NB) hipLaunchKernelGGL((k_scatter_coarse<C, (NB + 3) / 4, NB>), dim3(tiles, nvec), dim3(256), gpos_bytes, st, d_scalars, n_sc, stride, tile_len, \
+                       tiles, w_begin, w_count_vec, nvec, n * NB, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, (size_t)0, \
+                       (uint32_t)n, 0u, chunks, chunk_len, d_chunk_len)
+    if (nb == 4) LAUNCH_NARROW_BY_WBITS(LAUNCH_SCATTER_NARROW, 4);
+    else LAUNCH_NARROW_BY_WBITS(LAUNCH_SCATTER_NARROW, 8);
+#undef LAUNCH_SCATTER_NARROW
+#undef LAUNCH_NARROW_BY_WBITS
   } else if (halves) {
     LAUNCH_BY_WBITS_SW(k_scatter_coarse, gpos_bytes, 4, d_scalars, n_sc, stride, tile_len, tiles, w_begin, w_count_vec, nvec, n * 8, ctx->d_counts, ctx->d_bin_total,
                        ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, (uint32_t)n, (uint32_t)ctx->n_bases, chunks, chunk_len, d_chunk_len);
@@ -713,17 +760,25 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   // ... ADAPTIVELY (later in round 5): few distinct / small / equal scalars (witness vectors) fill huge bins at any size, and the fallback costs their
   // fine sort 2 - 2.5 x (profiles/r05_skew_hist.txt): k_sort_fine reports a huge bin in the slot's status word, and the 64 launches after such a
   // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once)
-  const bool hist_useful = ctx->fine_hist_min_n != FINE_BIG + 1 || n_entries / ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
-  if (ctx->skew_credit > 0) ctx->skew_credit--;
-  if (n_entries >= ctx->fine_hist_min_n && hist_useful) {
-    hipLaunchKernelGGL(k_fine_hist, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
-                       ctx->d_part_hist);
-    AFTER_KERNEL(ctx, "k_fine_hist", st);
-    part_hist = ctx->d_part_hist;
+  // Narrow scalars always run it and leave the credit alone: their top window holds only the recode's carry (U8: all entries) -- one huge bin by
+  // construction, which says nothing about the context's later 32-byte launches
+  if (bytes) {  // byte windows: the scatter has grouped the entries by slot already; only the SMVP's chunk table is left
+    hipLaunchKernelGGL(k_byte_chunks, dim3(blocks_for(chunks, 256), w_count), dim3(256), 0, st, (const uint32_t*)s.d_col_ptr, half, chunks,
+                       (const uint32_t*)d_chunk_len, ctx->d_chunk_slot);
+    AFTER_KERNEL(ctx, "k_byte_chunks", st);
+  } else {
+    const bool hist_useful = nb || ctx->fine_hist_min_n != FINE_BIG + 1 || n_entries / ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
+    if (ctx->skew_credit > 0 && !nb) ctx->skew_credit--;
+    if (n_entries >= ctx->fine_hist_min_n && hist_useful) {
+      hipLaunchKernelGGL(k_fine_hist, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
+                         ctx->d_part_hist);
+      AFTER_KERNEL(ctx, "k_fine_hist", st);
+      part_hist = ctx->d_part_hist;
+    }
+    hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_val, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
+                       s.d_col_ptr, ctx->d_val, chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err);
+    AFTER_KERNEL(ctx, "k_sort_fine", st);
   }
-  hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_val, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
-                     s.d_col_ptr, ctx->d_val, chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err);
-  AFTER_KERNEL(ctx, "k_sort_fine", st);
   if (ctx->debug) {  // deterministic transpose for the stage read-back: every slot's run in ascending order
     hipLaunchKernelGGL(k_order_runs, dim3(blocks_for(n_entries, 256), w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_val, ctx->d_tmp_val, stride, half);
     hipLaunchKernelGGL(k_copy_runs, dim3(blocks_for(n_entries, 256), w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_tmp_val, ctx->d_val, stride, half);
@@ -826,6 +881,7 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   s.wide_bits = wide ? ctx->wide_bits : 0;
   s.parts = parts_mode;
   s.pairs = pairs;
+  s.narrow = nb;
   if (pairs) {
     s.w_begin = v_begin;
     s.w_count = v_count;
@@ -860,7 +916,7 @@ int wait_slot(msm_hip_ctx* ctx, Slot& s) {
   }
   uint32_t bits;
   memcpy(&bits, s.h_wsums + WSUM_BYTES, 4);
-  if (bits & INFOBIT_HUGE_BIN) ctx->skew_credit = 64;  // (see the launch of k_fine_hist)
+  if ((bits & INFOBIT_HUGE_BIN) && !s.narrow) ctx->skew_credit = 64;  // (see the launch of k_fine_hist; a narrow launch's huge bins are its own)
   return err_from_bits(bits);
 }
 
@@ -963,7 +1019,10 @@ size_t batch_group(msm_hip_ctx* ctx, size_t n, size_t batch) {
   // 4 at 16 bits, 3 at 14, 2 at 12 (8 / 6 / 5 with the endomorphism's half-length scalars); with fixed-base tables every MSM is one local window
   // (window size of a grouped launch: pick_window_bits with nvec > 1)
   // (wide tables: an MSM is 2^(C-16) local windows, and its launch leaves bit-plane sums for at most 24 of them: 24 / 12 / 3 / 1 MSMs at 16 / 17 / 19 / 20 bits)
-  const size_t fit = ctx->wide_bits ? (size_t)(24 / wide_vwin_of(ctx->wide_bits)) : ctx->precomputed ? (size_t)MAXLW : (size_t)(MAXLW / nwin_of(pick_window_bits(ctx, n, 2, ctx->endo), ctx->endo));
+  // (narrow scalars: their own windows, over the plain records whatever the base mode)
+  const int nb = narrow_bytes(ctx->scalar_format);
+  const size_t fit = nb ? (size_t)(narrow_max_windows(nb) / narrow_windows(byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, n, 2, false, nb), nb))
+                        : ctx->wide_bits ? (size_t)(24 / wide_vwin_of(ctx->wide_bits)) : ctx->precomputed ? (size_t)MAXLW : (size_t)(MAXLW / nwin_of(pick_window_bits(ctx, n, 2, ctx->endo), ctx->endo));
   size_t g = n ? ((size_t)1 << 20) / n : 1;
   if (g > fit) g = fit;
   if (g > batch) g = batch;
@@ -1146,12 +1205,17 @@ int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, i
   // (MODE_WIDE: called with wbits = 19 and all 14 windows; everything behind the recode sees 8 local windows of 16 bits)
   const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
   const bool pairs = wide && v_count != 0;
+  const int nb = ctx && mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;
   int rc = check_run_args(ctx, scalars_dev, n);
   const size_t base_off = ctx ? ctx->launch_base_off : 0;
   if (ctx && phase != 1) ctx->launch_base_off = 0;  // (a two-phase launch passes here twice)
   if (rc) return rc;
   if (base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
-  if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > nwin_of(wbits, halves) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
+  if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > (nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves)) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
+  // narrow scalars: whole MSMs only, over the plain records, from a pointer aligned to the scalar's size
+  if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != narrow_windows(wbits, nb) || window_sums_dev || base_off || nvec * w_end > narrow_max_windows(nb) ||
+                              (byte_windows(nb) && wbits != BYTE_WBITS) ||
+                              reinterpret_cast<uintptr_t>(scalars_dev) % (uintptr_t)nb)) return MSM_HIP_ERR_INVALID_ARG;
   if (wide && (nvec < 1 || w_begin != 0 || wbits != ctx->wide_bits || w_end != wide_tables_of(wbits))) return MSM_HIP_ERR_INVALID_ARG;
   if (wide && !pairs && (nvec * wide_vwin_of(ctx->wide_bits) > 24 || window_sums_dev)) return MSM_HIP_ERR_INVALID_ARG;
   if (pairs && (v_begin < 0 || v_count < 0 || v_begin + v_count > wide_vwin_of(ctx->wide_bits))) return MSM_HIP_ERR_INVALID_ARG;
@@ -1176,6 +1240,7 @@ int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, i
   s.wide_bits = wide ? ctx->wide_bits : 0;
   s.parts = false;
   s.pairs = pairs;
+  s.narrow = nb;
   if (pairs) {
     s.w_begin = v_begin;
     s.w_count = v_count;
@@ -1202,14 +1267,14 @@ int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, i
       ctx->cap_list_len = need_len;
     }
   } else if ((rc = ensure_work(ctx, merge ? n * (size_t)w_count : halves ? 2 * n : n, w_local, wbits,
-                               merge ? 1 : halves ? nwin_of(wbits, true) : NWIN, s, use_planes(ctx, mode, w_count, wbits)))) return rc;
+                               merge ? 1 : halves ? nwin_of(wbits, true) : nb ? w_count : NWIN, s, use_planes(ctx, mode, w_count, wbits)))) return rc;
   if (halves && !use_planes(ctx, mode, w_count, wbits) && (size_t)nvec * n > ctx->cap_halves) {  // (the halves as an array: only when the second pass reads them)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cap_halves = 0;
     if ((rc = dev_alloc(ctx, ctx->d_halves, (size_t)nvec * n * 8))) return rc;
     ctx->cap_halves = (size_t)nvec * n;
   }
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && (size_t)nvec * n > ctx->cap_scalar_conv) {
+  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !nb && (size_t)nvec * n > ctx->cap_scalar_conv) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cap_scalar_conv = 0;
     if ((rc = dev_alloc(ctx, ctx->d_scalar_conv, (size_t)nvec * n * 8))) return rc;
@@ -1225,6 +1290,13 @@ extern "C" {
 int msm_hip_launch_windows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int w_begin, int w_end,
                                               int slot, void* window_sums_dev) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
+  if (const int nb = narrow_bytes(ctx->scalar_format)) {
+    // narrow scalars (the format of this launch): whole MSMs only -- the window-sharding calls index the 16 windows of 32-byte scalars
+    if (w_begin != 0 || w_end != NWIN || window_sums_dev || nvec < 1) return MSM_HIP_ERR_INVALID_ARG;
+    if (n == 0) return launch_impl(ctx, scalars_dev, n, nvec, 0, NWIN, WBITS, slot, nullptr);  // (identity sums)
+    const int wbits = byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, n, nvec, false, nb);
+    return launch_impl(ctx, scalars_dev, n, nvec, 0, narrow_windows(wbits, nb), wbits, slot, nullptr, MODE_NARROW);
+  }
   // whole MSMs whose sums stay in the slot (finish / finish_batch combines them): the window size follows n
   if (w_begin == 0 && w_end == NWIN && window_sums_dev == nullptr && nvec >= 1 && ctx->wide_bits && n > 0)
     return launch_impl(ctx, scalars_dev, n, nvec, 0, wide_tables_of(ctx->wide_bits), ctx->wide_bits, slot, nullptr, MODE_WIDE);  // wide fixed-base tables (one MSM per launch)
@@ -1243,14 +1315,14 @@ int msm_hip_launch_windows_batch_device(msm_hip_ctx* ctx, const void* scalars_de
 
 int msm_hip_launch_half_windows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int hw_begin, int hw_end,
                                                    int slot, void* window_sums_dev) {
-  if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
+  if (!ctx || narrow_bytes(ctx->scalar_format)) return MSM_HIP_ERR_INVALID_ARG;
   if (!ctx->endo && ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;  // needs bases set with MSM_HIP_BASES_ENDOMORPHISM
   return launch_impl(ctx, scalars_dev, n, nvec, hw_begin, hw_end, WBITS, slot, window_sums_dev, MODE_HALVES);
 }
 
 int msm_hip_launch_vwindows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int v_begin, int v_end, int slot,
                                          void* sums_dev) {
-  if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
+  if (!ctx || narrow_bytes(ctx->scalar_format)) return MSM_HIP_ERR_INVALID_ARG;
   if (!ctx->wide_bits) return ctx->n_bases || !n ? MSM_HIP_ERR_INVALID_ARG : MSM_HIP_ERR_NO_BASES;  // needs bases set with MSM_HIP_BASES_PRECOMPUTE_WIDE
   if (v_begin < 0 || v_end <= v_begin) return MSM_HIP_ERR_INVALID_ARG;
   return launch_impl(ctx, scalars_dev, n, nvec, 0, wide_tables_of(ctx->wide_bits), ctx->wide_bits, slot, sums_dev, MODE_WIDE, v_begin, v_end - v_begin);
@@ -1284,8 +1356,9 @@ int msm_hip_finish_batch(msm_hip_ctx* ctx, int slot, uint8_t* out_xyz) {
   if (!ctx || !out_xyz || slot < 0 || slot >= NSLOT) return MSM_HIP_ERR_INVALID_ARG;
   Slot& s = ctx->slot[slot];
   // fixed-base launches leave ONE sum per vector (every table already carries its power of two): nothing to combine but the copy
-  const int nwin = s.merged ? 1 : s.wide_bits ? wide_vwin_of(s.wide_bits) : nwin_of(s.wbits, s.halves);
-  if (!s.pending || !s.to_host || s.pairs || s.w_count != (s.wide_bits ? wide_tables_of(s.wide_bits) : nwin_of(s.wbits, s.halves))) return MSM_HIP_ERR_INVALID_ARG;
+  const int nwin = s.merged ? 1 : s.wide_bits ? wide_vwin_of(s.wide_bits) : s.narrow ? narrow_windows(s.wbits, s.narrow) : nwin_of(s.wbits, s.halves);
+  const int combine_bits = byte_windows(s.narrow) ? 8 : s.wbits;  // (byte windows: window j weighs 2^(8 j))
+  if (!s.pending || !s.to_host || s.pairs || s.w_count != (s.wide_bits ? wide_tables_of(s.wide_bits) : s.narrow ? nwin : nwin_of(s.wbits, s.halves))) return MSM_HIP_ERR_INVALID_ARG;
   ON_DEVICE(ctx);
   int rc = wait_slot(ctx, s);
   if (rc) return rc;
@@ -1302,10 +1375,10 @@ int msm_hip_finish_batch(msm_hip_ctx* ctx, int slot, uint8_t* out_xyz) {
       combine_pool().run(s.nvec, [&](int v) {
         if (!ctx->ops->combine_wide(sums + jb * (size_t)v * nwin, s.h_wsums + (size_t)v * nwin * PLANES_PER_WINDOW * jb, nwin, out_xyz + jb * (size_t)v)) all_ok = false;
       });
-    } else if (!ctx->ops->combine_windows(sums, nwin, s.wbits, out_xyz)) all_ok = false;
+    } else if (!ctx->ops->combine_windows(sums, nwin, combine_bits, out_xyz)) all_ok = false;
   } else {
     combine_pool().run(s.nvec, [&](int v) {  // one independent Horner chain per MSM of the launch: side by side when there are several
-      if (!ctx->ops->combine_windows(s.h_wsums + (size_t)v * nwin * ctx->jb, nwin, s.wbits, out_xyz + ctx->jb * (size_t)v)) all_ok = false;
+      if (!ctx->ops->combine_windows(s.h_wsums + (size_t)v * nwin * ctx->jb, nwin, combine_bits, out_xyz + ctx->jb * (size_t)v)) all_ok = false;
     });
   }
   if (!all_ok) return MSM_HIP_ERR_HIP;
@@ -1337,6 +1410,10 @@ int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n,
   int rc = check_run_args(ctx, scalars_host, n);
   if (rc) return rc;
   if (slot < 0 || slot >= NSLOT) return MSM_HIP_ERR_INVALID_ARG;
+  // narrow scalars: n x 1 .. 8 bytes cross the link as they are (never widened on the host); whole MSMs only
+  const int nb = narrow_bytes(ctx->scalar_format);
+  if (nb && !auto_bits) return MSM_HIP_ERR_INVALID_ARG;
+  const size_t sbytes = nb ? (size_t)nb : 32;
   ON_DEVICE(ctx);
   Slot& s = ctx->slot[slot];
   if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
@@ -1352,7 +1429,7 @@ int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n,
   // (a caller that alternates two slots gets the copy of MSM i+1 under the device work of MSM i); the main stream waits
   // for it on the device.  From pageable memory the call returns when the bytes have left the caller's buffer; from
   // pinned memory (hipHostMalloc / hipHostRegister) at once -- the buffer must then stay untouched until finish / slot_sync.
-  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, n * 32, hipMemcpyHostToDevice, ctx->copy_stream));
+  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, n * sbytes, hipMemcpyHostToDevice, ctx->copy_stream));
   HIP_TRY(ctx, hipEventRecord(s.staged, ctx->copy_stream));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
   if (auto_bits) return msm_hip_launch_windows_batch_device(ctx, s.d_host_scalars, n, 1, 0, NWIN, slot, nullptr);
@@ -1371,7 +1448,8 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
   // Parts (round 5): 32 n bytes over the host link come before anything can run.  From 2^19 points on the call is the sum of sub-MSMs over
   // ranges of the points, one result slot each: part k + 1's scalars arrive while part k is sorted and accumulated, and the results are added
   // on the host.  (Not with fixed-base tables: their launches are shaped by the table count.)
-  int parts = ctx->precomputed || ctx->wide_bits || !scalars_host ? 1 : upload_parts(n, NSLOT, 20, 22);  // (2^20: 2.44 -> 2.38 ms, 2^22: 8.61 -> 6.91; 2^19: slower)
+  // (Nor with narrow scalars: 1 - 8 bytes per point leave no upload worth hiding.)
+  int parts = ctx->precomputed || ctx->wide_bits || narrow_bytes(ctx->scalar_format) || !scalars_host ? 1 : upload_parts(n, NSLOT, 20, 22);  // (2^20: 2.44 -> 2.38 ms, 2^22: 8.61 -> 6.91; 2^19: slower)
   for (int k = 0; k < parts; k++)
     if (ctx->slot[k].pending) parts = 1;  // the caller has launches of its own in flight: the plain path (which reports a busy slot 0)
   if (parts > 1 && n <= ctx->n_bases) {
@@ -1403,8 +1481,9 @@ int msm_hip_run_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n
   int rc = check_run_args(ctx, scalars_dev, n);
   if (rc) return rc;
   const uint8_t* sc = static_cast<const uint8_t*>(scalars_dev);
+  const size_t sbytes = narrow_bytes(ctx->scalar_format) ? (size_t)narrow_bytes(ctx->scalar_format) : 32;  // (a vector: n x sbytes)
   return run_batch_groups(ctx, n, batch, out_xyz, [&](size_t, size_t first, size_t, const void** dev) {
-    *dev = sc + first * n * 32;
+    *dev = sc + first * n * sbytes;
     return (int)MSM_HIP_OK;
   });
 }
@@ -1418,7 +1497,7 @@ int msm_hip_run_batch(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, s
     return MSM_HIP_OK;
   }
   ON_DEVICE(ctx);
-  const size_t vec = n * 32, entry = vec * batch_group(ctx, n, batch);
+  const size_t vec = n * (narrow_bytes(ctx->scalar_format) ? (size_t)narrow_bytes(ctx->scalar_format) : 32), entry = vec * batch_group(ctx, n, batch);
   if (entry * NSLOT > ctx->cap_batch_stage) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->cap_batch_stage = 0;
@@ -1738,7 +1817,7 @@ int msm_hip_set_stage_timing(msm_hip_ctx* ctx, int level) {
 }
 
 int msm_hip_set_scalar_format(msm_hip_ctx* ctx, uint32_t format) {
-  if (!ctx || (format != MSM_HIP_SCALARS_CANONICAL && format != MSM_HIP_SCALARS_MONT256)) return MSM_HIP_ERR_INVALID_ARG;
+  if (!ctx || (format != MSM_HIP_SCALARS_CANONICAL && format != MSM_HIP_SCALARS_MONT256 && !narrow_bytes(format))) return MSM_HIP_ERR_INVALID_ARG;
   if (format == MSM_HIP_SCALARS_MONT256 && !ctx->ops->scalars_from_mont256) return MSM_HIP_ERR_INVALID_ARG;
   ctx->scalar_format = format;
   return MSM_HIP_OK;
@@ -1798,6 +1877,8 @@ int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n) {
   ctx->fine_hist_min_n = n;
   return MSM_HIP_OK;
 }
+
+int msm_hip_test_skew_credit(const msm_hip_ctx* ctx) { return ctx ? ctx->skew_credit : MSM_HIP_ERR_INVALID_ARG; }
 
 int msm_hip_set_debug(msm_hip_ctx* ctx, int keep_digit_planes) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;

@@ -45,18 +45,21 @@ constexpr int JAC_WORDS = 3 * CW;   // a Jacobian record x || y || z: 96 B (144 
 // additions per point for 16 x / 4 x fewer buckets.  The host picks C from n (msm_hip.hip: pick_window_bits).
 // SW = words per scalar the recode reads: 8 (a 254-bit scalar) or 4 (one 127-bit half of the endomorphism split, csrc/glv.h:
 // magnitude in bits 0 .. 126, sign in bit 127).
-template <int C, int SW = 8>
+// NB != 0: narrow scalars (MSM_HIP_SCALARS_U8 .. U64) of NB bytes, unsigned, in SW = 1 (NB <= 4) or 2 (NB = 8) words: 8 NB bits, and
+// NWIN = (8 NB + C) / C windows -- 1 / 2 / 3 / 5 at 16 bits; the top window of U16 .. U64 holds only the recode's carry.
+template <int C, int SW = 8, int NB = 0>
 struct WinCfg {
   static_assert((C >= 10 && C <= 16) || (C >= 17 && C <= 20), "window bits (17 .. 20: the digits of the wide fixed-base tables, k_count_wide)");
-  static_assert(SW == 8 || SW == 4, "scalar words");
+  static_assert(NB ? (SW == (NB + 3) / 4 && (NB == 1 || NB == 2 || NB == 4 || NB == 8)) : (SW == 8 || SW == 4), "scalar words");
   static constexpr int BITS = C;
-  static constexpr int SBITS = SW == 8 ? 254 : 127;        // bits of the scalar (magnitude)
+  static constexpr int SBITS = NB ? 8 * NB : SW == 8 ? 254 : 127;  // bits of the scalar (magnitude)
   static constexpr int NWIN = (SBITS + C) / C;             // 16: 16 | 8, 14: 19 | 10, 12: 22 | 11
   static constexpr int HALF = 1 << (C - 1);                // bucket slots per window
   static constexpr int TBITS = NWIN * C;                   // bits of the biased scalar that carry digits
   static constexpr int WORDS = (TBITS + 31) / 32;          // 8 or 9 | 4 or 5
 };
 __host__ __device__ constexpr int nwin_of(int bits, bool halves = false) { return ((halves ? 127 : 254) + bits) / bits; }
+__host__ __device__ constexpr int narrow_nwin_of(int bits, int nb) { return (8 * nb + bits) / bits; }  // windows of an nb-byte narrow scalar
 
 // (exponent tables live in constant memory; filled from the generated constexpr arrays)
 template <int N>
@@ -296,28 +299,40 @@ constexpr int FINE = HALF / NCOARSE;  // 256 slots per coarse bin
 // 105-112), and the carry out of bit 255 is its "final carry".  Each window's digit is then read independently.
 // The same for C-bit windows: the bias constant has bit C w + C - 1 set for every window w (word i of it below), the biased
 // scalar t has WinCfg<C>::WORDS words, and the recode overflows iff t has a bit at or above C * NWIN.
-template <int C, int SW = 8>
+template <int C, int SW = 8, int NB = 0>
 __host__ __device__ constexpr uint32_t bias_word(int i) {
   uint32_t v = 0;
-  for (int w = 0; w < WinCfg<C, SW>::NWIN; w++) {
+  for (int w = 0; w < WinCfg<C, SW, NB>::NWIN; w++) {
     const int bit = C * w + C - 1;
     if (bit / 32 == i) v |= 1u << (bit % 32);
   }
   return v;
 }
-template <int C, int SW = 8>
-__device__ __forceinline__ uint32_t bias_scalar(const uint32_t s[SW], uint32_t t[WinCfg<C, SW>::WORDS]) {
-  constexpr int WORDS = WinCfg<C, SW>::WORDS;
+template <int C, int SW = 8, int NB = 0>
+__device__ __forceinline__ uint32_t bias_scalar(const uint32_t s[SW], uint32_t t[WinCfg<C, SW, NB>::WORDS]) {
+  constexpr int WORDS = WinCfg<C, SW, NB>::WORDS;
   uint64_t c = 0;
 #pragma unroll
   for (int i = 0; i < WORDS; i++) {
-    c += (uint64_t)(i < SW ? s[i] : 0u) + bias_word<C, SW>(i);
+    c += (uint64_t)(i < SW ? s[i] : 0u) + bias_word<C, SW, NB>(i);
     t[i] = (uint32_t)c;
     c >>= 32;
   }
-  // 1: the recode does not fit NWIN windows ("final carry is 1", test/utils.rs:150-152)
-  if constexpr (WinCfg<C, SW>::TBITS == 32 * WORDS) return (uint32_t)c;
-  else return (t[WORDS - 1] >> (WinCfg<C, SW>::TBITS - 32 * (WORDS - 1))) != 0u ? 1u : 0u;
+  // 1: the recode does not fit NWIN windows ("final carry is 1", test/utils.rs:150-152; never for a narrow scalar: NWIN C > 8 NB)
+  if constexpr (WinCfg<C, SW, NB>::TBITS == 32 * WORDS) return (uint32_t)c;
+  else return (t[WORDS - 1] >> (WinCfg<C, SW, NB>::TBITS - 32 * (WORDS - 1))) != 0u ? 1u : 0u;
+}
+// scalar i of a vector of narrow NB-byte scalars (unsigned little-endian, packed: the vector is n x NB bytes), zero-extended into SW words
+template <int NB>
+__device__ __forceinline__ void ld_narrow(const uint8_t* v, size_t i, uint32_t s[(NB + 3) / 4]) {
+  if constexpr (NB == 1) s[0] = v[i];
+  else if constexpr (NB == 2) s[0] = reinterpret_cast<const uint16_t*>(v)[i];
+  else if constexpr (NB == 4) s[0] = reinterpret_cast<const uint32_t*>(v)[i];
+  else {
+    const uint2 a = reinterpret_cast<const uint2*>(v)[i];
+    s[0] = a.x;
+    s[1] = a.y;
+  }
 }
 // the recode's input: a scalar (8 words) or one half of the endomorphism split (4 words; `neg` receives its sign)
 template <int SW>
@@ -428,13 +443,15 @@ __global__ void __launch_bounds__(256) k_scalars_from_mont256(const uint32_t* __
 // INTERLEAVED positions, so that a tile of positions is a tile of scalars and one LDS histogram serves both halves.  The halves go to
 // `halves_out` (position p at word 4 p: the same 32 B the scalar took) for k_scatter_coarse<C, 4>; negbits[v][h][n / 128 rounded up]: bit j of
 // half h's array is the sign of half h of scalar j.
-template <int C, int SW, bool SPLIT = false>
+// NB != 0 (narrow scalars, MSM_HIP_SCALARS_U8 .. U64): `scalars` holds nvec x n x NB packed bytes, `vec_stride` counts BYTES, SW = (NB + 3) / 4.
+template <int C, int SW, bool SPLIT = false, int NB = 0>
 __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
                                                int w_begin, int w_count, int nvec, size_t vec_stride,
                                                uint32_t* __restrict__ counts, uint16_t* __restrict__ planes, int plane_mode,
                                                uint64_t* __restrict__ negbits, uint32_t* __restrict__ halves_out,
                                                uint32_t* __restrict__ err, size_t merge_nb) {
   static_assert(!SPLIT || SW == 4, "the split produces 4-word halves");
+  static_assert(!SPLIT || NB == 0, "narrow scalars are never split");
   // merge_nb != 0 (fixed-base tables, see k_precompute_tables): every window of vector v feeds ONE bucket set, local window v
   // grid (tiles, nvec): a workgroup counts one tile of ONE scalar vector (round 4: with the vectors looped over inside the workgroup a
   // grouped launch of small MSMs kept a quarter of the CUs busy -- 64 tiles at 2^16 -- for nvec times as long)
@@ -451,7 +468,7 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
   // one recoded input: histogram and plane entries of its local windows
   auto emit = [&](int v, size_t pos, const uint32_t* tb, uint32_t neg) {
 #pragma unroll
-    for (int w = 0; w < WinCfg<C, SW>::NWIN; w++) {
+    for (int w = 0; w < WinCfg<C, SW, NB>::NWIN; w++) {
       const int lw = w - w_begin;
       if (lw >= 0 && lw < w_count) {
         const int le = merge_nb ? v : v * w_count + lw;
@@ -497,6 +514,16 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
           bad |= bias_scalar<C, 4>(s, tb);
           emit(v, 2 * j + hh, tb, h[hh][3] >> 31);
         }
+      }
+    } else if constexpr (NB != 0) {
+      const uint8_t* nv = reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride;
+      for (size_t i0 = base; i0 < end; i0 += 256) {
+        const size_t i = i0 + tid;
+        if (i >= end) continue;
+        uint32_t s[SW], tb[WinCfg<C, SW, NB>::WORDS];
+        ld_narrow<NB>(nv, i, s);
+        (void)bias_scalar<C, SW, NB>(s, tb);  // (every unsigned NB-byte value fits: no input is rejected)
+        emit(v, i, tb, 0u);
       }
     } else {
       for (size_t i0 = base; i0 < end; i0 += 256) {
@@ -588,8 +615,9 @@ constexpr int SCAT_SUB = 2048;  // scalars staged per block iteration (8 per thr
 // declared statically, three workgroups fitted a CU whatever the launch's size; the half-scalar form is held to 128 registers (four waves per SIMD):
 // 1290 -> 1148 us at 2^24.  (Tried and dropped: splitting the scalars again here instead of reading the halves the first pass wrote -- 1 GB less
 // traffic at 2^24, and 1522 us instead of 1148 with the first pass no faster: profiles/r05_sort.txt.)
-template <int C, int SW>
-__global__ void __launch_bounds__(256, (SW == 4 ? 4 : 1)) k_scatter_coarse(const uint32_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len,
+// NB != 0: narrow scalars (the layout of k_count<C, SW, false, NB>; vec_stride in bytes)
+template <int C, int SW, int NB = 0>
+__global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_coarse(const uint32_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len,
                                                         uint32_t tiles, int w_begin, int w_count, int nvec, size_t vec_stride,
                                                         const uint32_t* __restrict__ counts,
                                                         const uint32_t* __restrict__ bin_total, uint32_t* __restrict__ coarse_ptr,
@@ -600,6 +628,7 @@ __global__ void __launch_bounds__(256, (SW == 4 ? 4 : 1)) k_scatter_coarse(const
   // 282 VGPRs + 26 AGPRs at 16 bits (one wave per SIMD) and a 304-byte scratch object at 12 bits (round 3)
   constexpr int PER = SW == 8 ? 4 : 8;
   constexpr int SUB = 256 * PER;
+  using Cfg = WinCfg<C, SW, NB>;
   static_assert(SUB <= SCAT_SUB, "LDS staging arrays");
   // SW = 4 (endomorphism halves, interleaved by k_count<C, 4, true>): input 2 j is k1 of scalar j and multiplies base j; input 2 j + 1 is
   // k2 and multiplies phi(P_j), record half_shift = n_bases + j
@@ -650,8 +679,7 @@ __global__ void __launch_bounds__(256, (SW == 4 ? 4 : 1)) k_scatter_coarse(const
   const size_t tile_end = tile_base + tile_len < n ? tile_base + tile_len : n;
   for (size_t sub = tile_base; sub < tile_end; sub += SUB) {
     // this thread's PER biased scalars stay in registers; every window's digit code is read from them
-    const uint32_t* sv = scalars + (size_t)v * vec_stride;
-    uint32_t sc[PER][WinCfg<C, SW>::WORDS];
+    uint32_t sc[PER][Cfg::WORDS];
     uint32_t negs = 0;  // bit j: scalar j is a negative half (its digits' signs are flipped)
 #pragma unroll
     for (int j = 0; j < PER; j++) {
@@ -659,12 +687,16 @@ __global__ void __launch_bounds__(256, (SW == 4 ? 4 : 1)) k_scatter_coarse(const
       uint32_t raw[SW], neg = 0;
 #pragma unroll
       for (int k = 0; k < SW; k++) raw[k] = 0;  // an all-zero scalar recodes to all-zero digits: no entries
-      if (i < tile_end) ld_scalar<SW>(sv + i * SW, raw, neg);
+      if constexpr (NB != 0) {
+        if (i < tile_end) ld_narrow<NB>(reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride, i, raw);
+      } else {
+        if (i < tile_end) ld_scalar<SW>(scalars + (size_t)v * vec_stride + i * SW, raw, neg);
+      }
       negs |= neg << j;
-      (void)bias_scalar<C, SW>(raw, sc[j]);
+      (void)bias_scalar<C, SW, NB>(raw, sc[j]);
     }
 #pragma unroll
-    for (int w = 0; w < WinCfg<C, SW>::NWIN; w++) {
+    for (int w = 0; w < Cfg::NWIN; w++) {
       if (w < w_begin || w >= w_begin + w_count) continue;  // block-uniform
       // fixed-base tables: window w of point i is table entry w * merge_nb + i, and all windows share local window v
       const int lw = merge_nb ? v : v * w_count + (w - w_begin);
@@ -708,6 +740,132 @@ __global__ void __launch_bounds__(256, (SW == 4 ? 4 : 1)) k_scatter_coarse(const
       __syncthreads();
     }
   }
+}
+
+// ---- byte windows (narrow U8 / U16 scalars: MSM_HIP_SCALARS_U8, MSM_HIP_SCALARS_U16) -------------------------------------------------------
+// A window is one byte of the scalar (U8: 1 window, U16: 2 -- low byte, high byte), its digit the byte itself: unsigned, bucket slot = value
+// (1 .. 255; a zero byte emits no entry).  With 256 slots a one-level counting sort suffices -- no coarse bins, so a few-distinct-values vector
+// (booleans: every entry in slot 1) never meets k_sort_fine's huge-bin fallback.  The four kernels leave exactly what k_sort_fine leaves:
+// val_idxs grouped by slot (point index, sign bit 0), col_ptr over the launch's whole bucket grid (slots 256 .. half hold the window's total:
+// empty), the SMVP's chunk table and chunk-length word.  Everything behind them (SMVP, stitch, bucket reduce on the 12-bit grid) is unchanged;
+// the host weighs window j by 2^(8 j).  No field arithmetic: instantiated once, in BN254's unit.
+// Layouts: counts[lw][tile][256] and bin_total[lw][256] in the arrays of the coarse sort, which hold BYTE_MAXLW windows of 256 bins.
+constexpr int BYTE_BINS = 256;
+constexpr int BYTE_MAXLW = MAXLW * NCOARSE / BYTE_BINS;  // local windows a byte-window launch may carry (32)
+template <int NB>
+__device__ __forceinline__ uint32_t ld_byte_scalar(const uint8_t* v, size_t i) {
+  static_assert(NB == 1 || NB == 2, "byte windows: U8 / U16");
+  if constexpr (NB == 1) return v[i];
+  else return reinterpret_cast<const uint16_t*>(v)[i];
+}
+// counting pass: grid (tiles, nvec); a 256-bin LDS histogram per (tile, window).  scalars: nvec x n x NB bytes.
+template <int NB>
+__global__ void __launch_bounds__(256) k_byte_count(const uint8_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
+                                                    uint32_t* __restrict__ counts) {
+  __shared__ uint32_t hist[NB * BYTE_BINS];
+  const int tid = threadIdx.x, v = blockIdx.y;
+#pragma unroll
+  for (int j = 0; j < NB; j++) hist[j * BYTE_BINS + tid] = 0;
+  __syncthreads();
+  const uint8_t* sv = scalars + (size_t)v * n * NB;
+  const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
+  for (size_t i = base + tid; i < end; i += 256) {
+    const uint32_t s = ld_byte_scalar<NB>(sv, i);
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const uint32_t b = (s >> (8 * j)) & 0xffu;
+      if (b) atomicAdd(&hist[j * BYTE_BINS + b], 1u);
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NB; j++) counts[((size_t)(v * NB + j) * tiles + blockIdx.x) * BYTE_BINS + tid] = hist[j * BYTE_BINS + tid];
+}
+// scan over the tiles: one wave per (window, bin) -- counts[lw][tile][bin] becomes the bin's entries in earlier tiles, bin_total[lw][bin] its size
+__global__ void __launch_bounds__(256) k_byte_scan(uint32_t* __restrict__ counts, uint32_t tiles, uint32_t* __restrict__ bin_total) {
+  const int lw = blockIdx.y, lane = threadIdx.x & 63;
+  const int bin = blockIdx.x * 4 + (threadIdx.x >> 6);
+  uint32_t* c = counts + (size_t)lw * tiles * BYTE_BINS + bin;
+  uint32_t run = 0;
+  for (uint32_t t0 = 0; t0 < tiles; t0 += 64) {
+    const uint32_t t = t0 + lane;
+    const uint32_t v = t < tiles ? c[(size_t)t * BYTE_BINS] : 0u;
+    uint32_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t y = __shfl_up(x, off);
+      if (lane >= off) x += y;
+    }
+    if (t < tiles) c[(size_t)t * BYTE_BINS] = run + x - v;
+    run += __shfl(x, 63);
+  }
+  if (lane == 0) bin_total[lw * BYTE_BINS + bin] = run;
+}
+// scatter pass: grid (tiles, nvec).  Every workgroup turns its windows' 256 bin totals into slot starts; workgroup (0, v) publishes col_ptr of
+// vector v's windows over the whole grid of `half` slots, workgroup (0, 0) the launch's SMVP chunk length (the fullest of its w_count windows).
+// Entries are placed with LDS cursors (order within a slot: unspecified, as everywhere).
+template <int NB>
+__global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len, uint32_t tiles,
+                                                      int w_count, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ bin_total,
+                                                      uint32_t* __restrict__ col_ptr, uint32_t half, uint32_t* __restrict__ val_idxs,
+                                                      uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev) {
+  __shared__ uint32_t cur[NB * BYTE_BINS];
+  __shared__ uint32_t wave_tot[4];
+  __shared__ uint32_t wtotal, max_total;
+  const int tid = threadIdx.x, v = blockIdx.y;
+  if (tid == 0) max_total = 0;
+  for (int j = 0; j < NB; j++) {
+    const int lw = v * NB + j;
+    const uint32_t bt = bin_total[lw * BYTE_BINS + tid];
+    const uint32_t excl = block_excl_scan_256(bt, wave_tot);
+    cur[j * BYTE_BINS + tid] = excl + counts[((size_t)lw * tiles + blockIdx.x) * BYTE_BINS + tid];
+    if (tid == BYTE_BINS - 1) wtotal = excl + bt;
+    __syncthreads();
+    if (blockIdx.x == 0) {
+      uint32_t* cp = col_ptr + (size_t)lw * (half + 1);
+      cp[tid] = excl;  // (slot 0: no entries, start 0)
+      for (uint32_t k = BYTE_BINS + tid; k <= half; k += 256) cp[k] = wtotal;
+    }
+    __syncthreads();
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0) {  // the chunk length: the fullest window of the launch spread over all `chunks` lanes
+    for (int lw = 0; lw < w_count; lw++) {
+      const uint32_t excl = block_excl_scan_256(bin_total[lw * BYTE_BINS + tid], wave_tot);
+      if (tid == BYTE_BINS - 1) atomicMax(&max_total, excl + bin_total[lw * BYTE_BINS + tid]);
+    }
+    __syncthreads();
+    if (tid == 0) *chunk_len_dev = smvp_chunk_len(max_total, chunks, host_chunk_len);
+  }
+  const uint8_t* sv = scalars + (size_t)v * n * NB;
+  const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
+  for (size_t i = base + tid; i < end; i += 256) {
+    const uint32_t s = ld_byte_scalar<NB>(sv, i);
+#pragma unroll
+    for (int j = 0; j < NB; j++) {
+      const uint32_t b = (s >> (8 * j)) & 0xffu;
+      if (b) val_idxs[(size_t)(v * NB + j) * stride + atomicAdd(&cur[j * BYTE_BINS + b], 1u)] = (uint32_t)i;
+    }
+  }
+}
+// the SMVP's chunk table: chunk c of window lw starts at entry c * chunk_len; its slot is the last of 1 .. 255 whose run starts at or before it
+__global__ void __launch_bounds__(256) k_byte_chunks(const uint32_t* __restrict__ col_ptr, uint32_t half, uint32_t chunks,
+                                                     const uint32_t* __restrict__ chunk_len_dev, uint32_t* __restrict__ chunk_slot) {
+  __shared__ uint32_t cp[BYTE_BINS + 1];
+  const int lw = blockIdx.y, tid = threadIdx.x;
+  const uint32_t* src = col_ptr + (size_t)lw * (half + 1);
+  cp[tid] = src[tid];
+  if (tid == 0) cp[BYTE_BINS] = src[BYTE_BINS];
+  __syncthreads();
+  const uint32_t c = blockIdx.x * 256 + tid;
+  const uint64_t e = (uint64_t)c * *chunk_len_dev;
+  if (c >= chunks || e >= cp[BYTE_BINS]) return;
+  uint32_t lo = 1, hi = BYTE_BINS - 1;  // cp[lo] <= e (cp[1] = 0); find the largest such slot
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (cp[mid] <= e) lo = mid;
+    else hi = mid - 1;
+  }
+  chunk_slot[(size_t)lw * chunks + c] = lo;
 }
 
 // ---- wide fixed-base tables (round 4; SURVEY.md 8f-2, MSM_HIP_BASES_PRECOMPUTE_WIDE) ------------------------------------------------
