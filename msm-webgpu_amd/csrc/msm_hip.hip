@@ -15,12 +15,14 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <type_traits>
 
 #define MSM_HIP_TEST_HOOKS 1
 #include "../../include/msm_hip.h"
@@ -85,12 +87,37 @@ constexpr int NREDUCE = 2;  // reduce streams (slot k uses stream k % NREDUCE): 
                             // then owns 3 streams; streams beyond the process's hardware queues (GPU_MAX_HW_QUEUES) share
                             // them: correct, with less overlap.
 
+// What a launch is made of, decided once from its request (plan_launch) and read by its buffer sizing (ensure_work), both stages of its enqueue
+// (enqueue_sort, enqueue_reduce), the host finish and the stage read-back hooks
+struct LaunchPlan {
+  LaunchMode mode = MODE_PLAIN;
+  int nb = 0;                         // MODE_NARROW: bytes per scalar
+  size_t n = 0, base_off = 0;         // point i of the launch is base base_off + i
+  int nvec = 1;                       // scalar vectors (contiguous) of the launch
+  int w_begin = 0, w_count_vec = 0;   // windows [w_begin, w_begin + w_count_vec) of every vector, in the request's window bits (MODE_WIDE: the T digits)
+  int wide_bits = 0;                  // MODE_WIDE: the tables' digit width
+  int v_begin = 0, v_count = 0;       // MODE_WIDE: virtual windows [v_begin, v_begin + v_count) of every vector (whole MSMs: all of them)
+  bool pairs = false;                 // MODE_WIDE, a share of the virtual windows: the launch leaves (window sum, plain total) record pairs
+  uint32_t* sums_dev = nullptr;       // device window sums; null: the slot's own buffer, and from there the host
+  int wbits = WBITS;                  // window bits of everything behind the recode (MODE_WIDE: 16)
+  uint32_t half = 0, ncoarse = 0;     // bucket slots per window; coarse bins that can hold entries
+  int w_count = 0;                    // local windows (bucket sets) of the launch
+  int nwin = 0, combine_bits = 0;     // host finish: window sums per MSM, and the bits between consecutive windows
+  bool whole = false;                 // every vector's windows make a whole MSM that the host finish can combine
+  size_t n_sc = 0, n_entries = 0;     // inputs of the recode; entries one local window may receive
+  int full_windows = 0;               // windows of one whole MSM in this mode: the sort arrays are sized for at least that many
+  bool digits = false;                // the first pass keeps the digit planes for the debug read-back
+  bool planes = false, share_shape = false, list_path = false;  // use_planes; the share kernels of the wide tables (k_scatter_wide<C, true>, k_scatter_list)
+  uint32_t tiles = 0, tile_len = 0, subtiles = 0;  // tiles of scalars of the two global sort passes; LIST_SUB sub-tiles
+  uint32_t chunks = 0, chunk_len = 0;              // SMVP chunks per local window and their (longest) length
+  size_t stride = 0;                               // per-window stride of the entry arrays
+};
+
 struct Slot {
   uint8_t* h_wsums = nullptr;      // pinned: MAXLW x 96 B window sums + 4 B error word
   uint8_t* d_wsums = nullptr;      // device: MAXLW x 96 B window sums + 4 B error word
   uint32_t* d_buckets = nullptr;   // [cap_lw][32768] XYZZ records
   size_t cap_buckets = 0;          // bucket records d_buckets holds (local windows x slots per window of the largest launch seen)
-  int wbits = WBITS;               // window bits of the launch in this slot
   uint32_t* d_partials = nullptr;  // bucket-reduce scratch: [W][256] row sums, [W][256] column sums, [W][3] parts (XYZZ)
   uint32_t* d_col_ptr = nullptr;   // [W][32769] start of every bucket slot's run in the sorted entry list
   uint32_t* d_heads = nullptr;     // [W][chunks] XYZZ records: SMVP pieces of runs that cross chunk boundaries
@@ -106,16 +133,9 @@ struct Slot {
   size_t cap_recs = 0;                        // capacity (records) of d_heads / d_tails
   bool ready = false;                         // small buffers + events exist (slots are set up on first use)
   bool timed = false, pending = false, to_host = false;
-  bool merged = false;                        // fixed-base launch: one bucket set (one window sum) per scalar vector
-  bool halves = false;                        // endomorphism launch: the windows are those of 127-bit halves
-  int wide_bits = 0;                          // wide fixed-base launch (its digit width): h_wsums holds the bit-plane sums of the virtual windows (combine_wide)
   bool parts = false;                         // h_wsums holds the bit-plane sums of every window (k_bpr_planes): the host finishes the window sums
-  bool pairs = false;                         // a share of the wide tables' virtual windows: the launch leaves (window sum, plain total) record pairs
-  int narrow = 0;                             // narrow-scalar launch: bytes per scalar (its windows: narrow_windows(wbits, narrow))
   int timing_level = 0;
-  int w_begin = 0, w_count = 0, nvec = 1;  // windows [w_begin, w_begin + w_count) of nvec scalar vectors
-  size_t n = 0;
-  size_t base_off = 0;  // first base of this launch (records): point i of the launch is base base_off + i
+  LaunchPlan plan;                            // the launch in this slot
 };
 
 }  // namespace
@@ -162,7 +182,6 @@ struct msm_hip_ctx {
   hipEvent_t bases_ready = nullptr;     // the one-shot entry point: the last chunk of the bases has been converted (conversion stream -> main stream)
   hipEvent_t chunk_landed[8] = {};      // ... and chunk k of the wire bytes has landed (copy stream -> conversion stream)
   size_t cap_entries = 0;  // capacity of the entry arrays (tmp_val, tmp_fine, val): local windows x per-window stride
-  size_t last_stride = 0;  // per-window stride of the last launch (n rounded up to a multiple of 4)
   size_t cap_chunk_slot = 0;  // capacity (records) of d_chunk_slot
   uint8_t* d_batch_stage = nullptr;   // staging ring (NSLOT vectors) of msm_hip_run_batch, allocated on first use
   size_t cap_batch_stage = 0;
@@ -193,10 +212,8 @@ struct msm_hip_ctx {
   size_t cap_stage = 0;
 
   Slot slot[NSLOT];
-  // description of the last launched run (for the stage read-back hooks)
-  size_t last_n = 0;
-  int last_w_count = 0, last_slot = 0, last_wbits = WBITS;
-  bool last_has_digits = false;
+  LaunchPlan last;  // the last launch that enqueued kernels, and its slot (for the stage read-back hooks)
+  int last_slot = 0;
   float stage_ms[10] = {};
 };
 
@@ -221,15 +238,20 @@ int dev_alloc(msm_hip_ctx* ctx, T*& p, size_t count) {
   return MSM_HIP_OK;
 }
 
-int ensure_stage(msm_hip_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->cap_stage) return MSM_HIP_OK;
-  int rc = dev_alloc(ctx, ctx->d_stage, bytes);
-  if (rc) {
-    ctx->cap_stage = 0;
-    return rc;
-  }
-  ctx->cap_stage = bytes;
+// Grow a pooled buffer set of capacity `cap` (in the caller's unit) to `size`: `alloc(size)` (re)allocates every buffer of the set, and `cap` reads 0
+// until all of them exist.  `sync`: a context-wide set that the main stream may still be using -- wait for it first.
+template <typename Alloc>
+int grow(msm_hip_ctx* ctx, size_t& cap, size_t size, bool sync, Alloc alloc) {
+  if (size <= cap) return MSM_HIP_OK;
+  if (sync) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  cap = 0;
+  if (const int rc = alloc(size)) return rc;
+  cap = size;
   return MSM_HIP_OK;
+}
+
+int ensure_stage(msm_hip_ctx* ctx, size_t bytes) {
+  return grow(ctx, ctx->cap_stage, bytes, false, [&](size_t c) { return dev_alloc(ctx, ctx->d_stage, c); });
 }
 
 // entries per SMVP lane: about SMVP_TARGET_LANES lanes over all windows of the run, within the kernel's limits
@@ -434,64 +456,56 @@ int setup_slot(msm_hip_ctx* ctx, Slot& s) {
   return MSM_HIP_OK;
 }
 
-// make the pools fit a launch of `w_count` local windows (vectors x windows) over n points into slot `s` (not pending)
-// (`full_windows`: the windows of one whole MSM in the launch's mode -- the sort arrays are sized for at least that many)
-// (`recs_override`: the launch's own count of SMVP lanes, where it is not the one n entries per window give -- wide fixed-base launches)
-int ensure_work(msm_hip_ctx* ctx, size_t n, int w_count, int wbits, int full_windows, Slot& s, bool planes, size_t recs_override = 0) {
+// make the pools fit launch `p` into slot `s` (set up, not pending).  The sort arrays are sized for at least one whole MSM in the launch's mode
+// (p.full_windows) over up to p.n_entries entries per window.
+int ensure_work(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   int rc;
-  if ((rc = setup_slot(ctx, s))) return rc;
-  const size_t need_recs = recs_override ? recs_override : (size_t)w_count * chunks_for(n, chunk_len_for(n, w_count));
-  const size_t need_entries = stride_for(n) * (size_t)w_count;
-  if ((planes || ctx->debug) && need_entries > ctx->cap_planes) {  // digit planes (main stream only, like the sort arrays)
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    size_t entries = stride_for(n) * (size_t)full_windows;
-    if (entries < need_entries) entries = need_entries;
-    if (entries < ctx->cap_entries) entries = ctx->cap_entries;
-    ctx->cap_planes = 0;
-    if ((rc = dev_alloc(ctx, ctx->d_digits, entries))) return rc;
-    if ((rc = dev_alloc(ctx, ctx->d_negbits, entries / 64 + 2 * MAXLW))) return rc;
-    ctx->cap_planes = entries;
-  }
+  const size_t n = p.n_entries;
+  const size_t need_recs = (size_t)p.w_count * p.chunks;
+  const size_t need_entries = p.stride * (size_t)p.w_count;
+  const size_t entries = std::max(p.stride * (size_t)p.full_windows, need_entries);  // any single MSM over up to n entries per window
+  if ((p.planes || ctx->debug) && need_entries > ctx->cap_planes &&  // digit planes (main stream only, like the sort arrays)
+      (rc = grow(ctx, ctx->cap_planes, std::max(entries, ctx->cap_entries), true, [&](size_t c) {
+         const int r = dev_alloc(ctx, ctx->d_digits, c);
+         return r ? r : dev_alloc(ctx, ctx->d_negbits, c / 64 + 2 * MAXLW);
+       })))
+    return rc;
   if (need_entries > ctx->cap_entries || need_recs > ctx->cap_chunk_slot) {
     // growing the context-wide sort arrays (main stream only): nothing may still be running on them
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    size_t entries = stride_for(n) * (size_t)full_windows;  // any single MSM over up to n entries per window
-    if (entries < need_entries) entries = need_entries;
-    if (entries > ctx->cap_entries) {
-      ctx->cap_entries = 0;
-      if ((rc = dev_alloc(ctx, ctx->d_tmp_val, entries))) return rc;
-      if ((rc = dev_alloc(ctx, ctx->d_tmp_fine, entries))) return rc;
-      if ((rc = dev_alloc(ctx, ctx->d_val, entries))) return rc;
-      ctx->cap_entries = entries;
-    }
-    size_t recs = piece_records_for(n);
-    if (recs < need_recs) recs = need_recs;
-    if (recs > ctx->cap_chunk_slot) {
-      ctx->cap_chunk_slot = 0;
-      if ((rc = dev_alloc(ctx, ctx->d_chunk_slot, recs))) return rc;
-      ctx->cap_chunk_slot = recs;
-    }
+    if ((rc = grow(ctx, ctx->cap_entries, entries, false, [&](size_t c) {
+           int r = dev_alloc(ctx, ctx->d_tmp_val, c);
+           if (!r) r = dev_alloc(ctx, ctx->d_tmp_fine, c);
+           return r ? r : dev_alloc(ctx, ctx->d_val, c);
+         })))
+      return rc;
+    if ((rc = grow(ctx, ctx->cap_chunk_slot, std::max(piece_records_for(n), need_recs), false, [&](size_t c) { return dev_alloc(ctx, ctx->d_chunk_slot, c); })))
+      return rc;
   }
-  if (need_recs > s.cap_recs) {  // this slot's piece arrays (the slot is idle: its previous occupant was collected)
-    size_t recs = piece_records_for(n);
-    if (recs < need_recs) recs = need_recs;
-    s.cap_recs = 0;
-    if ((rc = dev_alloc(ctx, s.d_heads, recs * ctx->ops->rec_words))) return rc;
-    if ((rc = dev_alloc(ctx, s.d_tails, recs * ctx->ops->rec_words))) return rc;
-    s.cap_recs = recs;
-  }
-  const size_t need_buckets = (size_t)w_count << (wbits - 1);
-  if (need_buckets > s.cap_buckets) {  // one MSM's worth (16 x 2^15 at 16 bits) at least; larger launches grow it
-    size_t recs = (size_t)NWIN * HALF;
-    if (recs < need_buckets) recs = need_buckets;
-    s.cap_buckets = 0;
-    if ((rc = dev_alloc(ctx, s.d_buckets, recs * ctx->ops->rec_words))) return rc;
-    s.cap_buckets = recs;
-  }
+  if (need_recs > s.cap_recs &&  // this slot's piece arrays (the slot is idle: its previous occupant was collected)
+      (rc = grow(ctx, s.cap_recs, std::max(piece_records_for(n), need_recs), false, [&](size_t c) {
+         const int r = dev_alloc(ctx, s.d_heads, c * ctx->ops->rec_words);
+         return r ? r : dev_alloc(ctx, s.d_tails, c * ctx->ops->rec_words);
+       })))
+    return rc;
+  const size_t need_buckets = (size_t)p.w_count << (p.wbits - 1);
+  if (need_buckets > s.cap_buckets &&  // one MSM's worth (16 x 2^15 at 16 bits) at least; larger launches grow it
+      (rc = grow(ctx, s.cap_buckets, std::max((size_t)NWIN * HALF, need_buckets), false, [&](size_t c) { return dev_alloc(ctx, s.d_buckets, c * ctx->ops->rec_words); })))
+    return rc;
   if (n >= ctx->fine_hist_min_n && !ctx->d_part_hist) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = dev_alloc(ctx, ctx->d_part_hist, (size_t)MAXLW * NCOARSE * FINE_SPLIT * FINE))) return rc;
   }
+  const size_t scalars = (size_t)p.nvec * p.n;
+  if (p.pairs &&  // the list lengths of a share's first pass
+      (rc = grow(ctx, ctx->cap_list_len, (size_t)p.w_count * p.subtiles, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_list_len, c); })))
+    return rc;
+  if (p.mode == MODE_HALVES && !p.planes &&  // (the halves as an array: only when the second pass reads them)
+      (rc = grow(ctx, ctx->cap_halves, scalars, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_halves, c * 8); })))
+    return rc;
+  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb &&
+      (rc = grow(ctx, ctx->cap_scalar_conv, scalars, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_scalar_conv, c * 8); })))
+    return rc;
   return MSM_HIP_OK;
 }
 
@@ -557,35 +571,277 @@ inline bool use_planes(const msm_hip_ctx* ctx, LaunchMode mode, int w_count_vec,
   return w_count_vec <= max_w && w_count_vec < nwin_of(wbits, mode == MODE_HALVES);
 }
 
-// Enqueue one MSM (windows [w_begin, w_begin + w_count)) into slot `s`.  Window sums (canonical Jacobian bytes) go to
-// `wsums_out` (device memory; the slot's own buffer when null); the error word and, if `to_host`, the window sums are
-// copied to the slot's pinned buffer.  Returns without waiting.
-// (MODE_WIDE: `v_count` != 0 -- a SHARE of the virtual windows, [v_begin, v_begin + v_count) of every vector; its sums are (window sum, plain
-//  total) pairs, 2 records per local window.  0: whole MSMs, all 2^(C-16) virtual windows)
-// `phase`: 0 the whole launch; 1 only its recode + sort (everything that needs the scalars alone); 2 the rest, from the SMVP on (everything that
-// needs the bases) -- the one-shot entry point sorts while the bases are still being uploaded (msm_hip_msm_bn254_g1).  Phase 2 must follow
-// phase 1 of the same launch with the same arguments.
-int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, int w_count_vec, int nvec, int wbits, LaunchMode mode, Slot& s,
-            uint32_t* wsums_out, bool to_host, int v_begin = 0, int v_count = 0, int phase = 0) {
+constexpr size_t MAX_POINTS = (size_t)1 << 28;  // point indices carry the digit sign in bit 31; 2^28 keeps every per-window offset in u32
+
+int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n) {
+  if (!ctx || (!scalars && n) || n > MAX_POINTS) return MSM_HIP_ERR_INVALID_ARG;
+  if (ctx->n_bases == 0 && n) return MSM_HIP_ERR_NO_BASES;
+  if (n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  return MSM_HIP_OK;
+}
+
+// The one place a launch request is checked and shaped: windows [w_begin, w_end) -- in units of `wbits`-bit windows -- of `nvec` scalar vectors
+// into `slot`, their sums to `sums_dev` (device memory) or, when null, to the slot's pinned buffer.  Consumes ctx->launch_base_off.
+// (MODE_WIDE: called with the tables' digit width and all T digits; everything behind the recode sees local windows of 16 bits.  v_count != 0: a
+//  SHARE of the virtual windows -- [v_begin, v_begin + v_count) of every vector; its sums are (window sum, plain total) pairs, 2 records per local
+//  window.  0: whole MSMs, all 2^(C-16) virtual windows)
+int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* scalars, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
+                void* sums_dev, int v_begin, int v_count) {
   const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
   const bool pairs = wide && v_count != 0;
-  const int nb = mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;  // (launch_impl admits MODE_NARROW only under a narrow format)
-  const bool bytes = byte_windows(nb);  // U8 / U16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
+  const int nb = ctx && mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;
+  int rc = check_run_args(ctx, scalars, n);
+  const size_t base_off = ctx ? ctx->launch_base_off : 0;
+  if (ctx) ctx->launch_base_off = 0;
+  if (rc) return rc;
+  if (base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > (nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves)) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
+  // narrow scalars: whole MSMs only, over the plain records, from a pointer aligned to the scalar's size
+  if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != narrow_windows(wbits, nb) || sums_dev || base_off || nvec * w_end > narrow_max_windows(nb) ||
+                              (byte_windows(nb) && wbits != BYTE_WBITS) ||
+                              reinterpret_cast<uintptr_t>(scalars) % (uintptr_t)nb)) return MSM_HIP_ERR_INVALID_ARG;
+  if (wide && (nvec < 1 || w_begin != 0 || wbits != ctx->wide_bits || w_end != wide_tables_of(wbits))) return MSM_HIP_ERR_INVALID_ARG;
+  if (wide && !pairs && (nvec * wide_vwin_of(ctx->wide_bits) > 24 || sums_dev)) return MSM_HIP_ERR_INVALID_ARG;
+  if (pairs && (v_begin < 0 || v_count < 0 || v_begin + v_count > wide_vwin_of(ctx->wide_bits))) return MSM_HIP_ERR_INVALID_ARG;
+  if (!wide && v_count) return MSM_HIP_ERR_INVALID_ARG;
   if (wide && !pairs) v_count = wide_vwin_of(ctx->wide_bits);
-  const uint32_t half = 1u << (wbits - 1);   // bucket slots per window
-  const unsigned ncoarse = half / FINE;      // coarse bins that can hold entries
-  // fixed-base tables (`merge`): the w_count_vec windows of a vector feed one bucket set -- one local window of up to
-  // n * w_count_vec entries per vector -- whose entries index the tables (window w of point i = record w * n_bases + i)
-  // wide tables (`wide`; w_count_vec = the T digits of C bits): the same indexing; each vector's bucket set of 2^(C-1) slots is run as 2^(C-16) local
-  // ("virtual") windows of 2^15, into which the entries fall by the top bits of their digit's magnitude (msm_kernels.h: k_count_wide)
-  const size_t merge_nb = merge || wide ? ctx->n_bases : 0;
+  const int w_count_vec = w_end - w_begin;
+  // fixed-base tables (`merge`): the w_count_vec windows of a vector feed one bucket set -- one local window of up to n * w_count_vec entries per
+  // vector -- whose entries index the tables (window w of point i = record w * n_bases + i).  Wide tables: the same indexing; each vector's bucket
+  // set of 2^(C-1) slots is run as 2^(C-16) local ("virtual") windows of 2^15, into which the entries fall by the top bits of their digit's
+  // magnitude (msm_kernels.h: k_count_wide).  Otherwise local window lw = v * w_count_vec + (w - w_begin).
+  const int w_count = merge ? nvec : wide ? nvec * v_count : nvec * w_count_vec;
+  if (nvec < 1 || w_count > MAXLW) return MSM_HIP_ERR_INVALID_ARG;
+
+  p = LaunchPlan{};
+  p.mode = mode;
+  p.nb = nb;
+  p.n = n;
+  p.base_off = base_off;
+  p.nvec = nvec;
+  p.w_begin = w_begin;
+  p.w_count_vec = w_count_vec;
+  p.wide_bits = wide ? ctx->wide_bits : 0;
+  p.v_begin = v_begin;
+  p.v_count = v_count;
+  p.pairs = pairs;
+  p.sums_dev = static_cast<uint32_t*>(sums_dev);
+  p.wbits = wide ? WBITS : wbits;
+  p.half = 1u << (p.wbits - 1);
+  p.ncoarse = p.half / FINE;
+  p.w_count = w_count;
+  // fixed-base launches leave ONE sum per vector (every table already carries its power of two): nothing to combine but the copy
+  p.nwin = merge ? 1 : wide ? v_count : nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves);
+  p.combine_bits = byte_windows(nb) ? 8 : p.wbits;  // (byte windows: window j weighs 2^(8 j))
+  p.whole = !pairs && w_count_vec == (wide ? wide_tables_of(wbits) : nb ? p.nwin : nwin_of(wbits, halves));
   // endomorphism (`halves`): the recode runs over 2n halves of 16 B (the first pass splits the scalars) against 2n points -- P_i and, n_bases records
   // further on, phi(P_i) -- in half as many windows
-  const size_t n_sc = halves ? 2 * n : n;  // inputs of the recode
-  const size_t n_entries = merge || wide ? n * (size_t)w_count_vec : n_sc;  // (wide: what ONE virtual window may receive)
-  // `nvec` scalar vectors (contiguous, n x 32 B each) share this launch: local window lw = v * w_count_vec + (w - w_begin);
-  // everything after the two scalar-reading kernels only sees w_count = nvec * w_count_vec local windows
-  const int w_count = merge ? nvec : wide ? nvec * v_count : nvec * w_count_vec;
+  p.n_sc = halves ? 2 * n : n;
+  p.n_entries = merge || wide ? n * (size_t)w_count_vec : p.n_sc;  // (wide: what ONE virtual window may receive)
+  p.full_windows = wide ? wide_vwin_of(ctx->wide_bits) : merge ? 1 : halves ? nwin_of(wbits, true) : nb ? w_count_vec : NWIN;
+  p.digits = ctx->debug && !merge && !wide && !byte_windows(nb);
+  // window shares (a few of a scalar's windows per vector): the first pass leaves digit planes, the second reads them (k_scatter_planes)
+  p.planes = use_planes(ctx, mode, w_count_vec, p.wbits);
+  // shares of at most WIDE_SHARE_VWIN_MAX virtual windows of wide tables: the first pass leaves compact lists of the share's entries per sub-tile of
+  // LIST_SUB scalars (k_count_wide_list / k_scatter_list); tiles are then whole sub-tiles.  MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape (A/B aid)
+  static const bool share_lists = [] { const char* e = getenv("MSM_HIP_WIDE_SHARE_LISTS"); return !e || atoi(e) != 0; }();
+  p.share_shape = pairs && v_count <= WIDE_SHARE_VWIN_MAX;
+  p.list_path = p.share_shape && share_lists;
+  // tiles of scalars for the two global sort passes: >= 2048 scalars each, at most MAX_TILES of them
+  const uint32_t tile_unit = p.list_path ? (uint32_t)LIST_SUB : 256u;
+  p.tile_len = 2048;
+  if ((p.n_sc + p.tile_len - 1) / p.tile_len > MAX_TILES) p.tile_len = (uint32_t)((((p.n_sc + MAX_TILES - 1) / MAX_TILES) + tile_unit - 1) / tile_unit * tile_unit);
+  p.tiles = (uint32_t)((p.n_sc + p.tile_len - 1) / p.tile_len);
+  p.subtiles = (uint32_t)((p.n_sc + LIST_SUB - 1) / LIST_SUB);
+  if (wide) {
+    const WideShape ws = wide_shape(n, ctx->curve, ctx->wide_bits, w_count);
+    p.chunk_len = ws.host_len;  // (the longest the device may pick: smvp_chunk_len)
+    p.chunks = ws.chunks;
+  } else {
+    p.chunk_len = chunk_len_for(p.n_entries, w_count);
+    p.chunks = chunks_for(p.n_entries, p.chunk_len);
+  }
+  p.stride = stride_for(p.n_entries);
+  return MSM_HIP_OK;
+}
+
+// f(std::integral_constant<decltype(V), V>{}) for the V among V0, Vs... that equals the runtime value `v` -- the last one for any other value:
+// a kernel template is instantiated for exactly the values listed
+template <auto V0, auto... Vs, typename F>
+void dispatch(decltype(V0) v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<decltype(V0), V0>{});
+  else if (v == V0) f(std::integral_constant<decltype(V0), V0>{});
+  else dispatch<Vs...>(v, f);
+}
+
+// The launch's first stage, on the main stream: everything that needs the scalars alone -- recode, the two sort passes and the fine sort (+ the
+// debug read-back's ordering).  The slot's previous occupant (bucket reduce + copies on the reduce stream) must have drained; its error word was
+// re-zeroed at the end of that chain.  Stage events cost a few microseconds of queue time each, so only the ones the current timing level asks
+// for are recorded.
+int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t* d_scalars) {
+  const bool merge = p.mode == MODE_TABLES, halves = p.mode == MODE_HALVES, wide = p.mode == MODE_WIDE;
+  const bool bytes = byte_windows(p.nb);  // U8 / U16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
+  const size_t merge_nb = merge || wide ? ctx->n_bases : 0;
+  hipStream_t st = ctx->stream;
+  const dim3 grid(p.tiles, p.nvec), block(256);
+  uint32_t* d_err = reinterpret_cast<uint32_t*>(s.d_wsums + WSUM_BYTES);
+  // the SMVP chunk length the device settles on for this launch (k_scatter_coarse -> fine sort, SMVP, stitch): a word of the slot
+  uint32_t* d_chunk_len = s.d_big_queue + BIGQ_CHUNK_LEN;
+  const int tl = ctx->timing_level;
+  auto mark = [&](int i) { return tl >= 2 ? hipEventRecord(s.ev[i], st) : hipSuccess; };
+  HIP_TRY(ctx, hipStreamWaitEvent(st, s.done, 0));
+  HIP_TRY(ctx, mark(0));
+  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
+    const size_t count = (size_t)p.nvec * p.n;
+    hipLaunchKernelGGL(ctx->ops->scalars_from_mont256, dim3(blocks_for(count, 256)), dim3(256), 0, st, d_scalars, ctx->d_scalar_conv, count, d_err);
+    AFTER_KERNEL(ctx, "k_scalars_from_mont256", st);
+    d_scalars = ctx->d_scalar_conv;
+  }
+  const unsigned gpos_bytes = (unsigned)(merge ? p.nvec : p.nvec * p.w_count_vec) * NCOARSE * 4;  // k_scatter_coarse's run cursors (dynamic LDS)
+  const int top_shift = wide ? wide_top_shift(ctx->curve, p.wide_bits) : 0;
+  // words per input of the two-level sort: 8 (32-byte scalars), 4 (the endomorphism's halves) or 1 / 2 (U32 / U64: NB = 4 / 8 bytes)
+  const int sw = p.nb ? p.nb / 4 : halves ? 4 : 8;
+  // first pass: recode + coarse histogram (+ digit planes: 1 = debug read-back, 2 = the second pass reads them).  Endomorphism launches:
+  // the same kernel splits every scalar k = k1 + k2 lambda itself and leaves the halves (interleaved: input 2 j = k1 of scalar j, 2 j + 1 =
+  // k2; a vector's 2n halves take the room of its n scalars, vector stride n * 8 words either way) for a scalar-reading second pass.
+  uint16_t* digits = p.digits ? ctx->d_digits : nullptr;
+  uint16_t* plane_out = p.planes ? ctx->d_digits : digits;
+  const int plane_mode = p.planes ? 2 : (digits ? 1 : 0);
+  if (wide) {
+    dispatch<16, 17, 18, 19, 20>(p.wide_bits, [&](auto c) {
+      constexpr int C = decltype(c)::value;
+      if (p.list_path)
+        hipLaunchKernelGGL(k_count_wide_list<C>, grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.nvec, p.n * 8, ctx->d_counts, d_err, top_shift,
+                           p.v_begin, p.v_count, ctx->d_val, ctx->d_list_len, p.stride, p.subtiles);
+      else
+        hipLaunchKernelGGL(k_count_wide<C>, grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.nvec, p.n * 8, ctx->d_counts, d_err, top_shift,
+                           p.v_begin, p.v_count);
+    });
+  } else if (bytes) {
+    dispatch<1, 2>(p.nb, [&](auto b) {
+      hipLaunchKernelGGL(k_byte_count<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.tile_len, p.tiles, ctx->d_counts);
+    });
+  } else if (halves) {
+    hipLaunchKernelGGL(ctx->ops->count_split[p.wbits == 16 ? 2 : p.wbits == 14 ? 1 : 0], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin,
+                       p.w_count_vec, p.nvec, p.n * 8, ctx->d_counts, plane_out, plane_mode, p.planes ? ctx->d_negbits : nullptr,
+                       p.planes ? nullptr : ctx->d_halves, d_err, merge_nb);
+    d_scalars = ctx->d_halves;
+  } else {
+    dispatch<16, 14, 12>(p.wbits, [&](auto c) {
+      dispatch<8, 2, 1>(sw, [&](auto w) {
+        constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
+        hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
+                           p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
+      });
+    });
+  }
+  AFTER_KERNEL(ctx, "k_count", st);
+  HIP_TRY(ctx, mark(1));
+  if (bytes) hipLaunchKernelGGL(k_byte_scan, dim3(BYTE_BINS / 4, p.w_count), dim3(256), 0, st, ctx->d_counts, p.tiles, ctx->d_bin_total);
+  else hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, p.w_count), dim3(256), 0, st, ctx->d_counts, p.tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
+  AFTER_KERNEL(ctx, "k_scan_tiles", st);
+  HIP_TRY(ctx, mark(2));
+  if (p.list_path) {  // shares of at most WIDE_SHARE_VWIN_MAX virtual windows: from the first pass's lists
+    hipLaunchKernelGGL(k_scatter_list, dim3(p.tiles, p.w_count), dim3(256), 0, st, (const uint32_t*)ctx->d_val, (const uint32_t*)ctx->d_list_len, p.stride,
+                       (uint32_t)(LIST_SUB * wide_tables_of(p.wide_bits)), p.subtiles, p.n_sc, p.tile_len, p.tiles, p.w_count, ctx->d_counts, ctx->d_bin_total,
+                       ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, p.chunks, p.chunk_len, d_chunk_len);
+  } else if (wide) {  // (... or, MSM_HIP_WIDE_SHARE_LISTS=0, the small shape of the two-pass kernel: four workgroups per CU instead of one)
+    dispatch<16, 17, 18, 19, 20>(p.wide_bits, [&](auto c) {
+      dispatch<true, false>(p.share_shape, [&](auto share) {
+        constexpr int C = decltype(c)::value;
+        constexpr bool SHARE = decltype(share)::value;
+        hipLaunchKernelGGL((k_scatter_wide<C, SHARE>), grid, dim3(WideScatterShape<C, SHARE>::THREADS), 0, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles,
+                           p.nvec, p.n * 8, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, p.chunks, p.chunk_len,
+                           d_chunk_len, top_shift, p.v_begin, p.v_count);
+      });
+    });
+  } else if (p.planes) {
+    hipLaunchKernelGGL(k_scatter_planes, dim3(p.tiles), dim3(256), 0, st, ctx->d_digits, halves ? ctx->d_negbits : (const uint64_t*)nullptr, p.n_sc, p.stride,
+                       p.tile_len, p.tiles, p.w_count, p.w_count_vec, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                       (uint32_t)ctx->n_bases, p.chunks, p.chunk_len, d_chunk_len);
+  } else if (bytes) {
+    dispatch<1, 2>(p.nb, [&](auto b) {
+      hipLaunchKernelGGL(k_byte_scatter<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.stride, p.tile_len, p.tiles, p.w_count,
+                         ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len);
+    });
+  } else {
+    dispatch<16, 14, 12>(p.wbits, [&](auto c) {
+      dispatch<8, 4, 2, 1>(sw, [&](auto w) {
+        constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
+        hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
+                           p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                           merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
+      });
+    });
+  }
+  AFTER_KERNEL(ctx, "k_scatter_coarse", st);
+  HIP_TRY(ctx, mark(3));
+  // large n: the sub-range histograms of huge coarse bins are made once, not by every sharer.  (round 5) Not launched at all while uniform scalars
+  // cannot fill a coarse bin to three quarters of FINE_BIG -- 2^20 points and below: its 8192 workgroups found nothing to do and took 19 us of every
+  // launch's main stream; skewed scalars that make such a bin after all take the sharers' own histograms (k_sort_fine's fallback path)
+  // ... ADAPTIVELY (later in round 5): few distinct / small / equal scalars (witness vectors) fill huge bins at any size, and the fallback costs their
+  // fine sort 2 - 2.5 x (profiles/r05_skew_hist.txt): k_sort_fine reports a huge bin in the slot's status word, and the 64 launches after such a
+  // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once)
+  // Narrow scalars always run it and leave the credit alone: their top window holds only the recode's carry (U8: all entries) -- one huge bin by
+  // construction, which says nothing about the context's later 32-byte launches
+  if (bytes) {  // byte windows: the scatter has grouped the entries by slot already; only the SMVP's chunk table is left
+    hipLaunchKernelGGL(k_byte_chunks, dim3(blocks_for(p.chunks, 256), p.w_count), dim3(256), 0, st, (const uint32_t*)s.d_col_ptr, p.half, p.chunks,
+                       (const uint32_t*)d_chunk_len, ctx->d_chunk_slot);
+    AFTER_KERNEL(ctx, "k_byte_chunks", st);
+  } else {
+    const uint32_t* part_hist = nullptr;
+    const bool hist_useful = p.nb || ctx->fine_hist_min_n != FINE_BIG + 1 || p.n_entries / p.ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
+    if (ctx->skew_credit > 0 && !p.nb) ctx->skew_credit--;
+    if (p.n_entries >= ctx->fine_hist_min_n && hist_useful) {
+      hipLaunchKernelGGL(k_fine_hist, dim3(p.ncoarse, p.w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, p.stride, ctx->d_coarse_ptr,
+                         ctx->d_part_hist);
+      AFTER_KERNEL(ctx, "k_fine_hist", st);
+      part_hist = ctx->d_part_hist;
+    }
+    hipLaunchKernelGGL(k_sort_fine, dim3(p.ncoarse, p.w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_val, ctx->d_tmp_fine, p.stride, ctx->d_coarse_ptr,
+                       s.d_col_ptr, ctx->d_val, p.chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err);
+    AFTER_KERNEL(ctx, "k_sort_fine", st);
+  }
+  if (ctx->debug) {  // deterministic transpose for the stage read-back: every slot's run in ascending order
+    hipLaunchKernelGGL(k_order_runs, dim3(blocks_for(p.n_entries, 256), p.w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_val, ctx->d_tmp_val, p.stride, p.half);
+    hipLaunchKernelGGL(k_copy_runs, dim3(blocks_for(p.n_entries, 256), p.w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_tmp_val, ctx->d_val, p.stride, p.half);
+    AFTER_KERNEL(ctx, "k_order_runs", st);
+  }
+  return MSM_HIP_OK;
+}
+
+// The bucket reduce's row / column pass: the curve's k_bpr_rowcol<LOG_R, LOG_ROWS> and its workgroups per window.  Serial run per thread before
+// the LDS tree: 16 buckets when many windows are reduced at once (fewest wave-additions), 4 for a few windows (shallowest); measured optimum for 16
+// and for 2 windows respectively
+struct RowCol {
+  void (*kernel)(const uint32_t*, uint32_t*, uint32_t*);
+  int blocks;
+};
+RowCol pick_rowcol(const msm_hip_ctx* ctx, const LaunchPlan& p, const Slot& s) {
+  static const int force_logr = [] { const char* e = getenv("MSM_HIP_BPR_LOGR"); return e ? atoi(e) : 0; }();  // tuning aid
+  const CurveOps* o = ctx->ops;
+  if (p.wbits == 16) {
+    // one small MSM alone in its launch (8 half-length windows, up to 2^18 points): 8 buckets per thread -- its latency is what counts
+    // (-4 % at 2^16, -2.6 % at 2^18; the same setting costs grouped launches 3 - 16 % and a pipelined 2^20 MSM 0.5 %)
+    // ... and so is a larger one that has the GPU to itself: no other result slot of the context is in flight when it is launched
+    // (latency 1.81 -> 1.77 ms at 2^20; in a pipeline only the very first launch is alone: throughput unchanged)
+    bool alone = p.nvec == 1 && p.w_count == 8;
+    for (const Slot& q : ctx->slot) alone = alone && (&q == &s || !q.pending);
+    const bool small_single = p.nvec == 1 && p.w_count == 8 && (p.n_entries <= ((size_t)1 << 19) || alone);
+    if (force_logr == 4 || (force_logr == 0 && p.w_count >= 8 && !small_single)) return {o->rowcol_4_8, bpr_rowcol_blocks<4, 8>()};
+    if (force_logr == 3 || (force_logr == 0 && small_single)) return {o->rowcol_3_8, bpr_rowcol_blocks<3, 8>()};
+    return {o->rowcol_2_8, bpr_rowcol_blocks<2, 8>()};
+  }
+  if (p.wbits == 14) {  // 64 rows x 128 columns
+    if (force_logr == 4 || (force_logr == 0 && p.w_count > 2 * nwin_of(14))) return {o->rowcol_4_6, bpr_rowcol_blocks<4, 6>()};
+    return {o->rowcol_2_6, bpr_rowcol_blocks<2, 6>()};
+  }
+  return {o->rowcol_2_4, bpr_rowcol_blocks<2, 4>()};  // 16 rows x 128 columns
+}
+
+// The launch's second stage: the SMVP (it reads the bases) on the main stream, then stitch + bucket reduce on the slot's reduce stream, few waves
+// of long dependent chains; the error word and, for the host, the window sums go to the slot's pinned buffer.  Returns without waiting.
+int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   hipStream_t st = ctx->stream, rs = ctx->reduce_stream[(&s - ctx->slot) % NREDUCE];
   // a synchronous call with nothing else in flight (msm_hip_run_*: the caller waits for this launch before it issues another): the stitch and
   // the bucket reduce follow the SMVP on the MAIN stream -- no cross-stream hand-off (an event wait costs ~10 us more than an in-stream kernel
@@ -596,219 +852,31 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
     for (const Slot& o : ctx->slot) others = others || (&o != &s && o.pending);
     if (!others) rs = st;
   }
-  // tiles of scalars for the two global sort passes: >= 2048 scalars each, at most MAX_TILES of them
-  // window shares (a few of a scalar's windows per vector): the first pass leaves digit planes, the second reads them (k_scatter_planes)
-  const bool planes = use_planes(ctx, mode, w_count_vec, wbits);
-  // shares of at most WIDE_SHARE_VWIN_MAX virtual windows of wide tables: the first pass leaves compact lists of the share's entries per sub-tile of
-  // LIST_SUB scalars (k_count_wide_list / k_scatter_list); tiles are then whole sub-tiles.  MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape (A/B aid)
-  static const bool share_lists = [] { const char* e = getenv("MSM_HIP_WIDE_SHARE_LISTS"); return !e || atoi(e) != 0; }();
-  const bool share_shape = pairs && v_count <= WIDE_SHARE_VWIN_MAX;
-  const bool list_path = share_shape && share_lists;
-  const uint32_t tile_unit = list_path ? (uint32_t)LIST_SUB : 256u;
-  uint32_t tile_len = 2048;
-  if ((n_sc + tile_len - 1) / tile_len > MAX_TILES) tile_len = (uint32_t)((((n_sc + MAX_TILES - 1) / MAX_TILES) + tile_unit - 1) / tile_unit * tile_unit);
-  const uint32_t tiles = (uint32_t)((n_sc + tile_len - 1) / tile_len);
-  const uint32_t subtiles = (uint32_t)((n_sc + LIST_SUB - 1) / LIST_SUB);
-  const WideShape ws = wide ? wide_shape(n, ctx->curve, ctx->wide_bits, w_count) : WideShape{};
-  const uint32_t chunk_len = wide ? ws.host_len : chunk_len_for(n_entries, w_count);  // (the longest the device may pick: smvp_chunk_len)
-  const uint32_t chunks = wide ? ws.chunks : chunks_for(n_entries, chunk_len);
-  const size_t stride = stride_for(n_entries);
-  ctx->last_stride = stride;
-  uint16_t* digits = ctx->debug && !merge && !wide && !bytes ? ctx->d_digits : nullptr;
+  const bool to_host = !p.sums_dev;
+  uint32_t* wsums_out = to_host ? reinterpret_cast<uint32_t*>(s.d_wsums) : p.sums_dev;
   uint32_t* d_err = reinterpret_cast<uint32_t*>(s.d_wsums + WSUM_BYTES);
-  if (!wsums_out) wsums_out = reinterpret_cast<uint32_t*>(s.d_wsums);
-  // the SMVP chunk length the device settles on for this launch (k_scatter_coarse -> fine sort, SMVP, stitch): a word of the slot
   uint32_t* d_chunk_len = s.d_big_queue + BIGQ_CHUNK_LEN;
-
-  // the slot's previous occupant (bucket reduce + copies on the reduce stream) must have drained; its error word was
-  // re-zeroed at the end of that chain.  Stage events cost a few microseconds of queue time each, so only the ones the
-  // current timing level asks for are recorded.
   const int tl = ctx->timing_level;
-  auto mark = [&](int i, bool smvp_edge) -> hipError_t {
-    if (tl >= 2 || (tl == 1 && smvp_edge)) return hipEventRecord(s.ev[i], st);
-    return hipSuccess;
-  };
-  if (phase != 2) {  // ---- recode + sort
-  HIP_TRY(ctx, hipStreamWaitEvent(st, s.done, 0));
-  HIP_TRY(ctx, mark(0, false));
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !nb) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
-    const size_t count = (size_t)nvec * n;
-    hipLaunchKernelGGL(ctx->ops->scalars_from_mont256, dim3(blocks_for(count, 256)), dim3(256), 0, st, d_scalars, ctx->d_scalar_conv, count, d_err);
-    AFTER_KERNEL(ctx, "k_scalars_from_mont256", st);
-    d_scalars = ctx->d_scalar_conv;
-  }
-  const unsigned gpos_bytes = (unsigned)(merge ? nvec : nvec * w_count_vec) * NCOARSE * 4;  // k_scatter_coarse's run cursors (dynamic LDS)
-#define LAUNCH_BY_WBITS_SW(KERNEL, LDS, SW, ...)                                         \
-  do {                                                                                   \
-    if (wbits == 16) hipLaunchKernelGGL((KERNEL<16, SW>), dim3(tiles, nvec), dim3(256), LDS, st, __VA_ARGS__); \
-    else if (wbits == 14) hipLaunchKernelGGL((KERNEL<14, SW>), dim3(tiles, nvec), dim3(256), LDS, st, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<12, SW>), dim3(tiles, nvec), dim3(256), LDS, st, __VA_ARGS__); \
-  } while (0)
-  // first pass: recode + coarse histogram (+ digit planes: 1 = debug read-back, 2 = the second pass reads them).  Endomorphism launches:
-  // the same kernel splits every scalar k = k1 + k2 lambda itself and leaves the halves (interleaved: input 2 j = k1 of scalar j, 2 j + 1 =
-  // k2; a vector's 2n halves take the room of its n scalars, vector stride n * 8 words either way) for a scalar-reading second pass.
-  uint16_t* plane_out = planes ? ctx->d_digits : digits;
-  const int plane_mode = planes ? 2 : (digits ? 1 : 0);
-  if (wide) {
-    const int top_shift = wide_top_shift(ctx->curve, ctx->wide_bits);
-#define LAUNCH_COUNT_WIDE(C) hipLaunchKernelGGL(k_count_wide<C>, dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, nvec, n * 8, ctx->d_counts, d_err, top_shift, v_begin, v_count)
-#define LAUNCH_COUNT_WIDE_LIST(C) hipLaunchKernelGGL(k_count_wide_list<C>, dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, nvec, n * 8, ctx->d_counts, d_err, top_shift, v_begin, v_count, ctx->d_val, ctx->d_list_len, stride, subtiles)
-    switch (ctx->wide_bits * 2 + (list_path ? 1 : 0)) {
-      case 32: LAUNCH_COUNT_WIDE(16); break;
-      case 33: LAUNCH_COUNT_WIDE_LIST(16); break;
-      case 34: LAUNCH_COUNT_WIDE(17); break;
-      case 35: LAUNCH_COUNT_WIDE_LIST(17); break;
-      case 36: LAUNCH_COUNT_WIDE(18); break;
-      case 37: LAUNCH_COUNT_WIDE_LIST(18); break;
-      case 38: LAUNCH_COUNT_WIDE(19); break;
-      case 39: LAUNCH_COUNT_WIDE_LIST(19); break;
-      case 40: LAUNCH_COUNT_WIDE(20); break;
-      default: LAUNCH_COUNT_WIDE_LIST(20); break;
-    }
-#undef LAUNCH_COUNT_WIDE
-#undef LAUNCH_COUNT_WIDE_LIST
-  } else if (bytes) {
-    if (nb == 1) hipLaunchKernelGGL(k_byte_count<1>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, tile_len, tiles, ctx->d_counts);
-    else hipLaunchKernelGGL(k_byte_count<2>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, tile_len, tiles, ctx->d_counts);
-  } else if (nb) {
-    // U32 / U64: vectors of n x nb bytes (vec_stride in bytes)
-#define LAUNCH_COUNT_NARROW(C, NB) hipLaunchKernelGGL((k_count<C, (NB + 3) / 4, false, NB>), dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, w_begin, \
-                       w_count_vec, nvec, n * NB, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, (size_t)0)
-#define LAUNCH_NARROW_BY_WBITS(L, NB) \
-  do {                                \
-    if (wbits == 16) L(16, NB);       \
-    else if (wbits == 14) L(14, NB);  \
-    else L(12, NB);                   \
-  } while (0)
-    if (nb == 4) LAUNCH_NARROW_BY_WBITS(LAUNCH_COUNT_NARROW, 4);
-    else LAUNCH_NARROW_BY_WBITS(LAUNCH_COUNT_NARROW, 8);
-#undef LAUNCH_COUNT_NARROW
-  } else if (halves) {
-    hipLaunchKernelGGL(ctx->ops->count_split[wbits == 16 ? 2 : wbits == 14 ? 1 : 0], dim3(tiles, nvec), dim3(256), 0, st, d_scalars, n_sc, tile_len, tiles, w_begin,
-                       w_count_vec, nvec, n * 8, ctx->d_counts, plane_out, plane_mode, planes ? ctx->d_negbits : nullptr,
-                       planes ? nullptr : ctx->d_halves, d_err, merge_nb);
-    d_scalars = ctx->d_halves;
-  } else {
-    LAUNCH_BY_WBITS_SW(k_count, 0, 8, d_scalars, n_sc, tile_len, tiles, w_begin, w_count_vec, nvec, n * 8, ctx->d_counts, plane_out, plane_mode,
-                       (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
-  }
-  AFTER_KERNEL(ctx, "k_count", st);
-  HIP_TRY(ctx, mark(1, false));
-  if (bytes) hipLaunchKernelGGL(k_byte_scan, dim3(BYTE_BINS / 4, w_count), dim3(256), 0, st, ctx->d_counts, tiles, ctx->d_bin_total);
-  else hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, w_count), dim3(256), 0, st, ctx->d_counts, tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
-  AFTER_KERNEL(ctx, "k_scan_tiles", st);
-  HIP_TRY(ctx, mark(2, false));
-  if (wide) {
-    const int top_shift = wide_top_shift(ctx->curve, ctx->wide_bits);
-    // shares of at most WIDE_SHARE_VWIN_MAX virtual windows: from the first pass's lists, or (MSM_HIP_WIDE_SHARE_LISTS=0) the small shape of the
-    // two-pass kernel (four workgroups per CU instead of one)
-    if (list_path) {
-      hipLaunchKernelGGL(k_scatter_list, dim3(tiles, w_count), dim3(256), 0, st, (const uint32_t*)ctx->d_val, (const uint32_t*)ctx->d_list_len, stride,
-                         (uint32_t)(LIST_SUB * wide_tables_of(ctx->wide_bits)), subtiles, n_sc, tile_len, tiles, w_count, ctx->d_counts, ctx->d_bin_total,
-                         ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, chunks, chunk_len, d_chunk_len);
-    } else {
-#define LAUNCH_SCATTER_WIDE_SHAPE(C, SHARE)                                                                                                                         \
-  hipLaunchKernelGGL((k_scatter_wide<C, SHARE>), dim3(tiles, nvec), dim3(WideScatterShape<C, SHARE>::THREADS), 0, st, d_scalars, n_sc, stride, tile_len, tiles, nvec, n * 8, ctx->d_counts, ctx->d_bin_total, \
-                     ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, chunks, chunk_len, d_chunk_len, top_shift, v_begin, v_count)
-#define LAUNCH_SCATTER_WIDE(C)                       \
-  do {                                               \
-    if (share_shape) LAUNCH_SCATTER_WIDE_SHAPE(C, true); \
-    else LAUNCH_SCATTER_WIDE_SHAPE(C, false);        \
-  } while (0)
-    switch (ctx->wide_bits) {
-      case 16: LAUNCH_SCATTER_WIDE(16); break;
-      case 17: LAUNCH_SCATTER_WIDE(17); break;
-      case 18: LAUNCH_SCATTER_WIDE(18); break;
-      case 19: LAUNCH_SCATTER_WIDE(19); break;
-      default: LAUNCH_SCATTER_WIDE(20); break;
-    }
-#undef LAUNCH_SCATTER_WIDE_SHAPE
-#undef LAUNCH_SCATTER_WIDE
-    }
-  } else if (planes) {
-    hipLaunchKernelGGL(k_scatter_planes, dim3(tiles), dim3(256), 0, st, ctx->d_digits, halves ? ctx->d_negbits : (const uint64_t*)nullptr, n_sc, stride, tile_len,
-                       tiles, w_count, w_count_vec, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
-                       (uint32_t)ctx->n_bases, chunks, chunk_len, d_chunk_len);
-  } else if (bytes) {
-#define LAUNCH_SCATTER_BYTES(NB) hipLaunchKernelGGL(k_byte_scatter<NB>, dim3(tiles, nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, n, stride, tile_len, tiles, \
-                       w_count, ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, half, ctx->d_val, chunks, chunk_len, d_chunk_len)
-    if (nb == 1) LAUNCH_SCATTER_BYTES(1);
-    else LAUNCH_SCATTER_BYTES(2);
-#undef LAUNCH_SCATTER_BYTES
-  } else if (nb) {
-#define LAUNCH_SCATTER_NARROW(C, NB) hipLaunchKernelGGL((k_scatter_coarse<C, (NB + 3) / 4, NB>), dim3(tiles, nvec), dim3(256), gpos_bytes, st, d_scalars, n_sc, stride, tile_len, \
-                       tiles, w_begin, w_count_vec, nvec, n * NB, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, (size_t)0, \
-                       (uint32_t)n, 0u, chunks, chunk_len, d_chunk_len)
-    if (nb == 4) LAUNCH_NARROW_BY_WBITS(LAUNCH_SCATTER_NARROW, 4);
-    else LAUNCH_NARROW_BY_WBITS(LAUNCH_SCATTER_NARROW, 8);
-#undef LAUNCH_SCATTER_NARROW
-#undef LAUNCH_NARROW_BY_WBITS
-  } else if (halves) {
-    LAUNCH_BY_WBITS_SW(k_scatter_coarse, gpos_bytes, 4, d_scalars, n_sc, stride, tile_len, tiles, w_begin, w_count_vec, nvec, n * 8, ctx->d_counts, ctx->d_bin_total,
-                       ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, (uint32_t)n, (uint32_t)ctx->n_bases, chunks, chunk_len, d_chunk_len);
-  } else {
-    LAUNCH_BY_WBITS_SW(k_scatter_coarse, gpos_bytes, 8, d_scalars, n_sc, stride, tile_len, tiles, w_begin, w_count_vec, nvec, n * 8, ctx->d_counts, ctx->d_bin_total,
-                       ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine, merge_nb, (uint32_t)n, 0u, chunks, chunk_len, d_chunk_len);
-  }
-#undef LAUNCH_BY_WBITS_SW
-  AFTER_KERNEL(ctx, "k_scatter_coarse", st);
-  HIP_TRY(ctx, mark(3, false));
-  const uint32_t* part_hist = nullptr;
-  // large n: the sub-range histograms of huge coarse bins are made once, not by every sharer.  (round 5) Not launched at all while uniform scalars
-  // cannot fill a coarse bin to three quarters of FINE_BIG -- 2^20 points and below: its 8192 workgroups found nothing to do and took 19 us of every
-  // launch's main stream; skewed scalars that make such a bin after all take the sharers' own histograms (k_sort_fine's fallback path)
-  // ... ADAPTIVELY (later in round 5): few distinct / small / equal scalars (witness vectors) fill huge bins at any size, and the fallback costs their
-  // fine sort 2 - 2.5 x (profiles/r05_skew_hist.txt): k_sort_fine reports a huge bin in the slot's status word, and the 64 launches after such a
-  // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once)
-  // Narrow scalars always run it and leave the credit alone: their top window holds only the recode's carry (U8: all entries) -- one huge bin by
-  // construction, which says nothing about the context's later 32-byte launches
-  if (bytes) {  // byte windows: the scatter has grouped the entries by slot already; only the SMVP's chunk table is left
-    hipLaunchKernelGGL(k_byte_chunks, dim3(blocks_for(chunks, 256), w_count), dim3(256), 0, st, (const uint32_t*)s.d_col_ptr, half, chunks,
-                       (const uint32_t*)d_chunk_len, ctx->d_chunk_slot);
-    AFTER_KERNEL(ctx, "k_byte_chunks", st);
-  } else {
-    const bool hist_useful = nb || ctx->fine_hist_min_n != FINE_BIG + 1 || n_entries / ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
-    if (ctx->skew_credit > 0 && !nb) ctx->skew_credit--;
-    if (n_entries >= ctx->fine_hist_min_n && hist_useful) {
-      hipLaunchKernelGGL(k_fine_hist, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
-                         ctx->d_part_hist);
-      AFTER_KERNEL(ctx, "k_fine_hist", st);
-      part_hist = ctx->d_part_hist;
-    }
-    hipLaunchKernelGGL(k_sort_fine, dim3(ncoarse, w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_val, ctx->d_tmp_fine, stride, ctx->d_coarse_ptr,
-                       s.d_col_ptr, ctx->d_val, chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err);
-    AFTER_KERNEL(ctx, "k_sort_fine", st);
-  }
-  if (ctx->debug) {  // deterministic transpose for the stage read-back: every slot's run in ascending order
-    hipLaunchKernelGGL(k_order_runs, dim3(blocks_for(n_entries, 256), w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_val, ctx->d_tmp_val, stride, half);
-    hipLaunchKernelGGL(k_copy_runs, dim3(blocks_for(n_entries, 256), w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_tmp_val, ctx->d_val, stride, half);
-    AFTER_KERNEL(ctx, "k_order_runs", st);
-  }
-  }  // ---- (recode + sort)
-  if (phase == 1) {
-    HIP_TRY(ctx, hipGetLastError());
-    return MSM_HIP_OK;
-  }
   // the SMVP's own begin / end timestamps: attached to its dispatch (hipExtLaunchKernelGGL) instead of two event packets around it -- a
   // packet between two kernels costs a few microseconds of queue time, and these two sat between every launch's sort and its SMVP and
   // between the SMVP and the next launch (bench.py times every launch's SMVP for the roofline figure).  Level 2 keeps the packets: its
   // stage boundaries are read as differences of consecutive events.
   static const unsigned smvp_lds_pad = [] { const char* e = getenv("MSM_HIP_SMVP_LDS_PAD"); const long v = e ? atol(e) : 0; return v > 0 && v <= 65536 ? (unsigned)v : 0u; }();
   HIP_TRY(ctx, tl >= 2 ? hipEventRecord(s.ev[4], st) : hipSuccess);
-  hipExtLaunchKernelGGL(ctx->ops->smvp_chunks, dim3((chunks + 255) / 256, w_count), dim3(256), smvp_lds_pad, st, tl == 1 ? s.ev[4] : nullptr,
-                        tl == 1 ? s.ev[5] : nullptr, 0, (const uint32_t*)(ctx->d_bases + s.base_off * 2 * (size_t)ctx->ops->coord_words), (const uint32_t*)s.d_col_ptr, (const uint32_t*)ctx->d_val, stride, chunks,
-                        (const uint32_t*)d_chunk_len, (const uint32_t*)ctx->d_chunk_slot, s.d_buckets, s.d_heads, s.d_tails, half);
+  hipExtLaunchKernelGGL(ctx->ops->smvp_chunks, dim3((p.chunks + 255) / 256, p.w_count), dim3(256), smvp_lds_pad, st, tl == 1 ? s.ev[4] : nullptr,
+                        tl == 1 ? s.ev[5] : nullptr, 0, (const uint32_t*)(ctx->d_bases + p.base_off * 2 * (size_t)ctx->ops->coord_words), (const uint32_t*)s.d_col_ptr,
+                        (const uint32_t*)ctx->d_val, p.stride, p.chunks, (const uint32_t*)d_chunk_len, (const uint32_t*)ctx->d_chunk_slot, s.d_buckets, s.d_heads,
+                        s.d_tails, p.half);
   AFTER_KERNEL(ctx, "k_smvp_chunks", st);
   HIP_TRY(ctx, tl >= 2 ? hipEventRecord(s.ev[5], st) : hipSuccess);
   if (rs != st) HIP_TRY(ctx, hipEventRecord(s.smvp_done, st));
 
-  // stitch + bucket reduce on the slot's reduce stream: few waves, long dependent chains
   if (rs != st) HIP_TRY(ctx, hipStreamWaitEvent(rs, s.smvp_done, 0));
-  hipLaunchKernelGGL(ctx->ops->smvp_stitch, dim3(half / 256, w_count), dim3(256), 0, rs, s.d_col_ptr, chunks, d_chunk_len, s.d_heads, s.d_tails,
+  hipLaunchKernelGGL(ctx->ops->smvp_stitch, dim3(p.half / 256, p.w_count), dim3(256), 0, rs, s.d_col_ptr, p.chunks, d_chunk_len, s.d_heads, s.d_tails,
                      s.d_buckets, s.d_big_queue);
   AFTER_KERNEL(ctx, "k_smvp_stitch", rs);
-  hipLaunchKernelGGL(ctx->ops->smvp_stitch_big, dim3(STITCH_BLOCKS), dim3(256), 0, rs, s.d_col_ptr, chunks, s.d_heads, s.d_tails, s.d_buckets,
-                     s.d_big_queue, half);
+  hipLaunchKernelGGL(ctx->ops->smvp_stitch_big, dim3(STITCH_BLOCKS), dim3(256), 0, rs, s.d_col_ptr, p.chunks, s.d_heads, s.d_tails, s.d_buckets,
+                     s.d_big_queue, p.half);
   AFTER_KERNEL(ctx, "k_smvp_stitch_big", rs);
   if (tl >= 2) {
     HIP_TRY(ctx, hipEventRecord(s.ev[6], rs));
@@ -817,85 +885,50 @@ int enqueue(msm_hip_ctx* ctx, const uint32_t* d_scalars, size_t n, int w_begin, 
   uint32_t* d_rows = s.d_partials;
   uint32_t* d_cols = d_rows + (size_t)MAXLW * 256 * ctx->ops->xyzz_words;
   uint32_t* d_parts = d_cols + (size_t)MAXLW * 256 * ctx->ops->xyzz_words;
-  static const int force_logr = [] { const char* e = getenv("MSM_HIP_BPR_LOGR"); return e ? atoi(e) : 0; }();  // tuning aid
-  // serial run per thread before the LDS tree: 16 buckets when many windows are reduced at once (fewest wave-additions),
-  // 4 for a few windows (shallowest); measured optimum for 16 and for 2 windows respectively
-#define ROWCOL(LOG_R, LOG_ROWS) \
-  hipLaunchKernelGGL(ctx->ops->rowcol_##LOG_R##_##LOG_ROWS, dim3(bpr_rowcol_blocks<LOG_R, LOG_ROWS>(), w_count), dim3(256), 0, rs, s.d_buckets, d_rows, d_cols)
-  if (wbits == 16) {
-    // one small MSM alone in its launch (8 half-length windows, up to 2^18 points): 8 buckets per thread -- its latency is what counts
-    // (-4 % at 2^16, -2.6 % at 2^18; the same setting costs grouped launches 3 - 16 % and a pipelined 2^20 MSM 0.5 %)
-    // ... and so is a larger one that has the GPU to itself: no other result slot of the context is in flight when it is launched
-    // (latency 1.81 -> 1.77 ms at 2^20; in a pipeline only the very first launch is alone: throughput unchanged)
-    bool alone = nvec == 1 && w_count == 8;
-    for (const Slot& o : ctx->slot) alone = alone && (&o == &s || !o.pending);
-    const bool small_single = nvec == 1 && w_count == 8 && (n_entries <= ((size_t)1 << 19) || alone);
-    if (force_logr == 4 || (force_logr == 0 && w_count >= 8 && !small_single)) ROWCOL(4, 8);
-    else if (force_logr == 3 || (force_logr == 0 && small_single)) ROWCOL(3, 8);
-    else ROWCOL(2, 8);
-  } else if (wbits == 14) {  // 64 rows x 128 columns
-    if (force_logr == 4 || (force_logr == 0 && w_count > 2 * nwin_of(14))) ROWCOL(4, 6);
-    else ROWCOL(2, 6);
-  } else {  // 16 rows x 128 columns
-    ROWCOL(2, 4);
-  }
-#undef ROWCOL
+  const RowCol rowcol = pick_rowcol(ctx, p, s);
+  hipLaunchKernelGGL(rowcol.kernel, dim3(rowcol.blocks, p.w_count), dim3(256), 0, rs, s.d_buckets, d_rows, d_cols);
   AFTER_KERNEL(ctx, "k_bpr_rowcol", rs);
   // A launch that carries ONE MSM whose sums the host combines anyway (finish): the narrow end of the reduction -- ~25 dependent group
   // operations at ~7 us each in k_bpr_w256 / k_bpr_final -- is replaced by 16 independent masked tree sums per window (k_bpr_planes, 8 deep)
   // and 29 operations per window on the host (0.3 us each).  Sums that stay on the device (window shards for the gather), grouped launches
   // (their host thread is on the critical path: several MSMs' worth of host work per launch) and debug read-backs get finished sums.
-  // (a wide fixed-base launch always leaves the plane sums -- its finish needs every virtual window's plain total, which is one of them --: launch_impl
+  // (a wide fixed-base launch always leaves the plane sums -- its finish needs every virtual window's plain total, which is one of them --: plan_launch
   //  admits it only as whole MSMs whose sums go to the host, at most 24 virtual windows together)
-  const bool parts_mode = to_host && !pairs && (nvec == 1 || wide) && (!ctx->debug || wide) && wsums_out == reinterpret_cast<uint32_t*>(s.d_wsums) && w_count <= 24;
+  const bool wide = p.mode == MODE_WIDE;
+  const bool parts_mode = to_host && !p.pairs && (p.nvec == 1 || wide) && (!ctx->debug || wide) && p.w_count <= 24;
   // the kernel that ends the chain writes the launch's error word into the slot's pinned buffer itself and clears it (no copy, no fill); a
   // single MSM's bit-plane sums go to the pinned buffer directly as well (12 KB of stores over the host link instead of a copy behind the kernel)
   uint32_t* h_err = reinterpret_cast<uint32_t*>(s.h_wsums + WSUM_BYTES);
+  const int bpr_cols = (int)(p.half / BPR_COLS);
   if (parts_mode) {
-    hipLaunchKernelGGL(ctx->ops->bpr_planes, dim3(PLANES_PER_WINDOW, w_count), dim3(256), 0, rs, d_rows, d_cols, reinterpret_cast<uint32_t*>(s.h_wsums),
-                       (int)(half / BPR_COLS), s.d_big_queue, d_err, h_err);
+    hipLaunchKernelGGL(ctx->ops->bpr_planes, dim3(PLANES_PER_WINDOW, p.w_count), dim3(256), 0, rs, d_rows, d_cols, reinterpret_cast<uint32_t*>(s.h_wsums),
+                       bpr_cols, s.d_big_queue, d_err, h_err);
     AFTER_KERNEL(ctx, "k_bpr_planes", rs);
   } else if (ctx->ops->use_w256) {
-    hipLaunchKernelGGL(ctx->ops->bpr_w256, dim3(2, w_count), dim3(256), 0, rs, d_rows, d_cols, d_parts, (int)(half / BPR_COLS));
+    hipLaunchKernelGGL(ctx->ops->bpr_w256, dim3(2, p.w_count), dim3(256), 0, rs, d_rows, d_cols, d_parts, bpr_cols);
     AFTER_KERNEL(ctx, "k_bpr_w256", rs);
-    hipLaunchKernelGGL(ctx->ops->bpr_final, dim3(1), dim3(64), 0, rs, d_parts, w_count, wsums_out, s.d_big_queue, d_err, h_err, pairs ? 1 : 0);
+    hipLaunchKernelGGL(ctx->ops->bpr_final, dim3(1), dim3(64), 0, rs, d_parts, p.w_count, wsums_out, s.d_big_queue, d_err, h_err, p.pairs ? 1 : 0);
     AFTER_KERNEL(ctx, "k_bpr_final", rs);
   } else {  // a field too wide for k_bpr_w256's LDS footprint (BLS12-381): the same bit-plane sums, finished on the device
-    hipLaunchKernelGGL(ctx->ops->bpr_planes_xyzz, dim3(PLANES_PER_WINDOW, w_count), dim3(256), 0, rs, d_rows, d_cols, d_parts, (int)(half / BPR_COLS),
-                       s.d_big_queue, d_err, h_err);
+    hipLaunchKernelGGL(ctx->ops->bpr_planes_xyzz, dim3(PLANES_PER_WINDOW, p.w_count), dim3(256), 0, rs, d_rows, d_cols, d_parts, bpr_cols, s.d_big_queue,
+                       d_err, h_err);
     AFTER_KERNEL(ctx, "k_bpr_planes<xyzz>", rs);
-    hipLaunchKernelGGL(ctx->ops->bpr_final_planes, dim3(1), dim3(64), 0, rs, d_parts, w_count, wsums_out, s.d_big_queue, d_err, h_err, pairs ? 1 : 0);
+    hipLaunchKernelGGL(ctx->ops->bpr_final_planes, dim3(1), dim3(64), 0, rs, d_parts, p.w_count, wsums_out, s.d_big_queue, d_err, h_err, p.pairs ? 1 : 0);
     AFTER_KERNEL(ctx, "k_bpr_final_planes", rs);
   }
   if (tl >= 2) HIP_TRY(ctx, hipEventRecord(s.red1, rs));
-  if (to_host && !parts_mode) HIP_TRY(ctx, hipMemcpyAsync(s.h_wsums, wsums_out, (size_t)w_count * (pairs ? 2 : 1) * ctx->jb, hipMemcpyDeviceToHost, rs));
+  if (to_host && !parts_mode) HIP_TRY(ctx, hipMemcpyAsync(s.h_wsums, wsums_out, (size_t)p.w_count * (p.pairs ? 2 : 1) * ctx->jb, hipMemcpyDeviceToHost, rs));
   HIP_TRY(ctx, hipEventRecord(s.done, rs));
   HIP_TRY(ctx, hipGetLastError());
 
-  s.w_begin = w_begin;
-  s.w_count = w_count_vec;
-  s.nvec = nvec;
-  s.wbits = wbits;
-  s.merged = merge;
-  s.halves = halves;
-  s.wide_bits = wide ? ctx->wide_bits : 0;
+  s.plan = p;
   s.parts = parts_mode;
-  s.pairs = pairs;
-  s.narrow = nb;
-  if (pairs) {
-    s.w_begin = v_begin;
-    s.w_count = v_count;
-  }
-  s.n = n;
   s.timed = tl >= 1;
   s.timing_level = tl;
   s.pending = true;
   s.to_host = to_host;
-  ctx->last_n = n_sc;
-  ctx->last_w_count = w_count;
-  ctx->last_wbits = wbits;
+  ctx->last = p;
   ctx->last_slot = (int)(&s - ctx->slot);
-  ctx->last_has_digits = digits != nullptr;
   return MSM_HIP_OK;
 }
 
@@ -916,7 +949,7 @@ int wait_slot(msm_hip_ctx* ctx, Slot& s) {
   }
   uint32_t bits;
   memcpy(&bits, s.h_wsums + WSUM_BYTES, 4);
-  if ((bits & INFOBIT_HUGE_BIN) && !s.narrow) ctx->skew_credit = 64;  // (see the launch of k_fine_hist; a narrow launch's huge bins are its own)
+  if ((bits & INFOBIT_HUGE_BIN) && !s.plan.nb) ctx->skew_credit = 64;  // (see the launch of k_fine_hist; a narrow launch's huge bins are its own)
   return err_from_bits(bits);
 }
 
@@ -924,15 +957,6 @@ int wait_slot(msm_hip_ctx* ctx, Slot& s) {
 void drain_slots(msm_hip_ctx* ctx) {
   for (Slot& s : ctx->slot)
     if (s.pending) (void)wait_slot(ctx, s);
-}
-
-constexpr size_t MAX_POINTS = (size_t)1 << 28;  // point indices carry the digit sign in bit 31; 2^28 keeps every per-window offset in u32
-
-int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n) {
-  if (!ctx || (!scalars && n) || n > MAX_POINTS) return MSM_HIP_ERR_INVALID_ARG;
-  if (ctx->n_bases == 0 && n) return MSM_HIP_ERR_NO_BASES;
-  if (n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
-  return MSM_HIP_OK;
 }
 
 // room for n bases; no run may still be reading the old ones (the SMVP on the main stream)
@@ -970,13 +994,7 @@ int reserve_bases(msm_hip_ctx* ctx, size_t n, uint32_t flags) {
   ctx->wide_bits = 0;
   ctx->endo = false;
   const size_t records = wide ? n * (size_t)wide_tables_of(pick_wide_bits(ctx, n)) : tables ? n * NWIN : endo ? 2 * n : n;
-  if (records > ctx->cap_bases) {
-    ctx->cap_bases = 0;
-    int rc = dev_alloc(ctx, ctx->d_bases, records * 2 * (size_t)ctx->ops->coord_words);
-    if (rc) return rc;
-    ctx->cap_bases = records;
-  }
-  return MSM_HIP_OK;
+  return grow(ctx, ctx->cap_bases, records, false, [&](size_t c) { return dev_alloc(ctx, ctx->d_bases, c * 2 * (size_t)ctx->ops->coord_words); });
 }
 
 // wire bytes at d_xy (may be ctx->d_bases itself: the conversion is element-wise) -> resident Montgomery bases
@@ -1197,91 +1215,31 @@ int msm_hip_set_bases(msm_hip_ctx* ctx, const uint8_t* xy_host, size_t n, uint32
 }  // extern "C"
 
 namespace {
-// windows [w_begin, w_end) -- in units of `wbits`-bit windows -- of `nvec` scalar vectors into `slot`
-// (MODE_WIDE, v_count != 0: a SHARE of the wide tables' virtual windows -- [v_begin, v_begin + v_count) of every vector; its sums are (window sum,
-//  plain total) pairs: 2 records per local window, to `window_sums_dev` or, when null, to the slot's pinned buffer)
+// one launch into `slot` (the request as plan_launch takes it): plan, buffers, sort, reduce
 int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
-                void* window_sums_dev, LaunchMode mode = MODE_PLAIN, int v_begin = 0, int v_count = 0, int phase = 0) {
-  // (MODE_WIDE: called with wbits = 19 and all 14 windows; everything behind the recode sees 8 local windows of 16 bits)
-  const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
-  const bool pairs = wide && v_count != 0;
-  const int nb = ctx && mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;
-  int rc = check_run_args(ctx, scalars_dev, n);
-  const size_t base_off = ctx ? ctx->launch_base_off : 0;
-  if (ctx && phase != 1) ctx->launch_base_off = 0;  // (a two-phase launch passes here twice)
+                void* window_sums_dev, LaunchMode mode = MODE_PLAIN, int v_begin = 0, int v_count = 0) {
+  LaunchPlan p;
+  int rc = plan_launch(ctx, p, mode, scalars_dev, n, nvec, w_begin, w_end, wbits, slot, window_sums_dev, v_begin, v_count);
   if (rc) return rc;
-  if (base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
-  if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > (nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves)) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
-  // narrow scalars: whole MSMs only, over the plain records, from a pointer aligned to the scalar's size
-  if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != narrow_windows(wbits, nb) || window_sums_dev || base_off || nvec * w_end > narrow_max_windows(nb) ||
-                              (byte_windows(nb) && wbits != BYTE_WBITS) ||
-                              reinterpret_cast<uintptr_t>(scalars_dev) % (uintptr_t)nb)) return MSM_HIP_ERR_INVALID_ARG;
-  if (wide && (nvec < 1 || w_begin != 0 || wbits != ctx->wide_bits || w_end != wide_tables_of(wbits))) return MSM_HIP_ERR_INVALID_ARG;
-  if (wide && !pairs && (nvec * wide_vwin_of(ctx->wide_bits) > 24 || window_sums_dev)) return MSM_HIP_ERR_INVALID_ARG;
-  if (pairs && (v_begin < 0 || v_count < 0 || v_begin + v_count > wide_vwin_of(ctx->wide_bits))) return MSM_HIP_ERR_INVALID_ARG;
-  if (!wide && v_count) return MSM_HIP_ERR_INVALID_ARG;
-  const int WIDE_VWIN = wide ? (pairs ? v_count : wide_vwin_of(ctx->wide_bits)) : 0;
-  if (wide) wbits = WBITS;
-  const int w_count = w_end - w_begin;
-  const int w_local = merge ? nvec : wide ? nvec * WIDE_VWIN : nvec * w_count;  // bucket sets of the launch
-  if (nvec < 1 || w_local > MAXLW) return MSM_HIP_ERR_INVALID_ARG;
   ON_DEVICE(ctx);
   Slot& s = ctx->slot[slot];
   if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;  // its result was never collected (msm_hip_finish / msm_hip_slot_sync)
   if ((rc = setup_slot(ctx, s))) return rc;
-  s.n = n;
-  s.base_off = base_off;
-  s.w_begin = w_begin;
-  s.w_count = w_count;
-  s.nvec = nvec;
-  s.wbits = wbits;
-  s.merged = merge;
-  s.halves = halves;
-  s.wide_bits = wide ? ctx->wide_bits : 0;
+  s.plan = p;
   s.parts = false;
-  s.pairs = pairs;
-  s.narrow = nb;
-  if (pairs) {
-    s.w_begin = v_begin;
-    s.w_count = v_count;
-  }
   s.to_host = window_sums_dev == nullptr;
   if (n == 0) {  // identity window sums, nothing to compute
     s.pending = true;
     s.timed = false;
     memset(s.h_wsums, 0, WSUM_BYTES + 4);
     if (window_sums_dev) {
-      HIP_TRY(ctx, hipMemsetAsync(window_sums_dev, 0, (size_t)w_local * (pairs ? 2 : 1) * ctx->jb, ctx->reduce_stream[slot % NREDUCE]));
+      HIP_TRY(ctx, hipMemsetAsync(window_sums_dev, 0, (size_t)p.w_count * (p.pairs ? 2 : 1) * ctx->jb, ctx->reduce_stream[slot % NREDUCE]));
       HIP_TRY(ctx, hipEventRecord(s.done, ctx->reduce_stream[slot % NREDUCE]));
     }
     return MSM_HIP_OK;
   }
-  if (wide) {
-    const WideShape ws = wide_shape(n, ctx->curve, ctx->wide_bits, w_local);
-    if ((rc = ensure_work(ctx, ws.worst, w_local, wbits, wide_vwin_of(ctx->wide_bits), s, false, (size_t)w_local * ws.chunks))) return rc;
-    const size_t need_len = pairs ? (size_t)w_local * ((n + LIST_SUB - 1) / LIST_SUB) : 0;  // list lengths of a share's first pass
-    if (need_len > ctx->cap_list_len) {
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      ctx->cap_list_len = 0;
-      if ((rc = dev_alloc(ctx, ctx->d_list_len, need_len))) return rc;
-      ctx->cap_list_len = need_len;
-    }
-  } else if ((rc = ensure_work(ctx, merge ? n * (size_t)w_count : halves ? 2 * n : n, w_local, wbits,
-                               merge ? 1 : halves ? nwin_of(wbits, true) : nb ? w_count : NWIN, s, use_planes(ctx, mode, w_count, wbits)))) return rc;
-  if (halves && !use_planes(ctx, mode, w_count, wbits) && (size_t)nvec * n > ctx->cap_halves) {  // (the halves as an array: only when the second pass reads them)
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cap_halves = 0;
-    if ((rc = dev_alloc(ctx, ctx->d_halves, (size_t)nvec * n * 8))) return rc;
-    ctx->cap_halves = (size_t)nvec * n;
-  }
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !nb && (size_t)nvec * n > ctx->cap_scalar_conv) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cap_scalar_conv = 0;
-    if ((rc = dev_alloc(ctx, ctx->d_scalar_conv, (size_t)nvec * n * 8))) return rc;
-    ctx->cap_scalar_conv = (size_t)nvec * n;
-  }
-  return enqueue(ctx, static_cast<const uint32_t*>(scalars_dev), n, w_begin, w_count, nvec, wbits, mode, s,
-                 static_cast<uint32_t*>(window_sums_dev), window_sums_dev == nullptr, v_begin, v_count, phase);
+  if ((rc = ensure_work(ctx, p, s)) || (rc = enqueue_sort(ctx, p, s, static_cast<const uint32_t*>(scalars_dev)))) return rc;
+  return enqueue_reduce(ctx, p, s);
 }
 }  // namespace
 
@@ -1355,10 +1313,9 @@ int msm_hip_slot_sync(msm_hip_ctx* ctx, int slot) {
 int msm_hip_finish_batch(msm_hip_ctx* ctx, int slot, uint8_t* out_xyz) {
   if (!ctx || !out_xyz || slot < 0 || slot >= NSLOT) return MSM_HIP_ERR_INVALID_ARG;
   Slot& s = ctx->slot[slot];
-  // fixed-base launches leave ONE sum per vector (every table already carries its power of two): nothing to combine but the copy
-  const int nwin = s.merged ? 1 : s.wide_bits ? wide_vwin_of(s.wide_bits) : s.narrow ? narrow_windows(s.wbits, s.narrow) : nwin_of(s.wbits, s.halves);
-  const int combine_bits = byte_windows(s.narrow) ? 8 : s.wbits;  // (byte windows: window j weighs 2^(8 j))
-  if (!s.pending || !s.to_host || s.pairs || s.w_count != (s.wide_bits ? wide_tables_of(s.wide_bits) : s.narrow ? nwin : nwin_of(s.wbits, s.halves))) return MSM_HIP_ERR_INVALID_ARG;
+  const LaunchPlan& p = s.plan;
+  const int nwin = p.nwin;
+  if (!s.pending || !s.to_host || !p.whole) return MSM_HIP_ERR_INVALID_ARG;
   ON_DEVICE(ctx);
   int rc = wait_slot(ctx, s);
   if (rc) return rc;
@@ -1367,18 +1324,18 @@ int msm_hip_finish_batch(msm_hip_ctx* ctx, int slot, uint8_t* out_xyz) {
   if (s.parts) {  // one MSM (wide tables: up to 12), its windows as bit-plane sums: the windows' positional sums side by side, then the chain over them
     uint8_t sums[24 * MAX_JB];
     const size_t jb = ctx->jb;
-    const int total = s.wide_bits ? s.nvec * nwin : nwin;
+    const int total = p.wide_bits ? p.nvec * nwin : nwin;
     combine_pool().run(total, [&](int w) {
       if (!ctx->ops->window_from_planes(s.h_wsums + (size_t)w * PLANES_PER_WINDOW * jb, sums + jb * (size_t)w)) all_ok = false;
     });
-    if (s.wide_bits) {  // virtual windows: sum_hi W_hi + 2^15 sum_hi hi TC_hi (host_g1.h), one chain per MSM of the launch
-      combine_pool().run(s.nvec, [&](int v) {
+    if (p.wide_bits) {  // V virtual windows: V sum_vw W_vw - sum_{j=0}^{V-2} (TC_0 + ... + TC_j) (host_g1.h: combine_wide_strided), one chain per MSM
+      combine_pool().run(p.nvec, [&](int v) {
         if (!ctx->ops->combine_wide(sums + jb * (size_t)v * nwin, s.h_wsums + (size_t)v * nwin * PLANES_PER_WINDOW * jb, nwin, out_xyz + jb * (size_t)v)) all_ok = false;
       });
-    } else if (!ctx->ops->combine_windows(sums, nwin, combine_bits, out_xyz)) all_ok = false;
+    } else if (!ctx->ops->combine_windows(sums, nwin, p.combine_bits, out_xyz)) all_ok = false;
   } else {
-    combine_pool().run(s.nvec, [&](int v) {  // one independent Horner chain per MSM of the launch: side by side when there are several
-      if (!ctx->ops->combine_windows(s.h_wsums + (size_t)v * nwin * ctx->jb, nwin, combine_bits, out_xyz + ctx->jb * (size_t)v)) all_ok = false;
+    combine_pool().run(p.nvec, [&](int v) {  // one independent Horner chain per MSM of the launch: side by side when there are several
+      if (!ctx->ops->combine_windows(s.h_wsums + (size_t)v * nwin * ctx->jb, nwin, p.combine_bits, out_xyz + ctx->jb * (size_t)v)) all_ok = false;
     });
   }
   if (!all_ok) return MSM_HIP_ERR_HIP;
@@ -1387,7 +1344,7 @@ int msm_hip_finish_batch(msm_hip_ctx* ctx, int slot, uint8_t* out_xyz) {
 }
 
 int msm_hip_finish(msm_hip_ctx* ctx, int slot, uint8_t out_xyz[96]) {
-  if (!ctx || slot < 0 || slot >= NSLOT || ctx->slot[slot].nvec != 1) return MSM_HIP_ERR_INVALID_ARG;
+  if (!ctx || slot < 0 || slot >= NSLOT || ctx->slot[slot].plan.nvec != 1) return MSM_HIP_ERR_INVALID_ARG;
   return msm_hip_finish_batch(ctx, slot, out_xyz);
 }
 
@@ -1403,7 +1360,21 @@ int msm_hip_run_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, uint
 }  // extern "C"
 
 namespace {
-// host scalars -> the slot's own staging buffer (copy stream) -> windows [w_begin, w_end) of one MSM into `slot`
+// host scalars -> slot `s`'s own staging buffer (idle, since the slot is not pending; its capacity counts 32-byte scalars) on copy stream `cs`, so
+// that the copy overlaps whatever the main and reduce streams still hold of earlier launches (a caller that alternates two slots gets the copy of
+// MSM i+1 under the device work of MSM i); the main stream waits for it on the device.  From pageable memory the call returns when the bytes have
+// left the caller's buffer; from pinned memory (hipHostMalloc / hipHostRegister) at once -- the buffer must then stay untouched until finish /
+// slot_sync.  `count` scalars, of which `bytes` cross the link.
+int stage_host_scalars(msm_hip_ctx* ctx, Slot& s, hipStream_t cs, const void* scalars_host, size_t count, size_t bytes) {
+  const int rc = grow(ctx, s.cap_host_scalars, count, false, [&](size_t c) { return dev_alloc(ctx, s.d_host_scalars, c * 8); });
+  if (rc) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, bytes, hipMemcpyHostToDevice, cs));
+  HIP_TRY(ctx, hipEventRecord(s.staged, cs));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
+  return MSM_HIP_OK;
+}
+
+// host scalars -> the slot's own staging buffer -> windows [w_begin, w_end) of one MSM into `slot`
 // (windows in units of the reference's 16-bit windows; `auto_bits`: a whole MSM whose window size follows n)
 int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, int w_begin, int w_end, int slot, void* window_sums_dev,
                         bool auto_bits = false) {
@@ -1413,28 +1384,19 @@ int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n,
   // narrow scalars: n x 1 .. 8 bytes cross the link as they are (never widened on the host); whole MSMs only
   const int nb = narrow_bytes(ctx->scalar_format);
   if (nb && !auto_bits) return MSM_HIP_ERR_INVALID_ARG;
-  const size_t sbytes = nb ? (size_t)nb : 32;
   ON_DEVICE(ctx);
   Slot& s = ctx->slot[slot];
   if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
   if (n == 0) return launch_impl(ctx, scalars_host, 0, 1, w_begin, w_end, WBITS, slot, window_sums_dev);
   if ((rc = setup_slot(ctx, s))) return rc;
   if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  if (n > s.cap_host_scalars) {  // the slot's own staging buffer: idle, since the slot is not pending
-    s.cap_host_scalars = 0;
-    if ((rc = dev_alloc(ctx, s.d_host_scalars, n * 8))) return rc;
-    s.cap_host_scalars = n;
-  }
-  // H2D on the copy stream, so that it overlaps whatever the main and reduce streams still hold of earlier launches
-  // (a caller that alternates two slots gets the copy of MSM i+1 under the device work of MSM i); the main stream waits
-  // for it on the device.  From pageable memory the call returns when the bytes have left the caller's buffer; from
-  // pinned memory (hipHostMalloc / hipHostRegister) at once -- the buffer must then stay untouched until finish / slot_sync.
-  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, n * sbytes, hipMemcpyHostToDevice, ctx->copy_stream));
-  HIP_TRY(ctx, hipEventRecord(s.staged, ctx->copy_stream));
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
+  if ((rc = stage_host_scalars(ctx, s, ctx->copy_stream, scalars_host, n, n * (nb ? (size_t)nb : 32)))) return rc;
   if (auto_bits) return msm_hip_launch_windows_batch_device(ctx, s.d_host_scalars, n, 1, 0, NWIN, slot, nullptr);
   return launch_impl(ctx, s.d_host_scalars, n, 1, w_begin, w_end, WBITS, slot, window_sums_dev);
 }
+
+// first point of part k of n points split into `parts` ranges (the first n % parts ranges take one more)
+inline size_t part_first(size_t n, int parts, int k) { return n / parts * k + std::min(n % parts, (size_t)k); }
 }  // namespace
 
 extern "C" {
@@ -1456,7 +1418,7 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
     uint8_t sums[NSLOT * MAX_JB];
     int rc = MSM_HIP_OK, launched = 0;
     for (int k = 0; k < parts && !rc; k++) {
-      const size_t first = n / parts * k + (n % parts < (size_t)k ? n % parts : (size_t)k), next = n / parts * (k + 1) + (n % parts < (size_t)(k + 1) ? n % parts : (size_t)(k + 1));
+      const size_t first = part_first(n, parts, k), next = part_first(n, parts, k + 1);
       ctx->launch_base_off = first;
       rc = msm_hip_launch(ctx, scalars_host + first * 32, next - first, k);
       ctx->launch_base_off = 0;
@@ -1498,12 +1460,7 @@ int msm_hip_run_batch(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, s
   }
   ON_DEVICE(ctx);
   const size_t vec = n * (narrow_bytes(ctx->scalar_format) ? (size_t)narrow_bytes(ctx->scalar_format) : 32), entry = vec * batch_group(ctx, n, batch);
-  if (entry * NSLOT > ctx->cap_batch_stage) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->cap_batch_stage = 0;
-    if ((rc = dev_alloc(ctx, ctx->d_batch_stage, entry * NSLOT))) return rc;
-    ctx->cap_batch_stage = entry * NSLOT;
-  }
+  if ((rc = grow(ctx, ctx->cap_batch_stage, entry * NSLOT, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_batch_stage, c); }))) return rc;
   // group j is staged in ring entry j % NSLOT on the main stream just ahead of its own sort (the entry's previous
   // reader, group j - NSLOT, was finished DEPTH + 1 iterations ago)
   return run_batch_groups(ctx, n, batch, out_xyz, [&](size_t j, size_t first, size_t count, const void** dev) {
@@ -1593,17 +1550,17 @@ inline bool oneshot_keep() {
 
 namespace {
 // The one-shot call on a kept (or fresh) context, OVERLAPPED (round 5): the reference uploads everything, then dispatches (src/cuzk/msm.rs:84-94,
-// 441-480); here the 32 n bytes of scalars go first and their recode + sort (everything that needs the scalars alone: launch phase 1) runs while
+// 441-480); here the 32 n bytes of scalars go first and their recode + sort (everything that needs the scalars alone: enqueue_sort) runs while
 // the 64 n bytes of points are still arriving -- in chunks on the copy stream, each converted to the device form (and its endomorphism image
-// made) as soon as it has landed --, and only the SMVP (launch phase 2) waits for the last chunk.  Hidden: the sort (~0.26 ms at 2^20), the
+// made) as soon as it has landed --, and only the SMVP (enqueue_reduce) waits for the last chunk.  Hidden: the sort (~0.26 ms at 2^20), the
 // conversion kernels (~0.1 ms) and one host synchronisation.  MSM_HIP_ONESHOT_OVERLAP=0: upload, convert, then run (rounds 1 - 4).
 // Two halves: oneshot_enqueue queues everything (copies on `cs` -- the copy stream of the call's FIRST part, so that the parts' uploads follow each
-// other instead of sharing the link -- and both launch phases), oneshot_collect waits for the result.  `he_out`: the first HIP error of the
+// other instead of sharing the link -- and both launch stages), oneshot_collect waits for the result.  `he_out`: the first HIP error of the
 // chunk loop (the launch is completed regardless, its result discarded).
 int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, const uint8_t* scalars_host, size_t n, hipError_t* he_out, bool* queued) {
   ON_DEVICE(ctx);
   *he_out = hipSuccess;
-  *queued = false;  // true: the launch was taken to its second phase -- oneshot_collect has to follow, whatever this function returns
+  *queued = false;  // true: the launch was taken to its reduce stage -- oneshot_collect has to follow, whatever this function returns
   const uint32_t flags = resolve_base_flags(ctx, n, 0);
   const bool endo = (flags & MSM_HIP_BASES_ENDOMORPHISM) != 0;
   int rc = reserve_bases(ctx, n, flags);  // (waits for the main stream: nothing is reading the old bases)
@@ -1612,23 +1569,22 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
   if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
   if ((rc = setup_slot(ctx, s))) return rc;
   if (!ctx->bases_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->bases_ready, hipEventDisableTiming));
-  if (n > s.cap_host_scalars) {
-    s.cap_host_scalars = 0;
-    if ((rc = dev_alloc(ctx, s.d_host_scalars, n * 8))) return rc;
-    s.cap_host_scalars = n;
-  }
   // 1. the scalars, and their sort
-  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, n * 32, hipMemcpyHostToDevice, cs));
-  HIP_TRY(ctx, hipEventRecord(s.staged, cs));
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
+  if ((rc = stage_host_scalars(ctx, s, cs, scalars_host, n, n * 32))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_err, 0, 4, cs));  // (ahead of every chunk's copy, hence of every conversion)
   ctx->n_bases = n;  // (what the launch checks n against; the records themselves follow below)
   ctx->endo = endo;
-  const LaunchMode mode = endo ? MODE_HALVES : MODE_PLAIN;
-  const int wbits = pick_window_bits(ctx, n, 1, endo), w_end = nwin_of(wbits, endo);
+  const int wbits = pick_window_bits(ctx, n, 1, endo);
   ctx->sync_call = true;
-  rc = launch_impl(ctx, s.d_host_scalars, n, 1, 0, w_end, wbits, 0, nullptr, mode, 0, 0, 1);
-  if (rc) {
+  LaunchPlan p;
+  auto sort = [&]() -> int {
+    int r = plan_launch(ctx, p, endo ? MODE_HALVES : MODE_PLAIN, s.d_host_scalars, n, 1, 0, nwin_of(wbits, endo), wbits, 0, nullptr, 0, 0);
+    if (!r) r = ensure_work(ctx, p, s);
+    if (!r) r = enqueue_sort(ctx, p, s, s.d_host_scalars);
+    if (!r) HIP_TRY(ctx, hipGetLastError());
+    return r;
+  };
+  if ((rc = sort())) {
     ctx->sync_call = false;
     ctx->n_bases = 0;
     return rc;
@@ -1658,10 +1614,10 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
   }
   if (he == hipSuccess) he = hipEventRecord(ctx->bases_ready, conv);
   if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->bases_ready, 0);
-  // 3. the rest of the launch (on failure above too: phase 1 left the slot's streams mid-launch -- the bases it then reads are whatever arrived,
+  // 3. the rest of the launch (on failure above too: the sort left the slot's streams mid-launch -- the bases it then reads are whatever arrived,
   //    and the result is discarded)
   *queued = true;
-  rc = launch_impl(ctx, s.d_host_scalars, n, 1, 0, w_end, wbits, 0, nullptr, mode, 0, 0, 2);
+  rc = enqueue_reduce(ctx, p, s);
   ctx->sync_call = false;
   *he_out = he;
   return rc;
@@ -1730,7 +1686,7 @@ int msm_hip_msm_curve(int curve, const uint8_t* xy_host, const uint8_t* scalars_
     uint8_t sums[ONESHOT_MAX_PARTS * MAX_JB];
     const size_t pb = c0->pb, jb = c0->jb;
     size_t first[ONESHOT_MAX_PARTS + 1];
-    for (int k = 0; k <= parts; k++) first[k] = n / parts * k + (n % parts < (size_t)k ? n % parts : (size_t)k);
+    for (int k = 0; k <= parts; k++) first[k] = part_first(n, parts, k);
     for (int k = 0; k < parts && !rc; k++) {
       prc[k] = oneshot_enqueue(ctxs[k], c0->copy_stream, xy_host + first[k] * pb, scalars_host + first[k] * 32, first[k + 1] - first[k], &phe[k], &queued[k]);
       if (prc[k] && !queued[k]) rc = prc[k];  // nothing of this part is in flight: stop queueing, drain the earlier ones
@@ -1858,7 +1814,7 @@ int msm_hip_window_config(int bits, int* num_windows, int* buckets_per_window) {
   return MSM_HIP_OK;
 }
 
-int msm_hip_last_window_bits(msm_hip_ctx* ctx) { return ctx ? ctx->last_wbits : MSM_HIP_ERR_INVALID_ARG; }
+int msm_hip_last_window_bits(msm_hip_ctx* ctx) { return ctx ? ctx->last.wbits : MSM_HIP_ERR_INVALID_ARG; }
 
 int msm_hip_endomorphism_window_count(int bits) {
   if (bits != 12 && bits != 14 && bits != 16) return MSM_HIP_ERR_INVALID_ARG;
@@ -1887,29 +1843,29 @@ int msm_hip_set_debug(msm_hip_ctx* ctx, int keep_digit_planes) {
 }
 
 int msm_hip_read_digits(msm_hip_ctx* ctx, uint16_t* out, size_t cap_elems) {
-  if (!ctx || !ctx->last_has_digits) return MSM_HIP_ERR_INVALID_ARG;
-  return read_back(ctx, out, ctx->d_digits, ctx->last_n * ctx->last_w_count * 2, cap_elems * 2);
+  if (!ctx || !ctx->last.digits) return MSM_HIP_ERR_INVALID_ARG;
+  return read_back(ctx, out, ctx->d_digits, ctx->last.n_sc * ctx->last.w_count * 2, cap_elems * 2);
 }
 int msm_hip_read_col_ptr(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
-  const size_t half = (size_t)1 << (ctx->last_wbits - 1);  // [w][half + 1]
-  return read_back(ctx, out, ctx->slot[ctx->last_slot].d_col_ptr, (size_t)ctx->last_w_count * (half + 1) * 4, cap_elems * 4);
+  const size_t half = (size_t)1 << (ctx->last.wbits - 1);  // [w][half + 1]
+  return read_back(ctx, out, ctx->slot[ctx->last_slot].d_col_ptr, (size_t)ctx->last.w_count * (half + 1) * 4, cap_elems * 4);
 }
 int msm_hip_read_val_idxs(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
   // out[w][n]; only the first col_ptr[w][32768] entries of each window are meaningful
-  const size_t n = ctx->last_n;
-  if (!out || n * ctx->last_w_count > cap_elems) return MSM_HIP_ERR_INVALID_ARG;
+  const size_t n = ctx->last.n_sc;
+  if (!out || n * ctx->last.w_count > cap_elems) return MSM_HIP_ERR_INVALID_ARG;
   if (n == 0) return MSM_HIP_OK;
   ON_DEVICE(ctx);
-  HIP_TRY(ctx, hipMemcpy2DAsync(out, n * 4, ctx->d_val, ctx->last_stride * 4, n * 4, (size_t)ctx->last_w_count, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipMemcpy2DAsync(out, n * 4, ctx->d_val, ctx->last.stride * 4, n * 4, (size_t)ctx->last.w_count, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MSM_HIP_OK;
 }
 
 int msm_hip_read_buckets(msm_hip_ctx* ctx, uint8_t* out, size_t cap_bytes) {
   if (!ctx || !out) return MSM_HIP_ERR_INVALID_ARG;
-  const size_t count = (size_t)ctx->last_w_count << (ctx->last_wbits - 1);  // [w][2^(bits-1)]
+  const size_t count = (size_t)ctx->last.w_count << (ctx->last.wbits - 1);  // [w][2^(bits-1)]
   if (count * ctx->jb > cap_bytes) return MSM_HIP_ERR_INVALID_ARG;
   if (count == 0) return MSM_HIP_OK;
   ON_DEVICE(ctx);
@@ -1925,9 +1881,9 @@ int msm_hip_read_buckets(msm_hip_ctx* ctx, uint8_t* out, size_t cap_bytes) {
 int msm_hip_read_window_sums(msm_hip_ctx* ctx, uint8_t* out, size_t cap_bytes) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
   const Slot& s = ctx->slot[ctx->last_slot];
-  if (!s.parts) return read_back(ctx, out, s.d_wsums, (size_t)ctx->last_w_count * ctx->jb, cap_bytes);
+  if (!s.parts) return read_back(ctx, out, s.d_wsums, (size_t)ctx->last.w_count * ctx->jb, cap_bytes);
   // the last launch handed its window sums to the host as bit-plane sums (k_bpr_planes): finish them here
-  const size_t w = (size_t)ctx->last_w_count;
+  const size_t w = (size_t)ctx->last.w_count;
   if (!out || w * ctx->jb > cap_bytes || w > 24) return MSM_HIP_ERR_INVALID_ARG;
   const size_t plane_bytes = PLANES_PER_WINDOW * ctx->jb;
   {  // (the plane sums were written into the slot's pinned buffer by the launch's last kernel: complete once its reduce stream has drained)

@@ -124,14 +124,7 @@ int mgpu_enqueue_on_device(msm_hip_mgpu* m, int d, int k, const void* scalars, b
     if ((rc = setup_slot(ctx, s))) return rc;
     if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
     const size_t count = (size_t)nvec * n;
-    if (count > s.cap_host_scalars) {
-      s.cap_host_scalars = 0;
-      if ((rc = dev_alloc(ctx, s.d_host_scalars, count * 8))) return rc;
-      s.cap_host_scalars = count;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars, count * 32, hipMemcpyHostToDevice, ctx->copy_stream));
-    HIP_TRY(ctx, hipEventRecord(s.staged, ctx->copy_stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
+    if ((rc = stage_host_scalars(ctx, s, ctx->copy_stream, scalars, count, count * 32))) return rc;
     dev = s.d_host_scalars;
   }
   void* sums = m->rccl ? ms.d_send[d] : nullptr;  // host gather: the sums leave through the context slot's pinned buffer
