@@ -219,6 +219,23 @@ int msm_hip_finish(msm_hip_ctx* ctx, int slot, uint8_t out_xyz[96]);
  * hipHostRegister): returns at once and the buffer must stay untouched until the slot is collected. */
 int msm_hip_launch(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, int slot);
 
+/* ---- sparse: out = sum_{j < nnz} scalars[j] * P[indices[j]] over the resident bases.  Scalars are in the context's scalar format (canonical,
+ *      MONT256, U8 .. U64), nnz of them.  Indices are uint32, in any order; repeats are allowed and their terms add.  Each index must be < n_bases
+ *      of the last set_bases.
+ *      - Every curve, with plain bases, endomorphism bases and 16-bit fixed-base tables; narrow formats use the plain records, as dense narrow
+ *        MSMs do.  Wide tables (MSM_HIP_BASES_PRECOMPUTE_WIDE) are out of scope: MSM_HIP_ERR_INVALID_ARG.
+ *      - Whole MSMs only: the window-sharded, batch and multi-GPU entry points have no sparse form.
+ *      - nnz == 0 gives the identity; nnz may exceed n_bases (repeats) and is bounded as n is (2^28).  The window size follows nnz as for a dense
+ *        MSM of nnz points; msm_hip_set_window_bits overrides it.
+ *      - msm_hip_run_sparse checks the host indices before anything is enqueued (MSM_HIP_ERR_INVALID_ARG) and uploads both arrays once, into
+ *        slot 0's staging buffer.  Device indices are checked by the kernels: an index >= n_bases counts as a zero scalar, and msm_hip_finish /
+ *        the run call returns MSM_HIP_ERR_INVALID_ARG.  Either way the context and the slot stay usable.
+ *      - launch_sparse_device enqueues into `slot` like msm_hip_launch_device; msm_hip_finish collects it.
+ *      (Added within ABI version 7.) ---- */
+int msm_hip_run_sparse(msm_hip_ctx* ctx, const uint32_t* indices_host, const uint8_t* scalars_host, size_t nnz, uint8_t out_xyz[96]);
+int msm_hip_run_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, uint8_t out_xyz[96]);
+int msm_hip_launch_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot);
+
 /* ---- batch: `batch` independent scalar vectors (batch x n x 32 B, contiguous, device memory) over the resident bases;
  *      out: batch x 96 B.  Internally a software pipeline over the result slots (BASELINE.json config 5: many MSMs over
  *      one shared base). ---- */
@@ -383,7 +400,8 @@ int msm_hip_set_debug(msm_hip_ctx* ctx, int keep_digit_planes);
  * whenever such a bin can exist); tests raise it to drive the fallback in which every sharer of a bin histograms it itself */
 int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n);
 /* the number of coming launches for which the fine sort's sub-range histograms (k_fine_hist) run because an earlier launch met a huge coarse
- * bin (skewed 32-byte scalars arm it for 64 launches; narrow-scalar launches neither arm nor consume it) */
+ * bin (skewed 32-byte scalars arm it for 64 launches; narrow-scalar launches neither arm nor consume it).  Sparse launches follow the rule of
+ * their scalar format: 32-byte ones arm and consume it as dense launches do, narrow ones leave it alone. */
 int msm_hip_test_skew_credit(const msm_hip_ctx* ctx);
 int msm_hip_read_digits(msm_hip_ctx* ctx, uint16_t* out, size_t cap_elems);
 int msm_hip_read_col_ptr(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems);
@@ -414,7 +432,7 @@ int msm_hip_test_oneshot_parts(int parts, size_t min_points);
 const char* msm_hip_strerror(int code);
 int msm_hip_last_hip_error(msm_hip_ctx* ctx);
 /* ABI version; bumped on any signature change or addition (7 = round 5: curve-neutral names with the `_bn254` aliases kept, the virtual-window
- * launches and their pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits) */
+ * launches and their pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits; the three sparse calls arrived within version 7) */
 int msm_hip_abi_version(void);
 
 /* ---- aliases: the names of rounds 1 - 4 (the reference instantiates its generic functions with halo2curves::bn256 only, src/lib.rs:91,154). Each is

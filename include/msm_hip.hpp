@@ -138,6 +138,32 @@ class MsmContext {
     for (size_t k = 0; k < vs.size(); k++) std::memcpy(r[k].xyz.data(), out.data() + 96 * k, 96);
     return r;
   }
+  /// Sparse MSMs: sum_j scalars[j] * P[indices[j]] over the resident bases (msm_hip_run_sparse ...): indices in any order, repeats add up.
+  /// msm_sparse_bytes takes nnz scalars in the context's scalar format; out-of-range indices throw before anything is enqueued.
+  G1 msm_sparse(const std::vector<uint32_t>& indices, const std::vector<Fr>& v) {
+    if (indices.size() != v.size()) throw std::invalid_argument("msm_sparse: one index per scalar");
+    const std::vector<uint8_t> b = scalars_to_bytes(v);
+    return msm_sparse_bytes(indices.data(), b.data(), v.size());
+  }
+  G1 msm_sparse_bytes(const uint32_t* indices, const uint8_t* scalars, size_t nnz) {
+    G1 r;
+    check(msm_hip_run_sparse(ctx_, indices, scalars, nnz, r.xyz.data()), "msm_hip_run_sparse");
+    return r;
+  }
+  G1 msm_sparse_device(const uint32_t* indices_dev, const void* scalars_dev, size_t nnz) {
+    G1 r;
+    check(msm_hip_run_sparse_device(ctx_, indices_dev, scalars_dev, nnz, r.xyz.data()), "msm_hip_run_sparse_device");
+    return r;
+  }
+  /// asynchronous form: enqueue into result slot `slot`; finish(slot) collects it
+  void launch_sparse_device(const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot) {
+    check(msm_hip_launch_sparse_device(ctx_, indices_dev, scalars_dev, nnz, slot), "msm_hip_launch_sparse_device");
+  }
+  G1 finish(int slot) {
+    G1 r;
+    check(msm_hip_finish(ctx_, slot, r.xyz.data()), "msm_hip_finish");
+    return r;
+  }
   msm_hip_ctx* raw() { return ctx_; }
 
  private:

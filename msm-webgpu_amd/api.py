@@ -78,6 +78,9 @@ def lib():
         L.msm_hip_run_batch_device.argtypes = [vp, vp, sz, sz, u8p]
         L.msm_hip_launch_device.argtypes = [vp, vp, sz, i]
         L.msm_hip_launch.argtypes = [vp, u8p, sz, i]
+        L.msm_hip_run_sparse.argtypes = [vp, vp, u8p, sz, u8p]
+        L.msm_hip_run_sparse_device.argtypes = [vp, vp, vp, sz, u8p]
+        L.msm_hip_launch_sparse_device.argtypes = [vp, vp, vp, sz, i]
         L.msm_hip_wait_stream.argtypes = [vp, vp]
         L.msm_hip_finish.argtypes = [vp, i, u8p]
         L.msm_hip_run_windows_device.argtypes = [vp, vp, sz, i, i, vp]
@@ -258,6 +261,31 @@ def _as_device_scalars(t, width, what="scalars"):
     return t, n
 
 
+def _host_indices(indices, n_bases):
+    """Host base indices of a sparse MSM (a numpy array or anything numpy takes) -> contiguous uint32, every one checked against n_bases."""
+    a = np.asarray(indices).reshape(-1)
+    if a.dtype.kind not in "iu":
+        raise TypeError("indices must be integers, not %s" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= n_bases):
+        raise ValueError("indices must lie in [0, %d): found %d .. %d" % (n_bases, int(a.min()), int(a.max())))
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def _device_indices(t):
+    """Device base indices of a sparse MSM (a CUDA int64 / int32 / uint32 tensor) -> contiguous 32-bit words holding the uint32 indices.  Values
+    outside the uint32 range become 0xffffffff (a negative int32 already reads as a huge uint32): the kernels reject them like any index beyond
+    the bases, and finish raises."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise TypeError("device scalars take device indices (a CUDA integer tensor)")
+    t = t.reshape(-1)
+    if t.dtype == torch.int64:
+        t = torch.where((t < 0) | (t > 0xFFFFFFFF), torch.full_like(t, 0xFFFFFFFF), t)
+        return torch.where(t >= 1 << 31, t - (1 << 32), t).to(torch.int32)
+    if t.dtype == torch.int32 or t.dtype == getattr(torch, "uint32", None):
+        return t.contiguous()
+    raise TypeError("indices must be int64, int32 or uint32, not %s" % t.dtype)
+
+
 class MsmContext:
     """Persistent engine on one GPU: stream, pooled buffers, resident bases (include/msm_hip.h)."""
 
@@ -361,6 +389,38 @@ class MsmContext:
         self._order_after_torch(t)
         _check(lib().msm_hip_run_batch_device(self._h, t.data_ptr(), n, batch, out), "msm_hip_run_batch_device")
         return [G1(out.raw[self.jb * k:self.jb * (k + 1)], self.modulus) for k in range(batch)]
+
+    def msm_sparse(self, indices, scalars):
+        """sum_j scalars[j] * bases[indices[j]] -> G1 (msm_hip_run_sparse): nnz entries, indices in any order, repeats adding up.  Both on the
+        device (CUDA tensors: indices int64 / int32 / uint32, scalars as for msm) or both on the host (numpy arrays or bytes).  Host indices are
+        checked here: a negative or out-of-range one raises ValueError before anything reaches the device; device indices are checked by the
+        kernels (MsmHipError, the context stays usable)."""
+        out = C.create_string_buffer(self.jb)
+        if isinstance(scalars, torch.Tensor) and scalars.is_cuda:
+            ix = _device_indices(indices)
+            t, nnz = _as_device_scalars(scalars, self.scalar_width)
+            if ix.numel() != nnz:
+                raise ValueError("%d indices for %d scalars" % (ix.numel(), nnz))
+            self._order_after_torch(t)
+            _check(lib().msm_hip_run_sparse_device(self._h, ix.data_ptr(), t.data_ptr(), nnz, out), "msm_hip_run_sparse_device")
+        else:
+            ix = _host_indices(indices, self.n_bases)
+            b, nnz = self._host_scalars(scalars)
+            if ix.size != nnz:
+                raise ValueError("%d indices for %d scalars" % (ix.size, nnz))
+            _check(lib().msm_hip_run_sparse(self._h, ix.ctypes.data, b, nnz, out), "msm_hip_run_sparse")
+        return G1(out.raw, self.modulus)
+
+    def launch_sparse(self, indices, scalars, slot=0):
+        """msm_sparse's device work into a result slot (0..3), returning at once (msm_hip_launch_sparse_device); finish(slot) collects it.
+        Device tensors only."""
+        ix = _device_indices(indices)
+        t, nnz = _as_device_scalars(scalars, self.scalar_width)
+        if ix.numel() != nnz:
+            raise ValueError("%d indices for %d scalars" % (ix.numel(), nnz))
+        self._order_after_torch(t)
+        _check(lib().msm_hip_launch_sparse_device(self._h, ix.data_ptr(), t.data_ptr(), nnz, slot), "msm_hip_launch_sparse_device")
+        self._keepalive[slot] = (ix, t)
 
     def launch(self, scalars_dev, slot=0):
         """Enqueue the device work of one MSM into a result slot (0..3) and return at once."""

@@ -111,6 +111,8 @@ struct LaunchPlan {
   uint32_t tiles = 0, tile_len = 0, subtiles = 0;  // tiles of scalars of the two global sort passes; LIST_SUB sub-tiles
   uint32_t chunks = 0, chunk_len = 0;              // SMVP chunks per local window and their (longest) length
   size_t stride = 0;                               // per-window stride of the entry arrays
+  bool sparse = false;                             // a sparse launch: input j is (scalar j, base indices[j]); n counts entries (SparseIdx)
+  const uint32_t* indices = nullptr;               // sparse: the n base indices (device)
 };
 
 struct Slot {
@@ -556,27 +558,30 @@ inline unsigned blocks_for(size_t n, unsigned block) { return (unsigned)((n + bl
 int err_from_bits(uint32_t bits) {
   if (bits & ERRBIT_NOT_ON_CURVE) return MSM_HIP_ERR_NOT_ON_CURVE;
   if (bits & (ERRBIT_NONCANONICAL | ERRBIT_SCALAR_CARRY)) return MSM_HIP_ERR_NONCANONICAL;
+  if (bits & ERRBIT_BAD_INDEX) return MSM_HIP_ERR_INVALID_ARG;  // a sparse launch's device index was out of range (it counted as a zero scalar)
   return MSM_HIP_OK;
 }
 
 // Does a launch's second sort pass read digit planes left by the first (k_scatter_planes) instead of the scalars again?  Yes for window
 // shares -- at most PLANES_MAX_W of a vector's windows (8 GPUs: 2 of 16, or 1 of 8 half-length windows): 2 B per (input, window) instead
 // of 32 B per scalar, and no scalars held in registers.  Not for fixed-base tables (one bucket set per vector) and not while the debug
-// read-back wants the planes in its own format.  MSM_HIP_PLANES_MAX_W overrides the limit (0: never; tuning aid).
-inline bool use_planes(const msm_hip_ctx* ctx, LaunchMode mode, int w_count_vec, int wbits) {
+// read-back wants the planes in its own format.  MSM_HIP_PLANES_MAX_W overrides the limit (0: never; tuning aid).  Never for sparse launches
+// (k_scatter_planes writes positions, not the entries' base indices), whatever the tuning aids say.
+inline bool use_planes(const msm_hip_ctx* ctx, LaunchMode mode, int w_count_vec, int wbits, bool sparse) {
   static const int max_w = [] { const char* e = getenv("MSM_HIP_PLANES_MAX_W"); return e ? atoi(e) : 8; }();
   static const bool whole = [] { const char* e = getenv("MSM_HIP_PLANES_WHOLE"); return e && e[0] == '1'; }();  // A/B aid: whole MSMs too
-  if (mode == MODE_TABLES || mode == MODE_WIDE || mode == MODE_NARROW || ctx->debug) return false;
+  if (sparse || mode == MODE_TABLES || mode == MODE_WIDE || mode == MODE_NARROW || ctx->debug) return false;
   if (whole) return true;
   return w_count_vec <= max_w && w_count_vec < nwin_of(wbits, mode == MODE_HALVES);
 }
 
 constexpr size_t MAX_POINTS = (size_t)1 << 28;  // point indices carry the digit sign in bit 31; 2^28 keeps every per-window offset in u32
 
-int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n) {
+// (sparse: n entries, which may outnumber the bases -- their indices repeat)
+int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n, bool sparse = false) {
   if (!ctx || (!scalars && n) || n > MAX_POINTS) return MSM_HIP_ERR_INVALID_ARG;
   if (ctx->n_bases == 0 && n) return MSM_HIP_ERR_NO_BASES;
-  if (n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  if (n > ctx->n_bases && !sparse) return MSM_HIP_ERR_INVALID_ARG;
   return MSM_HIP_OK;
 }
 
@@ -585,16 +590,20 @@ int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n) {
 // (MODE_WIDE: called with the tables' digit width and all T digits; everything behind the recode sees local windows of 16 bits.  v_count != 0: a
 //  SHARE of the virtual windows -- [v_begin, v_begin + v_count) of every vector; its sums are (window sum, plain total) pairs, 2 records per local
 //  window.  0: whole MSMs, all 2^(C-16) virtual windows)
+// `sparse`: n entries (scalar j, base indices[j]) -- one whole MSM, into the slot, over the resident bases from record 0; not on wide tables.
 int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* scalars, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
-                void* sums_dev, int v_begin, int v_count) {
+                void* sums_dev, int v_begin, int v_count, bool sparse = false, const uint32_t* indices = nullptr) {
   const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
   const bool pairs = wide && v_count != 0;
   const int nb = ctx && mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;
-  int rc = check_run_args(ctx, scalars, n);
+  int rc = check_run_args(ctx, scalars, n, sparse);
   const size_t base_off = ctx ? ctx->launch_base_off : 0;
   if (ctx) ctx->launch_base_off = 0;
   if (rc) return rc;
-  if (base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  if (sparse && (wide || (!indices && n) || nvec != 1 || sums_dev || base_off || w_begin != 0 ||
+                 w_end != (nb ? narrow_windows(wbits, nb) : merge ? NWIN : nwin_of(wbits, halves))))
+    return MSM_HIP_ERR_INVALID_ARG;
+  if (!sparse && base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
   if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > (nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves)) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
   // narrow scalars: whole MSMs only, over the plain records, from a pointer aligned to the scalar's size
   if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != narrow_windows(wbits, nb) || sums_dev || base_off || nvec * w_end > narrow_max_windows(nb) ||
@@ -641,7 +650,7 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
   p.full_windows = wide ? wide_vwin_of(ctx->wide_bits) : merge ? 1 : halves ? nwin_of(wbits, true) : nb ? w_count_vec : NWIN;
   p.digits = ctx->debug && !merge && !wide && !byte_windows(nb);
   // window shares (a few of a scalar's windows per vector): the first pass leaves digit planes, the second reads them (k_scatter_planes)
-  p.planes = use_planes(ctx, mode, w_count_vec, p.wbits);
+  p.planes = use_planes(ctx, mode, w_count_vec, p.wbits, sparse);
   // shares of at most WIDE_SHARE_VWIN_MAX virtual windows of wide tables: the first pass leaves compact lists of the share's entries per sub-tile of
   // LIST_SUB scalars (k_count_wide_list / k_scatter_list); tiles are then whole sub-tiles.  MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape (A/B aid)
   static const bool share_lists = [] { const char* e = getenv("MSM_HIP_WIDE_SHARE_LISTS"); return !e || atoi(e) != 0; }();
@@ -662,6 +671,8 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
     p.chunks = chunks_for(p.n_entries, p.chunk_len);
   }
   p.stride = stride_for(p.n_entries);
+  p.sparse = sparse;
+  p.indices = indices;
   return MSM_HIP_OK;
 }
 
@@ -707,6 +718,9 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
   uint16_t* digits = p.digits ? ctx->d_digits : nullptr;
   uint16_t* plane_out = p.planes ? ctx->d_digits : digits;
   const int plane_mode = p.planes ? 2 : (digits ? 1 : 0);
+  // sparse launches: the same passes instantiated with one more argument (msm_kernels.h: SparseIdx) -- the count passes guard the indices, the
+  // scatter passes write them in place of the positions
+  const SparseIdx sp{p.indices, (uint32_t)ctx->n_bases, d_err};
   if (wide) {
     dispatch<16, 17, 18, 19, 20>(p.wide_bits, [&](auto c) {
       constexpr int C = decltype(c)::value;
@@ -719,19 +733,31 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
     });
   } else if (bytes) {
     dispatch<1, 2>(p.nb, [&](auto b) {
-      hipLaunchKernelGGL(k_byte_count<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.tile_len, p.tiles, ctx->d_counts);
+      if (p.sparse)
+        hipLaunchKernelGGL((k_byte_count<decltype(b)::value, SparseIdx>), grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.tile_len, p.tiles, ctx->d_counts, sp);
+      else
+        hipLaunchKernelGGL(k_byte_count<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.tile_len, p.tiles, ctx->d_counts);
     });
   } else if (halves) {
-    hipLaunchKernelGGL(ctx->ops->count_split[p.wbits == 16 ? 2 : p.wbits == 14 ? 1 : 0], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin,
-                       p.w_count_vec, p.nvec, p.n * 8, ctx->d_counts, plane_out, plane_mode, p.planes ? ctx->d_negbits : nullptr,
-                       p.planes ? nullptr : ctx->d_halves, d_err, merge_nb);
+    const int k = p.wbits == 16 ? 2 : p.wbits == 14 ? 1 : 0;
+    if (p.sparse)
+      hipLaunchKernelGGL(ctx->ops->count_split_sparse[k], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec, p.n * 8,
+                         ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, ctx->d_halves, d_err, merge_nb, sp);
+    else
+      hipLaunchKernelGGL(ctx->ops->count_split[k], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin,
+                         p.w_count_vec, p.nvec, p.n * 8, ctx->d_counts, plane_out, plane_mode, p.planes ? ctx->d_negbits : nullptr,
+                         p.planes ? nullptr : ctx->d_halves, d_err, merge_nb);
     d_scalars = ctx->d_halves;
   } else {
     dispatch<16, 14, 12>(p.wbits, [&](auto c) {
       dispatch<8, 2, 1>(sw, [&](auto w) {
         constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
-        hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
-                           p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
+        if (p.sparse)
+          hipLaunchKernelGGL((k_count<C, SW, false, NB, SparseIdx>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec,
+                             p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
+        else
+          hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
+                             p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
       });
     });
   }
@@ -761,16 +787,25 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
                        (uint32_t)ctx->n_bases, p.chunks, p.chunk_len, d_chunk_len);
   } else if (bytes) {
     dispatch<1, 2>(p.nb, [&](auto b) {
-      hipLaunchKernelGGL(k_byte_scatter<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.stride, p.tile_len, p.tiles, p.w_count,
-                         ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len);
+      if (p.sparse)
+        hipLaunchKernelGGL((k_byte_scatter<decltype(b)::value, SparseIdx>), grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.stride, p.tile_len, p.tiles,
+                           p.w_count, ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len, sp);
+      else
+        hipLaunchKernelGGL(k_byte_scatter<decltype(b)::value>, grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.stride, p.tile_len, p.tiles, p.w_count,
+                           ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len);
     });
   } else {
     dispatch<16, 14, 12>(p.wbits, [&](auto c) {
       dispatch<8, 4, 2, 1>(sw, [&](auto w) {
         constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
-        hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
-                           p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
-                           merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
+        if (p.sparse)
+          hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB, SparseIdx>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
+                             p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                             merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len, sp);
+        else
+          hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
+                             p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                             merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
       });
     });
   }
@@ -1074,7 +1109,7 @@ int run_batch_groups(msm_hip_ctx* ctx, size_t n, size_t batch, uint8_t* out_xyz,
 
 extern "C" {
 
-int msm_hip_abi_version(void) { return 7; }  // 7 (round 5): curve-neutral names, virtual-window launches + pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits
+int msm_hip_abi_version(void) { return 7; }  // 7 (round 5): curve-neutral names, virtual-window launches + pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits; the sparse calls (msm_hip_run_sparse ...) arrived within 7
 
 const char* msm_hip_strerror(int code) {
   switch (code) {
@@ -1215,11 +1250,18 @@ int msm_hip_set_bases(msm_hip_ctx* ctx, const uint8_t* xy_host, size_t n, uint32
 }  // extern "C"
 
 namespace {
+// what a sparse entry point returns for a null context: NO_DEVICE when the process has no usable device (no context can exist), else INVALID_ARG
+int no_context_code() {
+  int count = 0;
+  return hipGetDeviceCount(&count) != hipSuccess || count <= 0 ? MSM_HIP_ERR_NO_DEVICE : MSM_HIP_ERR_INVALID_ARG;
+}
+
 // one launch into `slot` (the request as plan_launch takes it): plan, buffers, sort, reduce
 int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
-                void* window_sums_dev, LaunchMode mode = MODE_PLAIN, int v_begin = 0, int v_count = 0) {
+                void* window_sums_dev, LaunchMode mode = MODE_PLAIN, int v_begin = 0, int v_count = 0, bool sparse = false,
+                const uint32_t* indices = nullptr) {
   LaunchPlan p;
-  int rc = plan_launch(ctx, p, mode, scalars_dev, n, nvec, w_begin, w_end, wbits, slot, window_sums_dev, v_begin, v_count);
+  int rc = plan_launch(ctx, p, mode, scalars_dev, n, nvec, w_begin, w_end, wbits, slot, window_sums_dev, v_begin, v_count, sparse, indices);
   if (rc) return rc;
   ON_DEVICE(ctx);
   Slot& s = ctx->slot[slot];
@@ -1293,6 +1335,34 @@ int msm_hip_launch_windows_device(msm_hip_ctx* ctx, const void* scalars_dev, siz
 
 int msm_hip_launch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int slot) {
   return msm_hip_launch_windows_device(ctx, scalars_dev, n, 0, NWIN, slot, nullptr);
+}
+
+// Sparse: one whole MSM of nnz entries in the mode the resident bases and the scalar format call for, as msm_hip_launch_device picks it for nnz
+// points (not on wide tables).
+int msm_hip_launch_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot) {
+  if (!ctx) return no_context_code();
+  if (ctx->wide_bits) return MSM_HIP_ERR_INVALID_ARG;  // (out of scope: sparse launches over wide tables)
+  if (nnz == 0) return launch_impl(ctx, scalars_dev, 0, 1, 0, NWIN, WBITS, slot, nullptr, MODE_PLAIN, 0, 0, true, indices_dev);  // (identity)
+  if (const int nb = narrow_bytes(ctx->scalar_format)) {  // narrow scalars: the plain records idx_j, as the dense narrow path
+    const int wbits = byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, nnz, 1, false, nb);
+    return launch_impl(ctx, scalars_dev, nnz, 1, 0, narrow_windows(wbits, nb), wbits, slot, nullptr, MODE_NARROW, 0, 0, true, indices_dev);
+  }
+  if (ctx->precomputed) return launch_impl(ctx, scalars_dev, nnz, 1, 0, NWIN, WBITS, slot, nullptr, MODE_TABLES, 0, 0, true, indices_dev);
+  if (ctx->endo) {
+    const int wbits = pick_window_bits(ctx, nnz, 1, true);
+    return launch_impl(ctx, scalars_dev, nnz, 1, 0, nwin_of(wbits, true), wbits, slot, nullptr, MODE_HALVES, 0, 0, true, indices_dev);
+  }
+  const int wbits = pick_window_bits(ctx, nnz, 1);
+  return launch_impl(ctx, scalars_dev, nnz, 1, 0, nwin_of(wbits), wbits, slot, nullptr, MODE_PLAIN, 0, 0, true, indices_dev);
+}
+
+int msm_hip_run_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, uint8_t out_xyz[96]) {
+  if (ctx && !out_xyz) return MSM_HIP_ERR_INVALID_ARG;
+  if (ctx) ctx->sync_call = true;
+  const int rc = msm_hip_launch_sparse_device(ctx, indices_dev, scalars_dev, nnz, 0);
+  if (ctx) ctx->sync_call = false;
+  if (rc) return rc;
+  return msm_hip_finish(ctx, 0, out_xyz);
 }
 
 int msm_hip_slot_wait_stream(msm_hip_ctx* ctx, int slot, void* foreign_stream) {
@@ -1395,6 +1465,21 @@ int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n,
   return launch_impl(ctx, s.d_host_scalars, n, 1, w_begin, w_end, WBITS, slot, window_sums_dev);
 }
 
+// a sparse launch's host inputs -> slot `s`'s staging buffer, in one piece: the nnz scalars of `sbytes` bytes, then (256-byte aligned) the nnz
+// indices; returns the device address of the indices.  Ordered as stage_host_scalars.
+int stage_host_sparse(msm_hip_ctx* ctx, Slot& s, const uint32_t* indices_host, const void* scalars_host, size_t nnz, size_t sbytes, const uint32_t*& d_idx) {
+  const size_t off = (nnz * sbytes + 255) & ~(size_t)255, total = off + nnz * 4;
+  const int rc = grow(ctx, s.cap_host_scalars, (total + 31) / 32, false, [&](size_t c) { return dev_alloc(ctx, s.d_host_scalars, c * 8); });
+  if (rc) return rc;
+  uint8_t* base = reinterpret_cast<uint8_t*>(s.d_host_scalars);
+  HIP_TRY(ctx, hipMemcpyAsync(base, scalars_host, nnz * sbytes, hipMemcpyHostToDevice, ctx->copy_stream));
+  HIP_TRY(ctx, hipMemcpyAsync(base + off, indices_host, nnz * 4, hipMemcpyHostToDevice, ctx->copy_stream));
+  HIP_TRY(ctx, hipEventRecord(s.staged, ctx->copy_stream));
+  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
+  d_idx = reinterpret_cast<const uint32_t*>(base + off);
+  return MSM_HIP_OK;
+}
+
 // first point of part k of n points split into `parts` ranges (the first n % parts ranges take one more)
 inline size_t part_first(size_t n, int parts, int k) { return n / parts * k + std::min(n % parts, (size_t)k); }
 }  // namespace
@@ -1436,6 +1521,27 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
   ctx->sync_call = false;
   if (rc) return rc;
   return msm_hip_finish(ctx, 0, out_xyz);
+}
+
+// Host inputs of a sparse MSM: the indices are checked here, before anything is enqueued; one upload of both arrays into slot 0's staging buffer
+// and one launch (the part-splitting of msm_hip_run splits base ranges: not for sparse entries)
+int msm_hip_run_sparse(msm_hip_ctx* ctx, const uint32_t* indices_host, const uint8_t* scalars_host, size_t nnz, uint8_t out_xyz[96]) {
+  if (!ctx) return no_context_code();
+  if (!out_xyz || (nnz && (!indices_host || !scalars_host)) || nnz > MAX_POINTS || ctx->wide_bits) return MSM_HIP_ERR_INVALID_ARG;
+  if (nnz == 0) return msm_hip_run_sparse_device(ctx, nullptr, nullptr, 0, out_xyz);
+  if (ctx->n_bases == 0) return MSM_HIP_ERR_NO_BASES;
+  for (size_t j = 0; j < nnz; j++)
+    if (indices_host[j] >= ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  Slot& s = ctx->slot[0];
+  if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
+  ON_DEVICE(ctx);
+  int rc = setup_slot(ctx, s);
+  if (rc) return rc;
+  if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  const int nb = narrow_bytes(ctx->scalar_format);
+  const uint32_t* d_idx = nullptr;
+  if ((rc = stage_host_sparse(ctx, s, indices_host, scalars_host, nnz, nb ? (size_t)nb : 32, d_idx))) return rc;
+  return msm_hip_run_sparse_device(ctx, d_idx, s.d_host_scalars, nnz, out_xyz);
 }
 
 int msm_hip_run_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, size_t batch, uint8_t* out_xyz) {

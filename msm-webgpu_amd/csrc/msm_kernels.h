@@ -27,6 +27,19 @@
 
 #include <utility>
 
+#ifndef MSM_SPARSE_IDX
+#define MSM_SPARSE_IDX
+// Sparse launches (msm_hip_launch_sparse_device): entry j of the launch is the pair (scalar j, base idx[j]).  The recode and sort passes that
+// read scalars take it as ONE trailing argument -- a kernel's `Sparse...` pack holds SparseIdx or nothing, and the dense instantiations, with
+// nothing, keep their argument layout and code.  Only the record number an entry carries changes (the scatter passes: idx[j] where the dense
+// pass writes the position j); everything behind the scatter never sees positions.  Curve-neutral: no field constant enters the mapping.
+struct SparseIdx {
+  const uint32_t* idx;  // nnz base indices: any order, repeats allowed
+  uint32_t n_bases;     // points per base set; an entry whose index is not below it reads as a zero scalar and sets ERRBIT_BAD_INDEX
+  uint32_t* err;        // the slot's error word (for the count passes that have none of their own)
+};
+#endif
+
 namespace MSM_KERNEL_NS {
 using namespace MSM_FIELD_NS;
 
@@ -187,6 +200,7 @@ __device__ __forceinline__ g1_xyzz ld_xyzz(PTR p) {
 constexpr uint32_t ERRBIT_NONCANONICAL = 1u;
 constexpr uint32_t ERRBIT_NOT_ON_CURVE = 2u;
 constexpr uint32_t ERRBIT_SCALAR_CARRY = 4u;
+constexpr uint32_t ERRBIT_BAD_INDEX = 8u;  // a sparse launch's base index was not below the number of resident bases (SparseIdx)
 constexpr uint32_t INFOBIT_HUGE_BIN = 0x100u;  // not an error: the fine sort met a coarse bin beyond FINE_BIG (skewed scalars, or large n) -- the host's cue to run k_fine_hist
 
 // ------------------------------------------------------------------------------------------------ stage 0: bases
@@ -444,14 +458,20 @@ __global__ void __launch_bounds__(256) k_scalars_from_mont256(const uint32_t* __
 // `halves_out` (position p at word 4 p: the same 32 B the scalar took) for k_scatter_coarse<C, 4>; negbits[v][h][n / 128 rounded up]: bit j of
 // half h's array is the sign of half h of scalar j.
 // NB != 0 (narrow scalars, MSM_HIP_SCALARS_U8 .. U64): `scalars` holds nvec x n x NB packed bytes, `vec_stride` counts BYTES, SW = (NB + 3) / 4.
-template <int C, int SW, bool SPLIT = false, int NB = 0>
+// Sparse (a SparseIdx argument; one vector): scalar j whose index is out of range reads as zero, and the launch's error word gets ERRBIT_BAD_INDEX.
+__device__ __forceinline__ SparseIdx sparse_arg() { return SparseIdx{nullptr, 0u, nullptr}; }  // (a dense instantiation: never read)
+__device__ __forceinline__ SparseIdx sparse_arg(SparseIdx s) { return s; }
+template <int C, int SW, bool SPLIT = false, int NB = 0, typename... Sparse>
 __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
                                                int w_begin, int w_count, int nvec, size_t vec_stride,
                                                uint32_t* __restrict__ counts, uint16_t* __restrict__ planes, int plane_mode,
                                                uint64_t* __restrict__ negbits, uint32_t* __restrict__ halves_out,
-                                               uint32_t* __restrict__ err, size_t merge_nb) {
+                                               uint32_t* __restrict__ err, size_t merge_nb, Sparse... sparse) {
   static_assert(!SPLIT || SW == 4, "the split produces 4-word halves");
   static_assert(!SPLIT || NB == 0, "narrow scalars are never split");
+  constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  const SparseIdx sp = sparse_arg(sparse...);
+  uint32_t bad_idx = 0;
   // merge_nb != 0 (fixed-base tables, see k_precompute_tables): every window of vector v feeds ONE bucket set, local window v
   // grid (tiles, nvec): a workgroup counts one tile of ONE scalar vector (round 4: with the vectors looped over inside the workgroup a
   // grouped launch of small MSMs kept a quarter of the CUs busy -- 64 tiles at 2^16 -- for nvec times as long)
@@ -488,7 +508,11 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
         uint32_t k[8], h[2][4];
 #pragma unroll
         for (int q = 0; q < 8; q++) k[q] = 0;
-        if (valid) ld8(sv + j * 8, k);
+        bool live = valid;
+        if constexpr (SPARSE) {
+          if (valid && sp.idx[j] >= sp.n_bases) live = false, bad_idx = 1;  // (a zero scalar: zero halves, no entries)
+        }
+        if (live) ld8(sv + j * 8, k);
         // the input contract of the plain path: scalars that overflow the reference's 16-bit recode are rejected (test/utils.rs:150-152)
         uint64_t c = 0;
 #pragma unroll
@@ -522,6 +546,13 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
         if (i >= end) continue;
         uint32_t s[SW], tb[WinCfg<C, SW, NB>::WORDS];
         ld_narrow<NB>(nv, i, s);
+        if constexpr (SPARSE) {
+          if (sp.idx[i] >= sp.n_bases) {
+            bad_idx = 1;
+#pragma unroll
+            for (int k = 0; k < SW; k++) s[k] = 0;
+          }
+        }
         (void)bias_scalar<C, SW, NB>(s, tb);  // (every unsigned NB-byte value fits: no input is rejected)
         emit(v, i, tb, 0u);
       }
@@ -531,6 +562,14 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
         if (i >= end) continue;
         uint32_t s[SW], tb[WinCfg<C, SW>::WORDS], neg = 0;
         ld_scalar<SW>(sv + i * SW, s, neg);
+        if constexpr (SPARSE) {
+          if (sp.idx[i] >= sp.n_bases) {
+            bad_idx = 1;
+            neg = 0;
+#pragma unroll
+            for (int k = 0; k < SW; k++) s[k] = 0;
+          }
+        }
         bad |= bias_scalar<C, SW>(s, tb);
         if constexpr (C != 16 && SW == 8) {  // the same input contract for every window size: scalars that overflow the reference's
           uint32_t t16[8];                   // 16-bit recode ("final carry is 1", test/utils.rs:150-152) are rejected
@@ -541,6 +580,9 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
     }
   }
   if (bad) atomicOr(err, ERRBIT_SCALAR_CARRY);
+  if constexpr (SPARSE) {
+    if (bad_idx) atomicOr(err, ERRBIT_BAD_INDEX);
+  }
   __syncthreads();
   // counts[lw][tile][bin]
   for (int i = tid; i < le_n * NCOARSE; i += 256)
@@ -616,14 +658,19 @@ constexpr int SCAT_SUB = 2048;  // scalars staged per block iteration (8 per thr
 // 1290 -> 1148 us at 2^24.  (Tried and dropped: splitting the scalars again here instead of reading the halves the first pass wrote -- 1 GB less
 // traffic at 2^24, and 1522 us instead of 1148 with the first pass no faster: profiles/r05_sort.txt.)
 // NB != 0: narrow scalars (the layout of k_count<C, SW, false, NB>; vec_stride in bytes)
-template <int C, int SW, int NB = 0>
+// Sparse (a SparseIdx argument): input i carries base idx[i] (halves: idx[i / 2], + half_shift for k2) instead of its position, and an input
+// whose index is out of range reads as a zero scalar, as in k_count
+template <int C, int SW, int NB = 0, typename... Sparse>
 __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_coarse(const uint32_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len,
                                                         uint32_t tiles, int w_begin, int w_count, int nvec, size_t vec_stride,
                                                         const uint32_t* __restrict__ counts,
                                                         const uint32_t* __restrict__ bin_total, uint32_t* __restrict__ coarse_ptr,
                                                         uint32_t* __restrict__ tmp_val,
                                                         uint8_t* __restrict__ tmp_fine, size_t merge_nb, uint32_t half_n, uint32_t half_shift,
-                                                        uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev) {
+                                                        uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev,
+                                                        Sparse... sparse) {
+  constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  const SparseIdx sp = sparse_arg(sparse...);
   // scalars a thread holds (biased, in registers) per block iteration: 8 halves of 4 words, or 4 full scalars of 8 words -- 8 of those cost
   // 282 VGPRs + 26 AGPRs at 16 bits (one wave per SIMD) and a 304-byte scratch object at 12 bits (round 3)
   constexpr int PER = SW == 8 ? 4 : 8;
@@ -681,16 +728,23 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
     // this thread's PER biased scalars stay in registers; every window's digit code is read from them
     uint32_t sc[PER][Cfg::WORDS];
     uint32_t negs = 0;  // bit j: scalar j is a negative half (its digits' signs are flipped)
+    uint32_t rec[PER];  // sparse: the record input j feeds
 #pragma unroll
     for (int j = 0; j < PER; j++) {
       const size_t i = sub + (size_t)j * 256 + tid;
       uint32_t raw[SW], neg = 0;
 #pragma unroll
       for (int k = 0; k < SW; k++) raw[k] = 0;  // an all-zero scalar recodes to all-zero digits: no entries
+      bool live = i < tile_end;
+      if constexpr (SPARSE) {
+        const uint32_t x = live ? sp.idx[SW == 4 ? i >> 1 : i] : 0u;
+        live = live && x < sp.n_bases;
+        rec[j] = x + ((SW == 4 && (i & 1u)) ? half_shift : 0u);
+      }
       if constexpr (NB != 0) {
-        if (i < tile_end) ld_narrow<NB>(reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride, i, raw);
+        if (live) ld_narrow<NB>(reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride, i, raw);
       } else {
-        if (i < tile_end) ld_scalar<SW>(scalars + (size_t)v * vec_stride + i * SW, raw, neg);
+        if (live) ld_scalar<SW>(scalars + (size_t)v * vec_stride + i * SW, raw, neg);
       }
       negs |= neg << j;
       (void)bias_scalar<C, SW, NB>(raw, sc[j]);
@@ -722,7 +776,8 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
           const uint32_t slot = code & 0x7fffu, bin = slot >> 8;
           const uint32_t e = lstart[bin] + rank[j];
           uint32_t pos = (uint32_t)(sub + (size_t)j * 256 + tid);
-          if constexpr (SW == 4) pos = (pos >> 1) + ((pos & 1u) ? half_shift : 0u);
+          if constexpr (SPARSE) pos = rec[j];
+          else if constexpr (SW == 4) pos = (pos >> 1) + ((pos & 1u) ? half_shift : 0u);
           st_val[e] = (idx_base + pos) | (((code >> 15) ^ ((negs >> j) & 1u)) << 31);
           st_fine[e] = (uint8_t)(slot & 0xffu);
           st_dst[e] = gpos[lw * NCOARSE + bin] + rank[j];
@@ -759,9 +814,12 @@ __device__ __forceinline__ uint32_t ld_byte_scalar(const uint8_t* v, size_t i) {
   else return reinterpret_cast<const uint16_t*>(v)[i];
 }
 // counting pass: grid (tiles, nvec); a 256-bin LDS histogram per (tile, window).  scalars: nvec x n x NB bytes.
-template <int NB>
+// Sparse (a SparseIdx argument, as k_count): an entry whose index is out of range counts as a zero scalar and sets ERRBIT_BAD_INDEX in sp.err
+template <int NB, typename... Sparse>
 __global__ void __launch_bounds__(256) k_byte_count(const uint8_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
-                                                    uint32_t* __restrict__ counts) {
+                                                    uint32_t* __restrict__ counts, Sparse... sparse) {
+  constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  const SparseIdx sp = sparse_arg(sparse...);
   __shared__ uint32_t hist[NB * BYTE_BINS];
   const int tid = threadIdx.x, v = blockIdx.y;
 #pragma unroll
@@ -770,6 +828,12 @@ __global__ void __launch_bounds__(256) k_byte_count(const uint8_t* __restrict__ 
   const uint8_t* sv = scalars + (size_t)v * n * NB;
   const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
   for (size_t i = base + tid; i < end; i += 256) {
+    if constexpr (SPARSE) {
+      if (sp.idx[i] >= sp.n_bases) {
+        atomicOr(sp.err, ERRBIT_BAD_INDEX);
+        continue;
+      }
+    }
     const uint32_t s = ld_byte_scalar<NB>(sv, i);
 #pragma unroll
     for (int j = 0; j < NB; j++) {
@@ -804,11 +868,15 @@ __global__ void __launch_bounds__(256) k_byte_scan(uint32_t* __restrict__ counts
 // scatter pass: grid (tiles, nvec).  Every workgroup turns its windows' 256 bin totals into slot starts; workgroup (0, v) publishes col_ptr of
 // vector v's windows over the whole grid of `half` slots, workgroup (0, 0) the launch's SMVP chunk length (the fullest of its w_count windows).
 // Entries are placed with LDS cursors (order within a slot: unspecified, as everywhere).
-template <int NB>
+// Sparse (a SparseIdx argument): entry i carries base idx[i]; an out-of-range one is skipped, as k_byte_count skipped it.
+template <int NB, typename... Sparse>
 __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len, uint32_t tiles,
                                                       int w_count, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ bin_total,
                                                       uint32_t* __restrict__ col_ptr, uint32_t half, uint32_t* __restrict__ val_idxs,
-                                                      uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev) {
+                                                      uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev,
+                                                      Sparse... sparse) {
+  constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  const SparseIdx sp = sparse_arg(sparse...);
   __shared__ uint32_t cur[NB * BYTE_BINS];
   __shared__ uint32_t wave_tot[4];
   __shared__ uint32_t wtotal, max_total;
@@ -839,11 +907,16 @@ __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict_
   const uint8_t* sv = scalars + (size_t)v * n * NB;
   const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
   for (size_t i = base + tid; i < end; i += 256) {
+    uint32_t rec = (uint32_t)i;
+    if constexpr (SPARSE) {
+      rec = sp.idx[i];
+      if (rec >= sp.n_bases) continue;
+    }
     const uint32_t s = ld_byte_scalar<NB>(sv, i);
 #pragma unroll
     for (int j = 0; j < NB; j++) {
       const uint32_t b = (s >> (8 * j)) & 0xffu;
-      if (b) val_idxs[(size_t)(v * NB + j) * stride + atomicAdd(&cur[j * BYTE_BINS + b], 1u)] = (uint32_t)i;
+      if (b) val_idxs[(size_t)(v * NB + j) * stride + atomicAdd(&cur[j * BYTE_BINS + b], 1u)] = rec;
     }
   }
 }
