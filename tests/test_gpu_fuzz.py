@@ -54,3 +54,17 @@ def test_fuzz_upload_bound_calls_in_parts(built, capsys, monkeypatch, curve, cas
     finally:
         sys.argv = argv
     assert "fuzz ok: %d cases" % cases in capsys.readouterr().out
+
+
+@pytest.mark.parametrize("curve,cases", [("bn254", 30), ("bls12_381", 6), ("bn254_g2", 6)])
+def test_fuzz_narrow_and_sparse(built, capsys, monkeypatch, curve, cases):
+    """the opt-in modes: narrow scalars (random width, host / device, sync / slot / batch) and sparse MSMs (32-byte or narrow, nnz beyond n,
+    uniform / equal / sorted / cancelling indices), each at a random window width and base mode of the long-lived context"""
+    monkeypatch.setenv("FUZZ_MODES", "narrow,sparse")
+    argv = sys.argv
+    sys.argv = ["fuzz_gpu.py", str(cases), "20261016", curve]
+    try:
+        runpy.run_path(os.path.join(ROOT, "tools", "fuzz_gpu.py"), run_name="__main__")
+    finally:
+        sys.argv = argv
+    assert "fuzz ok: %d cases" % cases in capsys.readouterr().out

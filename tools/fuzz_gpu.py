@@ -1,6 +1,7 @@
 """Randomised differential test of the HIP engine against the CPU oracle: random sizes (tile / chunk / alignment edges),
 random scalar distributions (uniform, few distinct values, small values, zeros, equal), random window ranges.
-Usage: python tools/fuzz_gpu.py [cases] [seed] [bn254|grumpkin|pallas|vesta|bls12_381|bn254_g2|bls12_381_g2]   (test infrastructure: uses the oracle)"""
+Usage: python tools/fuzz_gpu.py [cases] [seed] [bn254|grumpkin|pallas|vesta|bls12_381|bn254_g2|bls12_381_g2]   (test infrastructure: uses the oracle)
+FUZZ_MODES=a,b,... restricts the soak to those modes; it also admits the opt-in modes "narrow" (U8 .. U64 scalars) and "sparse" (msm_sparse)."""
 import os, random, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -61,8 +62,13 @@ if curve == "bls12_381":
     MODES = [x for x in MODES if x not in ("mont", "endo", "endo_batch", "group_halves", "mgpu_batch_endo")]
 if curve.endswith("_g2"):  # (the "mont" case below writes G1 coordinates; the pool's points are multiples of G2's generator: the endomorphism modes are exact)
     MODES = [x for x in MODES if x != "mont"]
-if os.environ.get("FUZZ_MODES"):  # restrict the soak to some modes, e.g. FUZZ_MODES=wide,wide_batch
-    MODES = [x for x in MODES if x in os.environ["FUZZ_MODES"].split(",")]
+# opt-in modes, drawn only when FUZZ_MODES names them (in the default list they would change which cases a seed draws):
+# "narrow" -- U8 .. U64 scalars (the case's values cut to the width), "sparse" -- sum_j s_j P[idx_j] over the case's points
+OPT_IN = ["narrow", "sparse"]
+if os.environ.get("FUZZ_MODES"):  # restrict the soak to some modes, e.g. FUZZ_MODES=wide,wide_batch; or add opt-in ones, FUZZ_MODES=narrow,sparse
+    MODES = [x for x in MODES + OPT_IN if x in os.environ["FUZZ_MODES"].split(",")]
+# base modes of the opt-in cases (the endomorphism is not exact for the BLS12-381 G1 sampler's points, which lie outside the order-r subgroup)
+OPT_BASES = ["plain", "tables", "wide"] + ([] if curve == "bls12_381" else ["endo"])
 combine = lambda sums: m.MsmContext.combine_windows(sums, curve=curve)
 mg = {}  # lazily created msm_hip_mgpu handles by rank count (several contexts on this one GPU, pinned-buffer gather)
 R = ref.R
@@ -96,8 +102,9 @@ for case in range(cases):
         points = ref.points_to_bytes(pts)
         sc = [base[i % max(1, n // 5)] for i in range(n)]
     sb = ref.scalars_to_bytes(sc)
-    want = cpu.to_affine64(cpu.cpu_msm(points, sb))
     mode = rnd.choice(MODES)
+    if mode not in OPT_IN:  # (the opt-in modes compute their own)
+        want = cpu.to_affine64(cpu.cpu_msm(points, sb))
     # ("auto": the C ABI's flags = 0 -- the curve's fastest mode on a curve of prime order, the plain shape otherwise)
     wide_bits = 0
     if mode.startswith("wide"):  # every digit width the curve's scalar field admits (0: by the number of bases); BLS12-381 cannot hold 15 x 17 bits
@@ -106,7 +113,77 @@ for case in range(cases):
     ctx.set_bases(points, precompute="wide" if mode.startswith("wide") else mode.startswith("tables"), endomorphism=None if mode == "auto" else (mode.startswith("endo") or mode == "group_halves"))
     if mode.startswith("wide"):
         ctx.set_wide_bits(0)
-    if mode == "mont":
+    if mode in OPT_IN:
+        # a random base mode and window width on the long-lived context; 32-byte or narrow scalars (the case's values cut to 1 .. 8 bytes)
+        bm = rnd.choice(OPT_BASES if mode == "narrow" else [x for x in OPT_BASES if x != "wide"])  # (no sparse form over wide tables)
+        ctx.set_bases(points, precompute="wide" if bm == "wide" else bm == "tables", endomorphism=bm == "endo")
+        bits = rnd.choice([0, 12, 14, 16])
+        width = rnd.choice([1, 2, 4, 8]) if mode == "narrow" or rnd.random() < 0.5 else 32
+        vals = sc if width == 32 else [v & ((1 << (8 * width)) - 1) for v in sc]
+        wide_dtype = {1: torch.uint8, 2: torch.uint16, 4: torch.uint32, 8: torch.uint64}.get(width, torch.uint8)
+        enc = lambda vs: ref.scalars_to_bytes(vs) if width == 32 else b"".join(v.to_bytes(width, "little") for v in vs)
+        dev = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).cuda().view(wide_dtype)
+        ctx.set_window_bits(bits)
+        ctx.set_scalar_format(width=width)
+        try:
+            if mode == "narrow":
+                want = cpu.to_affine64(cpu.cpu_msm(points, ref.scalars_to_bytes(vals)))
+                vb = enc(vals)
+                how = rnd.choice(["host", "device", "slot", "batch"])
+                if how == "host":
+                    got = ctx.msm(vb)
+                elif how == "device":
+                    got = ctx.msm(dev(vb))
+                elif how == "slot":
+                    slot = rnd.randrange(4)
+                    if rnd.random() < 0.5:
+                        ctx.launch(dev(vb), slot=slot)
+                    else:
+                        ctx.launch_host(vb, slot=slot)
+                    got = ctx.finish(slot)
+                else:  # this case's vector at a random position of a batch of zero vectors and copies
+                    k = rnd.randrange(1, 9)
+                    pos = rnd.randrange(k)
+                    blob = b"".join(vb if j == pos or rnd.random() < 0.5 else bytes(len(vb)) for j in range(k))
+                    got = ctx.msm_batch(blob if rnd.random() < 0.5 else dev(blob), n)[pos]
+                if how != "batch" and width > 2 and bits:
+                    assert ctx.last_window_bits() == bits
+            else:
+                nnz = min(rnd.choice([1, 2, 255, 4096, 4097, n, 2 * n + 1, rnd.randrange(1, 3 * n + 2)]), 70000)
+                shape = rnd.choice(["uniform", "equal", "sorted", "pairs"])
+                idx = [rnd.randrange(n) for _ in range(nnz)]
+                if shape == "equal":
+                    idx = [idx[0]] * nnz
+                elif shape == "sorted":
+                    idx.sort()
+                s_j = [vals[j % n] for j in range(nnz)]
+                if shape == "pairs":  # entries 2k, 2k + 1 on one base: (s, r - s) cancel; narrow values cannot, they add up
+                    for j in range(0, nnz - 1, 2):
+                        idx[j + 1] = idx[j]
+                        if width == 32:
+                            s_j[j + 1] = (R - s_j[j]) % R
+                pb = len(points) // n
+                gathered = b"".join(points[pb * i:pb * i + pb] for i in idx)
+                want = cpu.to_affine64(cpu.cpu_msm(gathered, ref.scalars_to_bytes(s_j)))
+                vb = enc(s_j)
+                how = rnd.choice(["host", "device", "slot"])
+                if how == "host":
+                    got = ctx.msm_sparse(idx, vb)
+                else:
+                    di = torch.tensor(idx, dtype=rnd.choice([torch.int32, torch.int64]), device="cuda")
+                    if how == "device":
+                        got = ctx.msm_sparse(di, dev(vb))
+                    else:
+                        slot = rnd.randrange(4)
+                        ctx.launch_sparse(di, dev(vb), slot=slot)
+                        got = ctx.finish(slot)
+                if width > 2 and bits:
+                    assert ctx.last_window_bits() == (16 if width == 32 and bm == "tables" else bits)
+        finally:
+            ctx.set_scalar_format(width=32)
+            ctx.set_window_bits(0)
+        kind += "/%s/%s/w%d/b%d" % (mode, bm, width, bits)
+    elif mode == "mont":
         # both inputs as R = 2^256 Montgomery words (MSM_HIP_BASES_MONT256, MSM_HIP_SCALARS_MONT256)
         PM, RM = ref.P, ref.R
         pm = b"".join(((x << 256) % PM).to_bytes(32, "little") + ((y << 256) % PM).to_bytes(32, "little") for x, y in ref.bytes_to_points(points))
