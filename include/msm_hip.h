@@ -403,6 +403,10 @@ int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n);
  * bin (skewed 32-byte scalars arm it for 64 launches; narrow-scalar launches neither arm nor consume it).  Sparse launches follow the rule of
  * their scalar format: 32-byte ones arm and consume it as dense launches do, narrow ones leave it alone. */
 int msm_hip_test_skew_credit(const msm_hip_ctx* ctx);
+/* the environment settings (MSM_HIP_*) as the library resolved them, the part and upload-chunk counts of the last upload-bound call and, with a
+ * context, the shape of its last launch (window bits, planned SMVP chunk length, digit planes, bucket-reduce variant, inline reduce, k_fine_hist):
+ * "key=value\n" lines into `out`; returns their length, or MSM_HIP_ERR_INVALID_ARG when `cap` is too small.  Reads only; ctx may be null. */
+int msm_hip_test_env_report(const msm_hip_ctx* ctx, char* out, size_t cap);
 int msm_hip_read_digits(msm_hip_ctx* ctx, uint16_t* out, size_t cap_elems);
 int msm_hip_read_col_ptr(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems);
 int msm_hip_read_val_idxs(msm_hip_ctx* ctx, uint32_t* out, size_t cap_elems);

@@ -101,6 +101,7 @@ def lib():
         L.msm_hip_set_debug.argtypes = [vp, i]
         L.msm_hip_set_fine_hist_min_n.argtypes = [vp, sz]
         L.msm_hip_test_skew_credit.argtypes = [vp]
+        L.msm_hip_test_env_report.argtypes = [vp, C.c_char_p, sz]
         L.msm_hip_set_scalar_format.argtypes = [vp, C.c_uint32]
         L.msm_hip_set_stage_timing.argtypes = [vp, i]
         L.msm_hip_set_window_bits.argtypes = [vp, i]
@@ -658,6 +659,10 @@ class MsmContext:
         """launches left that run k_fine_hist because an earlier 32-byte launch met a huge coarse bin (test hook)"""
         return lib().msm_hip_test_skew_credit(self._h)
 
+    def env_report(self):
+        """test hook: env_report() plus the shape of this context's last launch (last_wbits, last_chunk_len, last_planes, last_logr, ...)"""
+        return env_report(self._h)
+
     def set_fine_hist_min_n(self, n):
         _check(lib().msm_hip_set_fine_hist_min_n(self._h, n), "msm_hip_set_fine_hist_min_n")
 
@@ -820,6 +825,15 @@ class MultiGpuMsm:
         finally:
             getattr(self, "_keep", {}).pop(slot, None)
         return [G1(out.raw[self.jb * k:self.jb * (k + 1)], self.modulus) for k in range(nvec)]
+
+
+def env_report(handle=None):
+    """test hook: the MSM_HIP_* settings as the library resolved them and the part / upload-chunk counts of the last upload-bound call
+    (msm_hip_test_env_report), as a dict of ints; `handle` (an MsmContext's) adds the shape of that context's last launch"""
+    buf = C.create_string_buffer(4096)
+    n = lib().msm_hip_test_env_report(handle, buf, len(buf))
+    _check(min(n, 0), "msm_hip_test_env_report")
+    return {k: int(v) for k, v in (line.split("=") for line in buf.raw[:n].decode().splitlines())}
 
 
 def window_range_abi(rank, world, num=NUM_WINDOWS):

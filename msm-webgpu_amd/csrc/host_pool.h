@@ -39,6 +39,17 @@ class CombinePool {
     total_ = 0;
     fn_ = nullptr;
   }
+  // helper threads (the caller not counted) the pool starts on first use; MSM_HIP_COMBINE_THREADS = total threads incl. the caller, 1 = serial
+  static int helpers_wanted() {
+    unsigned hw = std::thread::hardware_concurrency();
+    int nthreads = hw > 1 ? (int)(hw - 1 < 7 ? hw - 1 : 7) : 0;
+    if (const char* e = getenv("MSM_HIP_COMBINE_THREADS")) nthreads = atoi(e) - 1;
+    return nthreads;
+  }
+  int helpers_started() {  // (test hook: what the pool runs on)
+    std::lock_guard<std::mutex> lk(job_mu_);
+    return (int)threads_.size();
+  }
   ~CombinePool() {
     {
       std::lock_guard<std::mutex> lk(mu_);
@@ -51,9 +62,7 @@ class CombinePool {
  private:
   bool start() {  // under job_mu_
     if (!threads_.empty()) return true;
-    unsigned hw = std::thread::hardware_concurrency();
-    int nthreads = hw > 1 ? (int)(hw - 1 < 7 ? hw - 1 : 7) : 0;
-    if (const char* e = getenv("MSM_HIP_COMBINE_THREADS")) nthreads = atoi(e) - 1;  // total threads incl. the caller; 1 = serial
+    const int nthreads = helpers_wanted();
     if (nthreads <= 0) return false;
     try {
       for (int i = 0; i < nthreads; i++) threads_.emplace_back([this] { loop(); });

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -148,8 +149,15 @@ namespace {
 std::atomic<int> g_oneshot_parts{0};
 std::atomic<size_t> g_oneshot_parts_min_n{0};
 // `two_from`, `three_from`: log2 of the point counts from which the call shape runs 2 / 3 parts (measured: profiles/r05_oneshot.txt)
+inline int env_oneshot_parts() {
+  static const int v = [] { const char* e = getenv("MSM_HIP_ONESHOT_PARTS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? v : 0; }();
+  return v;
+}
+// what the last upload-bound call ran as (test hook msm_hip_test_env_report): its parts, and the most upload chunks of one part (the one-shot call's
+// overlapped upload; 0 for msm_hip_run)
+std::atomic<int> g_probe_upload_parts{0}, g_probe_upload_chunks{0};
 inline int upload_parts(size_t n, int cap, int two_from, int three_from) {
-  static const int env_parts = [] { const char* e = getenv("MSM_HIP_ONESHOT_PARTS"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? v : 0; }();
+  const int env_parts = env_oneshot_parts();
   const int hook = g_oneshot_parts.load();
   const size_t hook_n = g_oneshot_parts_min_n.load();
   int want = hook ? hook : env_parts;
@@ -216,6 +224,10 @@ struct msm_hip_ctx {
   Slot slot[NSLOT];
   LaunchPlan last;  // the last launch that enqueued kernels, and its slot (for the stage read-back hooks)
   int last_slot = 0;
+  int last_logr = 0;                // ... the LOG_R of its k_bpr_rowcol variant (pick_rowcol), and whether its stitch + reduce ran on the main stream
+  bool last_inline_reduce = false;  //     (test hook msm_hip_test_env_report)
+  bool last_fine_hist = false;      // ... and whether its sort ran k_fine_hist
+  bool sort_fine_hist = false;      // (the sort stage's, taken over by the reduce stage of the same launch)
   float stage_ms[10] = {};
 };
 
@@ -280,8 +292,12 @@ inline size_t num_cus() {
 // length that gives about SMVP_TARGET_LANES lanes (+- 25 %: the stitch's work follows the lane count) a length whose product is more than 1 % lower
 // than the plain quotient's replaces it (2^20 with 8 or 16 windows: 32, exact, instead of 29: 1.5 % per MSM).  (What the shares of an 8-rank run gained this round -- 3.5 % per MSM at 7 x 2 windows per launch -- came
 // from the quotient itself, 25, no longer being rounded up to a multiple of 4, 28.)  MSM_HIP_CHUNK_SEARCH=0: the plain quotient.
+inline bool chunk_search() {
+  static const bool v = [] { const char* e = getenv("MSM_HIP_CHUNK_SEARCH"); return !e || atoi(e) != 0; }();
+  return v;
+}
 inline uint32_t chunk_len_for(size_t n, int w_count) {
-  static const bool search = [] { const char* e = getenv("MSM_HIP_CHUNK_SEARCH"); return !e || atoi(e) != 0; }();
+  const bool search = chunk_search();
   size_t base = (n * (size_t)w_count + target_lanes() - 1) / target_lanes();
   if (base < (size_t)SMVP_CHUNK_MIN) base = SMVP_CHUNK_MIN;
   if (base > (size_t)SMVP_CHUNK_MAX) base = SMVP_CHUNK_MAX;
@@ -350,8 +366,12 @@ inline uint32_t wide_top_max(int curve, int bits) {
 // Round 5: with INTERLEAVED virtual windows (msm_kernels.h: wide_key) the narrow top digit spreads over the windows by itself and is used as it
 // is -- no shift.  (Round 4 shifted it by the largest amount that kept it within 2^(C-1), to spread it over contiguous magnitude ranges;
 // MSM_HIP_WIDE_TOP_SHIFT still forces a shift for A/B runs: the kernels and the tables' last step honour it.)
+inline int env_wide_top_shift() {  // tuning aid
+  static const int v = [] { const char* e = getenv("MSM_HIP_WIDE_TOP_SHIFT"); return e ? atoi(e) : -1; }();
+  return v;
+}
 inline int wide_top_shift(int curve, int bits) {
-  static const int forced = [] { const char* e = getenv("MSM_HIP_WIDE_TOP_SHIFT"); return e ? atoi(e) : -1; }();  // tuning aid
+  const int forced = env_wide_top_shift();
   if (forced < 0) return 0;
   const uint32_t dmax = wide_top_max(curve, bits), half = 1u << (bits - 1);
   int s = 0;
@@ -371,8 +391,12 @@ inline bool wide_bits_fit(int curve, int bits) { return wide_top_max(curve, bits
 // all that counts.  19 bits (14 additions, 8 bucket sets; the 7-bit top digit makes <= 128
 // giant buckets) lies between them at every size and serves the curve 17 bits cannot (BLS12-381); 18 bits (a 2-bit top digit: 3 giant buckets) loses everywhere.
 // msm_hip_set_wide_bits / MSM_HIP_WIDE_BITS = 16 .. 20 override.  -1: the chosen width cannot hold the curve's scalars.
+inline int env_wide_bits() {
+  static const int v = [] { const char* e = getenv("MSM_HIP_WIDE_BITS"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 20 ? v : 0; }();
+  return v;
+}
 inline int pick_wide_bits(const msm_hip_ctx* ctx, size_t n) {
-  static const int forced = [] { const char* e = getenv("MSM_HIP_WIDE_BITS"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 20 ? v : 0; }();
+  const int forced = env_wide_bits();
   const int asked = ctx->wide_bits_choice ? ctx->wide_bits_choice : forced;  // msm_hip_set_wide_bits, then the environment
   if (asked) return wide_bits_fit(ctx->curve, asked) ? asked : -1;
   const int bits = n <= ((size_t)1 << 16) ? 16 : n <= ((size_t)1 << 20) ? 17 : 20;
@@ -388,6 +412,10 @@ struct WideShape {
   size_t worst;
   uint32_t chunk_len, chunks, host_len;
 };
+inline double wide_slack() {  // tuning aid
+  static const double v = [] { const char* e = getenv("MSM_HIP_WIDE_SLACK_PCT"); return e ? atof(e) / 100.0 : 0.004; }();
+  return v;
+}
 inline WideShape wide_shape(size_t n, int curve, int bits, int lwin) {  // (lwin local windows share the lanes: nvec whole MSMs x VWIN, or nvec shares x their virtual windows)
   const int WIDE_TABLES = wide_tables_of(bits), WIDE_VWIN = wide_vwin_of(bits);
   WideShape w;
@@ -397,7 +425,7 @@ inline WideShape wide_shape(size_t n, int curve, int bits, int lwin) {  // (lwin
   // window only)
   const int shift = wide_top_shift(curve, bits);
   const int top_windows = WIDE_VWIN >> (shift < bits - WBITS ? shift : bits - WBITS);
-  static const double slack = [] { const char* e = getenv("MSM_HIP_WIDE_SLACK_PCT"); return e ? atof(e) / 100.0 : 0.004; }();  // tuning aid
+  const double slack = wide_slack();
   const double fullest = (double)n * (WIDE_TABLES - 1) / WIDE_VWIN + (double)n / (top_windows > 0 ? top_windows : 1);
   const size_t typ = (size_t)(fullest * (1.0 + slack)) + 64;
   w.chunk_len = chunk_len_for(typ, lwin);
@@ -524,8 +552,12 @@ int ensure_work(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
 // `nvec` whole MSMs must fit MAXLW local windows.  The window-sharding entry points always use 16-bit windows: their w_begin / w_end
 // index the reference's 16 windows.
 // (`nb`: narrow scalars of nb bytes -- the same choice, with their own window count)
+inline int env_window_bits() {  // tuning aid
+  static const int v = [] { const char* e = getenv("MSM_HIP_WINDOW_BITS"); return e ? atoi(e) : 0; }();
+  return v;
+}
 inline int pick_window_bits(const msm_hip_ctx* ctx, size_t n, int nvec, bool halves = false, int nb = 0) {
-  static const int forced = [] { const char* e = getenv("MSM_HIP_WINDOW_BITS"); return e ? atoi(e) : 0; }();  // tuning aid
+  const int forced = env_window_bits();
   int bits = ctx->window_bits ? ctx->window_bits : (forced == 12 || forced == 14 || forced == 16 ? forced : 0);
   if (!bits) bits = nvec > 1 ? (n <= ((size_t)1 << 16) ? 14 : 16) : (n <= ((size_t)1 << 12) ? 12 : 16);
   while (bits < 16 && nvec * (nb ? narrow_nwin_of(bits, nb) : nwin_of(bits, halves)) > MAXLW) bits += 2;
@@ -567,12 +599,25 @@ int err_from_bits(uint32_t bits) {
 // of 32 B per scalar, and no scalars held in registers.  Not for fixed-base tables (one bucket set per vector) and not while the debug
 // read-back wants the planes in its own format.  MSM_HIP_PLANES_MAX_W overrides the limit (0: never; tuning aid).  Never for sparse launches
 // (k_scatter_planes writes positions, not the entries' base indices), whatever the tuning aids say.
+inline int planes_max_w() {
+  static const int v = [] { const char* e = getenv("MSM_HIP_PLANES_MAX_W"); return e ? atoi(e) : 8; }();
+  return v;
+}
+inline bool planes_whole() {  // A/B aid: whole MSMs too
+  static const bool v = [] { const char* e = getenv("MSM_HIP_PLANES_WHOLE"); return e && e[0] == '1'; }();
+  return v;
+}
 inline bool use_planes(const msm_hip_ctx* ctx, LaunchMode mode, int w_count_vec, int wbits, bool sparse) {
-  static const int max_w = [] { const char* e = getenv("MSM_HIP_PLANES_MAX_W"); return e ? atoi(e) : 8; }();
-  static const bool whole = [] { const char* e = getenv("MSM_HIP_PLANES_WHOLE"); return e && e[0] == '1'; }();  // A/B aid: whole MSMs too
+  const int max_w = planes_max_w();
+  const bool whole = planes_whole();
   if (sparse || mode == MODE_TABLES || mode == MODE_WIDE || mode == MODE_NARROW || ctx->debug) return false;
   if (whole) return true;
   return w_count_vec <= max_w && w_count_vec < nwin_of(wbits, mode == MODE_HALVES);
+}
+
+inline bool wide_share_lists() {  // MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape of the wide tables' shares (A/B aid)
+  static const bool v = [] { const char* e = getenv("MSM_HIP_WIDE_SHARE_LISTS"); return !e || atoi(e) != 0; }();
+  return v;
 }
 
 constexpr size_t MAX_POINTS = (size_t)1 << 28;  // point indices carry the digit sign in bit 31; 2^28 keeps every per-window offset in u32
@@ -653,9 +698,8 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
   p.planes = use_planes(ctx, mode, w_count_vec, p.wbits, sparse);
   // shares of at most WIDE_SHARE_VWIN_MAX virtual windows of wide tables: the first pass leaves compact lists of the share's entries per sub-tile of
   // LIST_SUB scalars (k_count_wide_list / k_scatter_list); tiles are then whole sub-tiles.  MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape (A/B aid)
-  static const bool share_lists = [] { const char* e = getenv("MSM_HIP_WIDE_SHARE_LISTS"); return !e || atoi(e) != 0; }();
   p.share_shape = pairs && v_count <= WIDE_SHARE_VWIN_MAX;
-  p.list_path = p.share_shape && share_lists;
+  p.list_path = p.share_shape && wide_share_lists();
   // tiles of scalars for the two global sort passes: >= 2048 scalars each, at most MAX_TILES of them
   const uint32_t tile_unit = p.list_path ? (uint32_t)LIST_SUB : 256u;
   p.tile_len = 2048;
@@ -827,7 +871,8 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
     const uint32_t* part_hist = nullptr;
     const bool hist_useful = p.nb || ctx->fine_hist_min_n != FINE_BIG + 1 || p.n_entries / p.ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
     if (ctx->skew_credit > 0 && !p.nb) ctx->skew_credit--;
-    if (p.n_entries >= ctx->fine_hist_min_n && hist_useful) {
+    ctx->sort_fine_hist = p.n_entries >= ctx->fine_hist_min_n && hist_useful;
+    if (ctx->sort_fine_hist) {
       hipLaunchKernelGGL(k_fine_hist, dim3(p.ncoarse, p.w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, p.stride, ctx->d_coarse_ptr,
                          ctx->d_part_hist);
       AFTER_KERNEL(ctx, "k_fine_hist", st);
@@ -851,9 +896,14 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
 struct RowCol {
   void (*kernel)(const uint32_t*, uint32_t*, uint32_t*);
   int blocks;
+  int logr;  // LOG_R of the variant (test hook msm_hip_test_env_report)
 };
+inline int bpr_force_logr() {  // tuning aid
+  static const int v = [] { const char* e = getenv("MSM_HIP_BPR_LOGR"); return e ? atoi(e) : 0; }();
+  return v;
+}
 RowCol pick_rowcol(const msm_hip_ctx* ctx, const LaunchPlan& p, const Slot& s) {
-  static const int force_logr = [] { const char* e = getenv("MSM_HIP_BPR_LOGR"); return e ? atoi(e) : 0; }();  // tuning aid
+  const int force_logr = bpr_force_logr();
   const CurveOps* o = ctx->ops;
   if (p.wbits == 16) {
     // one small MSM alone in its launch (8 half-length windows, up to 2^18 points): 8 buckets per thread -- its latency is what counts
@@ -863,26 +913,33 @@ RowCol pick_rowcol(const msm_hip_ctx* ctx, const LaunchPlan& p, const Slot& s) {
     bool alone = p.nvec == 1 && p.w_count == 8;
     for (const Slot& q : ctx->slot) alone = alone && (&q == &s || !q.pending);
     const bool small_single = p.nvec == 1 && p.w_count == 8 && (p.n_entries <= ((size_t)1 << 19) || alone);
-    if (force_logr == 4 || (force_logr == 0 && p.w_count >= 8 && !small_single)) return {o->rowcol_4_8, bpr_rowcol_blocks<4, 8>()};
-    if (force_logr == 3 || (force_logr == 0 && small_single)) return {o->rowcol_3_8, bpr_rowcol_blocks<3, 8>()};
-    return {o->rowcol_2_8, bpr_rowcol_blocks<2, 8>()};
+    if (force_logr == 4 || (force_logr == 0 && p.w_count >= 8 && !small_single)) return {o->rowcol_4_8, bpr_rowcol_blocks<4, 8>(), 4};
+    if (force_logr == 3 || (force_logr == 0 && small_single)) return {o->rowcol_3_8, bpr_rowcol_blocks<3, 8>(), 3};
+    return {o->rowcol_2_8, bpr_rowcol_blocks<2, 8>(), 2};
   }
   if (p.wbits == 14) {  // 64 rows x 128 columns
-    if (force_logr == 4 || (force_logr == 0 && p.w_count > 2 * nwin_of(14))) return {o->rowcol_4_6, bpr_rowcol_blocks<4, 6>()};
-    return {o->rowcol_2_6, bpr_rowcol_blocks<2, 6>()};
+    if (force_logr == 4 || (force_logr == 0 && p.w_count > 2 * nwin_of(14))) return {o->rowcol_4_6, bpr_rowcol_blocks<4, 6>(), 4};
+    return {o->rowcol_2_6, bpr_rowcol_blocks<2, 6>(), 2};
   }
-  return {o->rowcol_2_4, bpr_rowcol_blocks<2, 4>()};  // 16 rows x 128 columns
+  return {o->rowcol_2_4, bpr_rowcol_blocks<2, 4>(), 2};  // 16 rows x 128 columns
 }
 
 // The launch's second stage: the SMVP (it reads the bases) on the main stream, then stitch + bucket reduce on the slot's reduce stream, few waves
 // of long dependent chains; the error word and, for the host, the window sums go to the slot's pinned buffer.  Returns without waiting.
+inline bool inline_reduce_on() {  // MSM_HIP_INLINE_REDUCE=0: the stitch and the bucket reduce always on the reduce stream
+  static const bool v = [] { const char* e = getenv("MSM_HIP_INLINE_REDUCE"); return !e || atoi(e) != 0; }();
+  return v;
+}
+inline unsigned smvp_lds_pad() {  // A/B aid: dynamic LDS added to the SMVP's workgroups
+  static const unsigned v = [] { const char* e = getenv("MSM_HIP_SMVP_LDS_PAD"); const long v = e ? atol(e) : 0; return v > 0 && v <= 65536 ? (unsigned)v : 0u; }();
+  return v;
+}
 int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   hipStream_t st = ctx->stream, rs = ctx->reduce_stream[(&s - ctx->slot) % NREDUCE];
   // a synchronous call with nothing else in flight (msm_hip_run_*: the caller waits for this launch before it issues another): the stitch and
   // the bucket reduce follow the SMVP on the MAIN stream -- no cross-stream hand-off (an event wait costs ~10 us more than an in-stream kernel
   // boundary), and no next launch exists whose sort the separate stream would let overlap.  MSM_HIP_INLINE_REDUCE=0: always the reduce stream.
-  static const bool inline_reduce = [] { const char* e = getenv("MSM_HIP_INLINE_REDUCE"); return !e || atoi(e) != 0; }();
-  if (inline_reduce && ctx->sync_call) {
+  if (inline_reduce_on() && ctx->sync_call) {
     bool others = false;
     for (const Slot& o : ctx->slot) others = others || (&o != &s && o.pending);
     if (!others) rs = st;
@@ -896,9 +953,8 @@ int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   // packet between two kernels costs a few microseconds of queue time, and these two sat between every launch's sort and its SMVP and
   // between the SMVP and the next launch (bench.py times every launch's SMVP for the roofline figure).  Level 2 keeps the packets: its
   // stage boundaries are read as differences of consecutive events.
-  static const unsigned smvp_lds_pad = [] { const char* e = getenv("MSM_HIP_SMVP_LDS_PAD"); const long v = e ? atol(e) : 0; return v > 0 && v <= 65536 ? (unsigned)v : 0u; }();
   HIP_TRY(ctx, tl >= 2 ? hipEventRecord(s.ev[4], st) : hipSuccess);
-  hipExtLaunchKernelGGL(ctx->ops->smvp_chunks, dim3((p.chunks + 255) / 256, p.w_count), dim3(256), smvp_lds_pad, st, tl == 1 ? s.ev[4] : nullptr,
+  hipExtLaunchKernelGGL(ctx->ops->smvp_chunks, dim3((p.chunks + 255) / 256, p.w_count), dim3(256), smvp_lds_pad(), st, tl == 1 ? s.ev[4] : nullptr,
                         tl == 1 ? s.ev[5] : nullptr, 0, (const uint32_t*)(ctx->d_bases + p.base_off * 2 * (size_t)ctx->ops->coord_words), (const uint32_t*)s.d_col_ptr,
                         (const uint32_t*)ctx->d_val, p.stride, p.chunks, (const uint32_t*)d_chunk_len, (const uint32_t*)ctx->d_chunk_slot, s.d_buckets, s.d_heads,
                         s.d_tails, p.half);
@@ -964,6 +1020,9 @@ int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   s.to_host = to_host;
   ctx->last = p;
   ctx->last_slot = (int)(&s - ctx->slot);
+  ctx->last_logr = rowcol.logr;
+  ctx->last_inline_reduce = rs == st;
+  ctx->last_fine_hist = ctx->sort_fine_hist;
   return MSM_HIP_OK;
 }
 
@@ -1003,8 +1062,16 @@ constexpr size_t MAX_PRECOMPUTE_POINTS = (size_t)1 << 24;  // 16 tables: 16 GiB,
 constexpr uint32_t BASE_FLAGS_ALL = MSM_HIP_CHECK_ON_CURVE | MSM_HIP_BASES_MONT256 | MSM_HIP_BASES_PRECOMPUTE | MSM_HIP_BASES_ENDOMORPHISM | MSM_HIP_BASES_PLAIN |
                                     MSM_HIP_BASES_PRECOMPUTE_WIDE;
 constexpr size_t MAX_WIDE_POINTS = (size_t)1 << 24;  // 13 tables of 20-bit digits: 13 GiB; sort arrays of 16 x 13 n entries: 31 GiB
+inline bool reduce_priority_on() {  // MSM_HIP_REDUCE_PRIORITY=0: plain reduce streams (msm_hip_ctx_create_curve)
+  static const bool v = [] { const char* e = getenv("MSM_HIP_REDUCE_PRIORITY"); return !e || atoi(e) != 0; }();
+  return v;
+}
+inline bool bases_auto() {  // MSM_HIP_BASES_AUTO=0: flags = 0 means plain (rounds 1 - 3)
+  static const bool v = [] { const char* e = getenv("MSM_HIP_BASES_AUTO"); return !e || atoi(e) != 0; }();
+  return v;
+}
 inline uint32_t resolve_base_flags(const msm_hip_ctx* ctx, size_t n, uint32_t flags) {
-  static const bool auto_endo = [] { const char* e = getenv("MSM_HIP_BASES_AUTO"); return !e || atoi(e) != 0; }();  // MSM_HIP_BASES_AUTO=0: flags = 0 means plain (rounds 1 - 3)
+  const bool auto_endo = bases_auto();
   if (flags & (MSM_HIP_BASES_PRECOMPUTE | MSM_HIP_BASES_PRECOMPUTE_WIDE | MSM_HIP_BASES_ENDOMORPHISM | MSM_HIP_BASES_PLAIN)) return flags;
   // ... on the curves of prime order only: phi(P) = lambda P holds on the subgroup of order r, and a base set of a curve with a cofactor
   // (BLS12-381, the G2 twists) may hold points outside it, for which the plain MSM is still defined -- there the mode stays an opt-in
@@ -1164,7 +1231,7 @@ int msm_hip_ctx_create_curve(msm_hip_ctx** out, int device_id, int curve) {
   // next launch's sort (latency-bound kernels that leave the multiplier idle) instead of trailing into its SMVP, which they slow down
   // (2^20, one GPU, five same-box pairs: 1.4025 vs 1.4231 ms per MSM, SMVP 0.976 vs 0.989 ms; a rank's window shares and 2^16: within the
   // noise; the opposite assignment -- main stream high, reduce low -- costs 3 %).  MSM_HIP_REDUCE_PRIORITY=0: plain streams.
-  static const bool reduce_high = [] { const char* e = getenv("MSM_HIP_REDUCE_PRIORITY"); return !e || atoi(e) != 0; }();
+  const bool reduce_high = reduce_priority_on();
   int prio_least = 0, prio_greatest = 0;
   if (reduce_high && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) prio_greatest = prio_least = 0;
   for (int k = 0; k < NREDUCE; k++) {
@@ -1499,6 +1566,8 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
   int parts = ctx->precomputed || ctx->wide_bits || narrow_bytes(ctx->scalar_format) || !scalars_host ? 1 : upload_parts(n, NSLOT, 20, 22);  // (2^20: 2.44 -> 2.38 ms, 2^22: 8.61 -> 6.91; 2^19: slower)
   for (int k = 0; k < parts; k++)
     if (ctx->slot[k].pending) parts = 1;  // the caller has launches of its own in flight: the plain path (which reports a busy slot 0)
+  g_probe_upload_parts.store(parts > 1 && n <= ctx->n_bases ? parts : 1);
+  g_probe_upload_chunks.store(0);
   if (parts > 1 && n <= ctx->n_bases) {
     uint8_t sums[NSLOT * MAX_JB];
     int rc = MSM_HIP_OK, launched = 0;
@@ -1650,6 +1719,18 @@ inline bool oneshot_keep() {
   static const bool v = [] { const char* e = getenv("MSM_HIP_ONESHOT_KEEP"); return !(e && e[0] == '0'); }();
   return v;
 }
+inline bool oneshot_overlap() {
+  static const bool v = [] { const char* e = getenv("MSM_HIP_ONESHOT_OVERLAP"); return !e || atoi(e) != 0; }();
+  return v;
+}
+inline size_t oneshot_chunk() {  // points per upload chunk of the overlapped one-shot call (MSM_HIP_ONESHOT_CHUNK_LOG: tuning aid)
+  static const size_t v = [] {
+    const char* e = getenv("MSM_HIP_ONESHOT_CHUNK_LOG");
+    const int l = e ? atoi(e) : 18;
+    return (size_t)1 << (l >= 10 && l <= 28 ? l : 18);
+  }();
+  return v;
+}
 }  // namespace
 
 }  // extern "C"
@@ -1698,11 +1779,7 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
   // 2. the points behind the scalars on the copy stream, in a few chunks (2^18 points = 16 MiB: smaller ones cost the pageable copy path more
   //    than they hide, profiles/r05_oneshot.txt); every chunk is converted on ANOTHER stream (the second reduce stream, idle in this call shape)
   //    as soon as it has landed, so the copies follow each other without waiting for kernels
-  static const size_t chunk = [] {  // points per chunk (MSM_HIP_ONESHOT_CHUNK_LOG: tuning aid)
-    const char* e = getenv("MSM_HIP_ONESHOT_CHUNK_LOG");
-    const int l = e ? atoi(e) : 18;
-    return (size_t)1 << (l >= 10 && l <= 28 ? l : 18);
-  }();
+  const size_t chunk = oneshot_chunk();
   hipStream_t conv = ctx->reduce_stream[NREDUCE - 1];
   hipError_t he = hipSuccess;
   int k = 0;
@@ -1718,6 +1795,7 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
     if (endo) hipLaunchKernelGGL(ctx->ops->endo_points, dim3(blocks_for(count, 256)), dim3(256), 0, conv, ctx->d_bases, n, first, count);
     he = hipGetLastError();
   }
+  if (k > g_probe_upload_chunks.load()) g_probe_upload_chunks.store(k);
   if (he == hipSuccess) he = hipEventRecord(ctx->bases_ready, conv);
   if (he == hipSuccess) he = hipStreamWaitEvent(ctx->stream, ctx->bases_ready, 0);
   // 3. the rest of the launch (on failure above too: the sort left the slot's streams mid-launch -- the bases it then reads are whatever arrived,
@@ -1760,7 +1838,7 @@ int msm_hip_msm_curve(int curve, const uint8_t* xy_host, const uint8_t* scalars_
   if (!out_xyz || ((!xy_host || !scalars_host) && n)) return MSM_HIP_ERR_INVALID_ARG;
   const bool keep = oneshot_keep() && dev >= 0 && dev < ONESHOT_MAX_DEVICES;
   std::lock_guard<std::mutex> lock(g_oneshot_mutex);  // (also without `keep`: the part policy below is process-wide state)
-  static const bool overlap = [] { const char* e = getenv("MSM_HIP_ONESHOT_OVERLAP"); return !e || atoi(e) != 0; }();
+  const bool overlap = oneshot_overlap();
   // Parts (round 5): a large one-shot MSM is upload-bound -- 96 n bytes over the host link against ~1 ms of SMVP at 2^20 --, and the SMVP cannot start
   // before the last point has arrived.  Sum over the points is sum over RANGES of the points: the call runs as `parts` sub-MSMs, each on a context
   // of its own, their uploads queued one behind the other on one copy stream, so that part k accumulates its buckets while part k + 1 is still
@@ -1768,6 +1846,8 @@ int msm_hip_msm_curve(int curve, const uint8_t* xy_host, const uint8_t* scalars_
   // 2 parts from 2^19 points on (MSM_HIP_ONESHOT_PARTS: tuning aid; more parts pay more per-part sorting, stitching and bucket reducing).
   const bool overlapped = overlap && n > 0 && n <= MAX_POINTS / 2;
   const int parts = overlapped ? upload_parts(n, ONESHOT_MAX_PARTS, 19, 30) : 1;  // (2^19: 2.00 -> 1.93 ms, 2^20: 3.55 -> 3.08, 2^22: 13.2 -> 11.1; three parts never better)
+  g_probe_upload_parts.store(parts);
+  g_probe_upload_chunks.store(0);  // (oneshot_enqueue: the most chunks of one part)
   msm_hip_ctx* ctxs[ONESHOT_MAX_PARTS] = {};
   int rc = MSM_HIP_OK;
   for (int k = 0; k < parts && !rc; k++) {
@@ -1941,6 +2021,57 @@ int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n) {
 }
 
 int msm_hip_test_skew_credit(const msm_hip_ctx* ctx) { return ctx ? ctx->skew_credit : MSM_HIP_ERR_INVALID_ARG; }
+
+int msm_hip_test_env_report(const msm_hip_ctx* ctx, char* out, size_t cap) {
+  if (!out || !cap) return MSM_HIP_ERR_INVALID_ARG;
+  size_t len = 0;
+  bool fits = true;
+  auto put = [&](const char* key, long long v) {
+    const int w = snprintf(out + len, cap - len, "%s=%lld\n", key, v);
+    if (w < 0 || (size_t)w >= cap - len) fits = false;
+    else len += (size_t)w;
+  };
+  // the settings as the library resolved them (read once per process)
+  put("target_lanes", (long long)target_lanes());
+  put("chunk_search", chunk_search());
+  put("window_bits", env_window_bits());
+  put("bpr_logr", bpr_force_logr());
+  put("planes_max_w", planes_max_w());
+  put("planes_whole", planes_whole());
+  put("inline_reduce", inline_reduce_on());
+  put("reduce_priority", reduce_priority_on());
+  put("smvp_lds_pad", smvp_lds_pad());
+  put("bases_auto", bases_auto());
+  put("debug_sync", debug_sync());
+  put("wide_bits", env_wide_bits());
+  put("wide_top_shift", env_wide_top_shift());
+  put("wide_slack_ppm", llround(wide_slack() * 1e6));
+  put("wide_share_lists", wide_share_lists());
+  put("oneshot_parts", env_oneshot_parts());
+  put("oneshot_keep", oneshot_keep());
+  put("oneshot_overlap", oneshot_overlap());
+  put("oneshot_chunk", (long long)oneshot_chunk());
+  put("combine_helpers", CombinePool::helpers_wanted());
+  put("combine_started", combine_pool().helpers_started());
+  // the last upload-bound call (msm_hip_msm_curve, msm_hip_run): its parts and the most upload chunks of one part
+  put("upload_parts", g_probe_upload_parts.load());
+  put("upload_chunks", g_probe_upload_chunks.load());
+  if (ctx) {  // the context's last launch
+    put("fine_hist_min_n", (long long)ctx->fine_hist_min_n);
+    put("last_wbits", ctx->last.wbits);
+    put("last_chunk_len", ctx->last.chunk_len);
+    put("last_chunks", ctx->last.chunks);
+    put("last_planes", ctx->last.planes);
+    put("last_list_path", ctx->last.list_path);
+    put("last_mode", ctx->last.mode);
+    put("last_w_count", ctx->last.w_count);
+    put("last_wide_top_shift", ctx->last.mode == MODE_WIDE ? wide_top_shift(ctx->curve, ctx->last.wide_bits) : 0);
+    put("last_logr", ctx->last_logr);
+    put("last_inline_reduce", ctx->last_inline_reduce);
+    put("last_fine_hist", ctx->last_fine_hist);
+  }
+  return fits ? (int)len : MSM_HIP_ERR_INVALID_ARG;
+}
 
 int msm_hip_set_debug(msm_hip_ctx* ctx, int keep_digit_planes) {
   if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
