@@ -9,7 +9,8 @@
  * signatures above (INTEGRATION.md shows the shim).  Wire formats are exactly what the reference's own helpers emit:
  *
  *     points  : n x 64 B, x || y, each coordinate the canonical (non-Montgomery) integer in [0, p), little-endian
- *               = points_to_bytes()   src/lib.rs:55-65  (the point at infinity is not representable, lib.rs:58 panics)
+ *               = points_to_bytes()   src/lib.rs:55-65  (the point at infinity is not representable, lib.rs:58 panics; a base set
+ *               set with MSM_HIP_BASES_ZERO_IS_IDENTITY takes it as x = y = 0, the form arkworks, halo2curves and blst store it in)
  *     scalars : n x 32 B, canonical integer in [0, r), little-endian
  *               = scalars_to_bytes()  src/lib.rs:50-52, field_to_bytes src/cuzk/utils.rs:10-14
  *     result  : 96 B Jacobian x || y || z, canonical little-endian, z = 0 <=> identity
@@ -90,6 +91,22 @@ extern "C" {
                                           2^27 points), else the plain shape (on a curve with a cofactor -- BLS12-381, the G2 twists -- the mode
                                           needs bases of order r and therefore stays an explicit choice).
                                           Same group element either way; what the flag decides is memory (n or 2n records) and speed. */
+
+#define MSM_HIP_BASES_ZERO_IS_IDENTITY 128u /* a record whose coordinate bytes are all zero is the point at infinity (x = y = 0: the affine identity of
+                                          arkworks, halo2curves and blst; Groth16 proving keys hold it wherever a variable's A or B polynomial is zero).
+                                          (0, 0) is on none of the curves (b != 0), so no point is read differently; the rule is the same for canonical and
+                                          MSM_HIP_BASES_MONT256 coordinates (64 B of zeros on the 254 / 255-bit G1 curves, 96 B on BLS12-381 G1, 128 / 192 B on
+                                          the G2 groups).  Every other record is checked as without the flag (MSM_HIP_ERR_NONCANONICAL, with
+                                          MSM_HIP_CHECK_ON_CURVE also MSM_HIP_ERR_NOT_ON_CURVE); an identity record passes MSM_HIP_CHECK_ON_CURVE.
+                                          Result: sum of s_i P_i over the bases that are not the identity.  A scalar paired with an identity base is IGNORED:
+                                          result and return code are those of the same call with that scalar set to zero, in every scalar format -- a scalar
+                                          that would be rejected elsewhere (2^256 - 1 in canonical form, say) is not rejected there.  Sparse calls: the base
+                                          at indices[j].  Composes with every mode (plain, endomorphism, 16-bit and wide tables), every scalar format and every
+                                          entry point of a context and of msm_hip_mgpu_*; it does not take part in the choice of mode (flags = 128 resolves as
+                                          flags = 0 does).  Cost: the scalars of every launch over a base set that holds an identity are copied once with
+                                          those of the identities zeroed (one read and write of the scalars); a flagged set without one runs as an unflagged
+                                          set.  Not for the one-shot calls (msm_hip_msm_curve, msm_hip_msm_bn254_g1): they take no flags.  No compressed points
+                                          and no subgroup checks.  (Added within ABI version 7.) */
 
 typedef struct msm_hip_ctx msm_hip_ctx;
 
@@ -309,6 +326,7 @@ int msm_hip_mgpu_create_curve(msm_hip_mgpu** out, const int* device_ids, int n_d
 void msm_hip_mgpu_destroy(msm_hip_mgpu* m);
 int msm_hip_mgpu_device_count(const msm_hip_mgpu* m);
 int msm_hip_mgpu_uses_rccl(const msm_hip_mgpu* m);
+/* (flags: as msm_hip_set_bases; MSM_HIP_BASES_ZERO_IS_IDENTITY passes through to every device's context) */
 int msm_hip_mgpu_set_bases(msm_hip_mgpu* m, const uint8_t* xy_host, size_t n, uint32_t flags);
 int msm_hip_mgpu_run(msm_hip_mgpu* m, const uint8_t* scalars_host, size_t n, uint8_t out_xyz[96]);
 /* The throughput form of the same (what a Rust caller that holds many (points, scalars) jobs drives, src/lib.rs:76-82; the reference creates
@@ -404,7 +422,8 @@ int msm_hip_set_fine_hist_min_n(msm_hip_ctx* ctx, size_t n);
  * their scalar format: 32-byte ones arm and consume it as dense launches do, narrow ones leave it alone. */
 int msm_hip_test_skew_credit(const msm_hip_ctx* ctx);
 /* the environment settings (MSM_HIP_*) as the library resolved them, the part and upload-chunk counts of the last upload-bound call and, with a
- * context, the shape of its last launch (window bits, planned SMVP chunk length, digit planes, bucket-reduce variant, inline reduce, k_fine_hist):
+ * context, the shape of its last launch (window bits, planned SMVP chunk length, digit planes, bucket-reduce variant, inline reduce, k_fine_hist,
+ * last_identity_mask: 1 when its scalars were masked for identity bases):
  * "key=value\n" lines into `out`; returns their length, or MSM_HIP_ERR_INVALID_ARG when `cap` is too small.  Reads only; ctx may be null. */
 int msm_hip_test_env_report(const msm_hip_ctx* ctx, char* out, size_t cap);
 int msm_hip_read_digits(msm_hip_ctx* ctx, uint16_t* out, size_t cap_elems);
@@ -436,7 +455,8 @@ int msm_hip_test_oneshot_parts(int parts, size_t min_points);
 const char* msm_hip_strerror(int code);
 int msm_hip_last_hip_error(msm_hip_ctx* ctx);
 /* ABI version; bumped on any signature change or addition (7 = round 5: curve-neutral names with the `_bn254` aliases kept, the virtual-window
- * launches and their pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits; the three sparse calls arrived within version 7) */
+ * launches and their pair combine, msm_hip_msm_curve, msm_hip_mgpu_set_wide_bits; the three sparse calls and MSM_HIP_BASES_ZERO_IS_IDENTITY arrived
+ * within version 7) */
 int msm_hip_abi_version(void);
 
 /* ---- aliases: the names of rounds 1 - 4 (the reference instantiates its generic functions with halo2curves::bn256 only, src/lib.rs:91,154). Each is

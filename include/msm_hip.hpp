@@ -72,11 +72,15 @@ inline std::vector<uint8_t> scalars_to_bytes(const std::vector<Fr>& v) {
   return out;
 }
 
-/// Convert points to bytes as [x0, y0, x1, y1, ...] (src/lib.rs:55-65); the point at infinity has no coordinates
-inline std::vector<uint8_t> points_to_bytes(const std::vector<G1Affine>& g) {
+/// Convert points to bytes as [x0, y0, x1, y1, ...] (src/lib.rs:55-65); the point at infinity has no coordinates -- unless `flags` include
+/// MSM_HIP_BASES_ZERO_IS_IDENTITY, under which it is written as 64 zero bytes (x = y = 0)
+inline std::vector<uint8_t> points_to_bytes(const std::vector<G1Affine>& g, uint32_t flags = 0) {
   std::vector<uint8_t> out(g.size() * 64);
   for (size_t i = 0; i < g.size(); i++) {
-    if (g[i].infinity) throw std::invalid_argument("points_to_bytes: point at infinity has no coordinates (src/lib.rs:58)");
+    if (g[i].infinity) {
+      if (!(flags & MSM_HIP_BASES_ZERO_IS_IDENTITY)) throw std::invalid_argument("points_to_bytes: point at infinity has no coordinates (src/lib.rs:58)");
+      continue;  // (out is zero-initialised)
+    }
     std::memcpy(out.data() + 64 * i, g[i].x.data(), 32);
     std::memcpy(out.data() + 64 * i + 32, g[i].y.data(), 32);
   }
@@ -92,8 +96,9 @@ class MsmContext {
   MsmContext& operator=(const MsmContext&) = delete;
 
   void set_bases(const std::vector<G1Affine>& g, bool check_on_curve = false, uint32_t more_flags = 0) {
-    // more_flags: MSM_HIP_BASES_ENDOMORPHISM (half-length scalars, 2 x the base memory) or MSM_HIP_BASES_PRECOMPUTE (fixed-base tables)
-    const std::vector<uint8_t> b = points_to_bytes(g);
+    // more_flags: MSM_HIP_BASES_ENDOMORPHISM (half-length scalars, 2 x the base memory) or MSM_HIP_BASES_PRECOMPUTE (fixed-base tables);
+    // MSM_HIP_BASES_ZERO_IS_IDENTITY: points at infinity are passed as (0, 0), and their scalars are ignored
+    const std::vector<uint8_t> b = points_to_bytes(g, more_flags);
     check(msm_hip_set_bases(ctx_, b.data(), g.size(), (check_on_curve ? MSM_HIP_CHECK_ON_CURVE : 0u) | more_flags), "msm_hip_set_bases");
   }
   /// Raw forms for callers whose field elements already sit in memory as bytes: `flags` as in msm_hip_set_bases
@@ -184,7 +189,7 @@ class MultiGpuMsm {
   MultiGpuMsm& operator=(const MultiGpuMsm&) = delete;
 
   void set_bases(const std::vector<G1Affine>& g, uint32_t flags = 0) {  // replicated on every device
-    const std::vector<uint8_t> b = points_to_bytes(g);
+    const std::vector<uint8_t> b = points_to_bytes(g, flags);
     check(msm_hip_mgpu_set_bases(m_, b.data(), g.size(), flags), "msm_hip_mgpu_set_bases");
   }
   int group_size() const { return msm_hip_mgpu_group_size(m_); }

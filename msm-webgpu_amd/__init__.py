@@ -7,6 +7,7 @@ libmsm_hip.so (hand-written HIP for gfx950); there is no CPU fallback -- using t
 built library, or without a GPU, raises.
 """
 from .api import (  # noqa: F401
+    BASES_ZERO_IS_IDENTITY,
     G1,
     MsmContext,
     MsmHipError,
@@ -22,4 +23,4 @@ from .api import (  # noqa: F401
 from .build import build  # noqa: F401
 
 __all__ = ["G1", "MsmContext", "MultiGpuMsm", "MsmHipError", "compute_msm", "run_webgpu_msm", "points_to_bytes", "scalars_to_bytes",
-           "sample_points", "sample_scalars", "build", "lib"]
+           "sample_points", "sample_scalars", "build", "lib", "BASES_ZERO_IS_IDENTITY"]

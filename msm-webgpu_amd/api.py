@@ -147,12 +147,20 @@ def _check(code, where):
 
 
 # ------------------------------------------------------------------------------------------------ wire format
-def points_to_bytes(points):
+# MSM_HIP_BASES_ZERO_IS_IDENTITY (include/msm_hip.h): an all-zero base record is the point at infinity
+BASES_ZERO_IS_IDENTITY = 128
+
+
+def points_to_bytes(points, zero_is_identity=False):
     """[(x, y), ...] canonical integers -> n x 64 B, x || y little-endian (src/lib.rs:55-65).
-    The point at infinity (None) is not representable: the reference panics at lib.rs:58, this raises."""
+    The point at infinity (None) is not representable: the reference panics at lib.rs:58, this raises -- unless zero_is_identity, which
+    writes it as 64 zero bytes (x = y = 0, for a base set set with zero_is_identity=True)."""
     out = bytearray()
     for pt in points:
         if pt is None:
+            if zero_is_identity:
+                out += bytes(64)
+                continue
             raise ValueError("point at infinity has no coordinates (src/lib.rs:58)")
         x, y = pt
         if not (0 <= x < P and 0 <= y < P):
@@ -323,7 +331,7 @@ class MsmContext:
             pass
 
     # -- bases
-    def set_bases(self, points, check_on_curve=False, mont256=False, precompute=False, endomorphism=False):
+    def set_bases(self, points, check_on_curve=False, mont256=False, precompute=False, endomorphism=False, zero_is_identity=False):
         """points: bytes (host, n x 64 B wire format) or a CUDA uint8 tensor holding the same bytes.
         mont256: the coordinates are x * 2^256 mod p (4 x 64-bit Montgomery limbs, R = 2^256) instead of canonical integers.
         precompute: fixed-base tables 2^(16 w) P_i (16 x the memory): whole MSMs then use one bucket set for all windows.  "wide":
@@ -332,8 +340,11 @@ class MsmContext:
         endomorphism: True: also store phi(P_i) (2 x the memory): whole MSMs split every scalar into two 127-bit halves and need
         half the windows.  False (this wrapper's default: the stage-level parity tests read the reference's 16-window shape):
         MSM_HIP_BASES_PLAIN.  None: the C ABI's own default (flags = 0) -- the fastest mode the curve has, which is what the
-        reference-shaped calls (compute_msm / run_webgpu_msm below, msm_hip_msm_bn254_g1) use."""
+        reference-shaped calls (compute_msm / run_webgpu_msm below, msm_hip_msm_bn254_g1) use.
+        zero_is_identity: MSM_HIP_BASES_ZERO_IS_IDENTITY -- an all-zero record is the point at infinity, and the scalars paired with it are
+        ignored (points_to_bytes(..., zero_is_identity=True) writes None that way)."""
         flags = (1 if check_on_curve else 0) | (2 if mont256 else 0) | (32 if precompute == "wide" else 4 if precompute else 0) | (8 if endomorphism else 0)
+        flags |= BASES_ZERO_IS_IDENTITY if zero_is_identity else 0
         if endomorphism is False and not precompute:
             flags |= 16
         if isinstance(points, torch.Tensor) and points.is_cuda:
@@ -753,14 +764,15 @@ class MultiGpuMsm:
     def uses_rccl(self):
         return lib().msm_hip_mgpu_uses_rccl(self._h) == 1
 
-    def set_bases(self, points, check_on_curve=False, endomorphism=False, precompute=False):
+    def set_bases(self, points, check_on_curve=False, endomorphism=False, precompute=False, zero_is_identity=False):
         """Replicated on every device.  endomorphism: True: MSM_HIP_BASES_ENDOMORPHISM -- msm_batch runs whole MSMs over the 2n points, and
         the window-sharded calls shard the 8 half-length windows; False: MSM_HIP_BASES_PLAIN; None: the C ABI's default (flags = 0: whole
         object resolves it to the plain set).  precompute: True -- the 16-bit fixed-base tables for the whole MSMs of msm_batch (the
         window-sharded calls ignore them); "wide" -- the wide tables: msm_batch runs whole MSMs on them and the window-sharded calls share
-        their virtual windows (set_wide_bits; default 19-bit digits: 8 virtual windows)."""
+        their virtual windows (set_wide_bits; default 19-bit digits: 8 virtual windows).  zero_is_identity: as MsmContext.set_bases, on every device."""
         b = bytes(points)
         flags = (1 if check_on_curve else 0) | (8 if endomorphism else 0) | (32 if precompute == "wide" else 4 if precompute else 0)
+        flags |= BASES_ZERO_IS_IDENTITY if zero_is_identity else 0
         if endomorphism is False and not precompute:
             flags |= 16
         _check(lib().msm_hip_mgpu_set_bases(self._h, b, len(b) // self.pb, flags), "msm_hip_mgpu_set_bases")

@@ -114,6 +114,7 @@ struct LaunchPlan {
   size_t stride = 0;                               // per-window stride of the entry arrays
   bool sparse = false;                             // a sparse launch: input j is (scalar j, base indices[j]); n counts entries (SparseIdx)
   const uint32_t* indices = nullptr;               // sparse: the n base indices (device)
+  bool mask = false;                               // the bases hold identity records: the scalars are first copied with theirs zeroed (k_mask_identity)
 };
 
 struct Slot {
@@ -184,6 +185,9 @@ struct msm_hip_ctx {
   int wide_bits_choice = 0;           // msm_hip_set_wide_bits: the digit width the next wide base set gets (0: by the number of bases)
   int wide_bits = 0;                  // != 0: d_bases holds the wide tables 2^(C w) P_i for C-bit digits (MSM_HIP_BASES_PRECOMPUTE_WIDE; pick_wide_bits)
   bool endo = false;                  // d_bases holds phi(P_i) behind the n bases (MSM_HIP_BASES_ENDOMORPHISM)
+  uint64_t* d_id_bits = nullptr;      // MSM_HIP_BASES_ZERO_IS_IDENTITY: bit i = base i is the identity (ceil(n / 64) words; k_convert_points_zero_id)
+  size_t cap_id_bits = 0;             // in words
+  size_t n_identity = 0;              // identity records among the resident bases: nonzero -> every launch masks its scalars (k_mask_identity)
   uint32_t* d_halves = nullptr;       // the split scalars of one launch (main stream only): [vector][2n] x 4 words
   size_t cap_halves = 0;              // in scalars
 
@@ -210,8 +214,9 @@ struct msm_hip_ctx {
   uint32_t* d_chunk_slot = nullptr;  // [W][chunks] bucket slot of every SMVP chunk's first entry
   uint32_t* d_list_len = nullptr;    // shares of the wide tables' virtual windows: [W][sub-tiles] lengths of the first pass's compact entry lists (k_count_wide_list)
   size_t cap_list_len = 0;
-  uint32_t* d_scalar_conv = nullptr;  // canonical copies of scalars handed over in R = 2^256 Montgomery form (one launch's worth)
-  size_t cap_scalar_conv = 0;         // in scalars
+  uint32_t* d_scalar_conv = nullptr;  // canonical copies of scalars handed over in R = 2^256 Montgomery form (one launch's worth); behind them, a
+                                      // masked launch's copy of its scalars with those of identity bases zeroed (k_mask_identity)
+  size_t cap_scalar_conv = 0;         // in 32-byte scalars
   uint32_t scalar_format = 0;         // MSM_HIP_SCALARS_CANONICAL / MSM_HIP_SCALARS_MONT256 / MSM_HIP_SCALARS_U8 .. U64 (read by each launch)
   int window_bits = 0;                // 0: chosen from n for whole-MSM launches (pick_window_bits); else 12 / 14 / 16
   uint32_t* d_part_hist = nullptr;  // [MAXLW][128][FINE_SPLIT][256] sub-range histograms of huge coarse bins (k_fine_hist), on first use
@@ -533,8 +538,9 @@ int ensure_work(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   if (p.mode == MODE_HALVES && !p.planes &&  // (the halves as an array: only when the second pass reads them)
       (rc = grow(ctx, ctx->cap_halves, scalars, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_halves, c * 8); })))
     return rc;
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb &&
-      (rc = grow(ctx, ctx->cap_scalar_conv, scalars, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_scalar_conv, c * 8); })))
+  // canonical copies of MONT256 scalars, and behind them a masked launch's copy of its scalars (any width: nb bytes each, 32 for the 32-byte formats)
+  const size_t conv = (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb ? scalars : 0) + (p.mask ? (scalars * (p.nb ? p.nb : 32) + 31) / 32 : 0);
+  if (conv && (rc = grow(ctx, ctx->cap_scalar_conv, conv, true, [&](size_t c) { return dev_alloc(ctx, ctx->d_scalar_conv, c * 8); })))
     return rc;
   return MSM_HIP_OK;
 }
@@ -717,6 +723,7 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
   p.stride = stride_for(p.n_entries);
   p.sparse = sparse;
   p.indices = indices;
+  p.mask = ctx->n_identity != 0;
   return MSM_HIP_OK;
 }
 
@@ -746,7 +753,17 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
   auto mark = [&](int i) { return tl >= 2 ? hipEventRecord(s.ev[i], st) : hipSuccess; };
   HIP_TRY(ctx, hipStreamWaitEvent(st, s.done, 0));
   HIP_TRY(ctx, mark(0));
-  if (ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
+  const bool mont = ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb;
+  if (p.mask) {  // identity records among the bases: a copy of the scalars with theirs zeroed, before anything validates or converts them (stage 0)
+    uint8_t* masked = reinterpret_cast<uint8_t*>(ctx->d_scalar_conv) + (mont ? (size_t)p.nvec * p.n * 32 : 0);  // (behind the canonical copies)
+    dispatch<32, 8, 4, 2, 1>(p.nb ? p.nb : 32, [&](auto w) {
+      hipLaunchKernelGGL(k_mask_identity<decltype(w)::value>, dim3(blocks_for(p.n, 256), p.nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, masked, p.n,
+                         p.base_off, (const uint64_t*)ctx->d_id_bits, (uint32_t)ctx->n_bases, p.sparse ? p.indices : (const uint32_t*)nullptr);
+    });
+    AFTER_KERNEL(ctx, "k_mask_identity", st);
+    d_scalars = reinterpret_cast<const uint32_t*>(masked);
+  }
+  if (mont) {  // Montgomery-form scalars: canonical copies first (part of stage 0)
     const size_t count = (size_t)p.nvec * p.n;
     hipLaunchKernelGGL(ctx->ops->scalars_from_mont256, dim3(blocks_for(count, 256)), dim3(256), 0, st, d_scalars, ctx->d_scalar_conv, count, d_err);
     AFTER_KERNEL(ctx, "k_scalars_from_mont256", st);
@@ -1060,7 +1077,7 @@ constexpr size_t MAX_PRECOMPUTE_POINTS = (size_t)1 << 24;  // 16 tables: 16 GiB,
 // over n points), or -- none of the three -- the fastest the curve has: the drop-in call shape (flags = 0; msm_hip_msm_bn254_g1 ≙ compute_msm,
 // src/cuzk/msm.rs:75-94) runs the mode the headline figure is measured in (656 vs 701 - 714 MSM/s at 2^20 in round 3, when it did not).
 constexpr uint32_t BASE_FLAGS_ALL = MSM_HIP_CHECK_ON_CURVE | MSM_HIP_BASES_MONT256 | MSM_HIP_BASES_PRECOMPUTE | MSM_HIP_BASES_ENDOMORPHISM | MSM_HIP_BASES_PLAIN |
-                                    MSM_HIP_BASES_PRECOMPUTE_WIDE;
+                                    MSM_HIP_BASES_PRECOMPUTE_WIDE | MSM_HIP_BASES_ZERO_IS_IDENTITY;
 constexpr size_t MAX_WIDE_POINTS = (size_t)1 << 24;  // 13 tables of 20-bit digits: 13 GiB; sort arrays of 16 x 13 n entries: 31 GiB
 inline bool reduce_priority_on() {  // MSM_HIP_REDUCE_PRIORITY=0: plain reduce streams (msm_hip_ctx_create_curve)
   static const bool v = [] { const char* e = getenv("MSM_HIP_REDUCE_PRIORITY"); return !e || atoi(e) != 0; }();
@@ -1095,21 +1112,29 @@ int reserve_bases(msm_hip_ctx* ctx, size_t n, uint32_t flags) {
   ctx->precomputed = false;
   ctx->wide_bits = 0;
   ctx->endo = false;
+  ctx->n_identity = 0;
   const size_t records = wide ? n * (size_t)wide_tables_of(pick_wide_bits(ctx, n)) : tables ? n * NWIN : endo ? 2 * n : n;
   return grow(ctx, ctx->cap_bases, records, false, [&](size_t c) { return dev_alloc(ctx, ctx->d_bases, c * 2 * (size_t)ctx->ops->coord_words); });
 }
 
 // wire bytes at d_xy (may be ctx->d_bases itself: the conversion is element-wise) -> resident Montgomery bases
+// (MSM_HIP_BASES_ZERO_IS_IDENTITY: all-zero records are the identity -- marked in d_id_bits, counted in the error word's neighbour d_err[1])
 int set_bases_from_device(msm_hip_ctx* ctx, const uint32_t* d_xy, size_t n, uint32_t flags) {
   if (n == 0) return MSM_HIP_OK;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_err, 0, 4, ctx->stream));
-  hipLaunchKernelGGL(ctx->ops->convert_points, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_xy, ctx->d_bases, n, flags, ctx->d_err);
+  const bool zero_id = (flags & MSM_HIP_BASES_ZERO_IS_IDENTITY) != 0;
+  int rc;
+  if (zero_id && (rc = grow(ctx, ctx->cap_id_bits, (n + 63) / 64, false, [&](size_t c) { return dev_alloc(ctx, ctx->d_id_bits, c); }))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_err, 0, zero_id ? 8 : 4, ctx->stream));
+  if (zero_id)
+    hipLaunchKernelGGL(ctx->ops->convert_points_zero_id, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_xy, ctx->d_bases, n, flags, ctx->d_err,
+                       ctx->d_id_bits, ctx->d_err + 1);
+  else
+    hipLaunchKernelGGL(ctx->ops->convert_points, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, d_xy, ctx->d_bases, n, flags, ctx->d_err);
   HIP_TRY(ctx, hipGetLastError());
-  uint32_t bits = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&bits, ctx->d_err, 4, hipMemcpyDeviceToHost, ctx->stream));
+  uint32_t bits[2] = {0u, 0u};
+  HIP_TRY(ctx, hipMemcpyAsync(bits, ctx->d_err, zero_id ? 8 : 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  int rc = err_from_bits(bits);
-  if (rc) return rc;
+  if ((rc = err_from_bits(bits[0]))) return rc;
   if (flags & (MSM_HIP_BASES_PRECOMPUTE | MSM_HIP_BASES_PRECOMPUTE_WIDE)) {  // tables 1 .. 15 behind the plain set: T_w[i] = 2^(16 w) P_i (wide: 1 .. 13, 2^(19 w) P_i, the last one top_shift doublings short)
     const bool wide = (flags & MSM_HIP_BASES_PRECOMPUTE_WIDE) != 0;
     const int wb = wide ? pick_wide_bits(ctx, n) : 0;
@@ -1126,6 +1151,7 @@ int set_bases_from_device(msm_hip_ctx* ctx, const uint32_t* d_xy, size_t n, uint
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->endo = true;
   }
+  ctx->n_identity = bits[1];
   ctx->n_bases = n;
   return MSM_HIP_OK;
 }
@@ -1246,7 +1272,7 @@ int msm_hip_ctx_create_curve(msm_hip_ctx** out, int device_id, int curve) {
   if ((rc = dev_alloc(ctx, ctx->d_counts, (size_t)MAXLW * MAX_TILES * NCOARSE))) return fail(rc);
   if ((rc = dev_alloc(ctx, ctx->d_bin_total, (size_t)MAXLW * NCOARSE))) return fail(rc);
   if ((rc = dev_alloc(ctx, ctx->d_coarse_ptr, (size_t)MAXLW * (NCOARSE + 1)))) return fail(rc);
-  if ((rc = dev_alloc(ctx, ctx->d_err, 1))) return fail(rc);
+  if ((rc = dev_alloc(ctx, ctx->d_err, 2))) return fail(rc);  // the error word, and the identity count of a base conversion
   // result slots (buckets, piece arrays, events) are set up by the first launch that uses them: setup_slot / ensure_work
   *out = ctx;
   return MSM_HIP_OK;
@@ -1260,7 +1286,7 @@ void msm_hip_ctx_destroy(msm_hip_ctx* ctx) {
   for (hipStream_t r : ctx->reduce_stream)
     if (r) (void)hipStreamSynchronize(r);
   void* bufs[] = {ctx->d_list_len, ctx->d_bases,   ctx->d_halves, ctx->d_batch_stage, ctx->d_scalar_conv, ctx->d_part_hist, ctx->d_digits, ctx->d_negbits, ctx->d_counts,     ctx->d_bin_total, ctx->d_coarse_ptr,
-                  ctx->d_tmp_val, ctx->d_tmp_fine, ctx->d_val,    ctx->d_chunk_slot, ctx->d_err,       ctx->d_stage};
+                  ctx->d_tmp_val, ctx->d_tmp_fine, ctx->d_val,    ctx->d_chunk_slot, ctx->d_err,       ctx->d_stage, ctx->d_id_bits};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (int k = 0; k < NSLOT; k++) {
@@ -2069,6 +2095,7 @@ int msm_hip_test_env_report(const msm_hip_ctx* ctx, char* out, size_t cap) {
     put("last_logr", ctx->last_logr);
     put("last_inline_reduce", ctx->last_inline_reduce);
     put("last_fine_hist", ctx->last_fine_hist);
+    put("last_identity_mask", ctx->last.mask);
   }
   return fits ? (int)len : MSM_HIP_ERR_INVALID_ARG;
 }

@@ -25,6 +25,7 @@
 #endif
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #ifndef MSM_SPARSE_IDX
@@ -221,6 +222,51 @@ __global__ void __launch_bounds__(256) k_convert_points(const uint32_t* in, uint
     const fq lhs = fq_canonical(fq_sqr(y));
     const fq rhs = fq_canonical(fq_tidy(fq_add(fq_mul(fq_sqr(x), x), fq_curve_b())));
     if (!fq_equal_exact(lhs, rhs)) atomicOr(err, ERRBIT_NOT_ON_CURVE);
+  }
+  st_fq(out + i * PT_WORDS, x);
+  st_fq(out + i * PT_WORDS + CW, y);
+}
+
+// The same for a base set that may hold the point at infinity as an all-zero record (MSM_HIP_BASES_ZERO_IS_IDENTITY; (0, 0) is on none of the
+// curves, b != 0).  Such a record is stored as the group's generator -- every resident record stays a point of order r, as k_precompute_tables and
+// k_endo_points assume -- and marked in `id_bits` (bit i of word i / 64: one wave's ballot, stored by its first lane); id_count receives how many
+// there are.  The launches zero the scalars of marked records (k_mask_identity) before anything reads them, so the placeholder is never summed.
+__global__ void __launch_bounds__(256) k_convert_points_zero_id(const uint32_t* in, uint32_t* out, size_t n,  // in may alias out (element-wise)
+                                                                uint32_t flags, uint32_t* __restrict__ err, uint64_t* __restrict__ id_bits,
+                                                                uint32_t* __restrict__ id_count) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = i < n;
+  uint32_t wx[CW], wy[CW], any = 0;
+  if (valid) {
+    ld_coord(in + i * PT_WORDS, wx);
+    ld_coord(in + i * PT_WORDS + CW, wy);
+#pragma unroll
+    for (int k = 0; k < CW; k++) any |= wx[k] | wy[k];
+  }
+  const bool zero = valid && any == 0;
+  const unsigned long long ids = __ballot(zero);  // (a wave's 64 lanes are the records of one bitmap word)
+  if ((threadIdx.x & 63) == 0 && valid) {
+    id_bits[i >> 6] = ids;
+    if (ids) atomicAdd(id_count, (uint32_t)__popcll(ids));
+  }
+  if (!valid) return;
+  fq x, y;
+  if (zero) {
+#pragma unroll
+    for (int k = 0; k < FQ_L; k++) {
+      x.v[k] = FQ_GEN_X29[k];
+      y.v[k] = FQ_GEN_Y29[k];
+    }
+  } else {
+    if (geq_modulus<0>(wx) || geq_modulus<0>(wy)) atomicOr(err, ERRBIT_NONCANONICAL);
+    const bool m256 = (flags & 2u) != 0;
+    x = m256 ? fq_from_mont256(fq_unpack(wx)) : fq_to_mont(fq_unpack(wx));
+    y = m256 ? fq_from_mont256(fq_unpack(wy)) : fq_to_mont(fq_unpack(wy));
+    if (flags & 1u) {
+      const fq lhs = fq_canonical(fq_sqr(y));
+      const fq rhs = fq_canonical(fq_tidy(fq_add(fq_mul(fq_sqr(x), x), fq_curve_b())));
+      if (!fq_equal_exact(lhs, rhs)) atomicOr(err, ERRBIT_NOT_ON_CURVE);
+    }
   }
   st_fq(out + i * PT_WORDS, x);
   st_fq(out + i * PT_WORDS + CW, y);
@@ -439,6 +485,43 @@ __global__ void __launch_bounds__(256) k_scalars_from_mont256(const uint32_t* __
   uint4* q = reinterpret_cast<uint4*>(out + i * 8);
   q[0] = make_uint4(o[0], o[1], o[2], o[3]);
   q[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// A launch over a base set with identity records (k_convert_points_zero_id): its scalars -- `nvec` (grid.y) contiguous vectors of n elements of NB
+// bytes -- copied to `out` with zeros where the base is the identity.  Input j of a vector is base base_off + j or, sparse (idx != null), base
+// idx[j]; an index not below n_bases is left to the sort's ERRBIT_BAD_INDEX path and reads no bitmap word.  It runs before any pass validates,
+// converts or splits the scalars, so a scalar paired with the identity is ignored exactly as a zero scalar is.  No field arithmetic: BN254's unit only.
+template <int NB>
+__global__ void __launch_bounds__(256) k_mask_identity(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, size_t n, size_t base_off,
+                                                       const uint64_t* __restrict__ id_bits, uint32_t n_bases, const uint32_t* __restrict__ idx) {
+  static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 8 || NB == 32, "scalar width");
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const size_t e = (size_t)blockIdx.y * n + j;
+  bool zero;
+  if (idx) {
+    const uint32_t b = idx[j];
+    zero = b < n_bases && ((id_bits[b >> 6] >> (b & 63u)) & 1u);
+  } else {
+    const size_t b = base_off + j;
+    zero = (id_bits[b >> 6] >> (b & 63u)) & 1u;
+  }
+  if constexpr (NB == 32) {
+    const uint4* s = reinterpret_cast<const uint4*>(in) + 2 * e;
+    uint4* d = reinterpret_cast<uint4*>(out) + 2 * e;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+    if (!zero) {
+      a = s[0];
+      b = s[1];
+    }
+    d[0] = a;
+    d[1] = b;
+  } else {
+    using T = std::conditional_t<NB == 1, uint8_t, std::conditional_t<NB == 2, uint16_t, std::conditional_t<NB == 4, uint32_t, uint64_t>>>;
+    T v = 0;
+    if (!zero) v = reinterpret_cast<const T*>(in)[e];
+    reinterpret_cast<T*>(out)[e] = v;
+  }
 }
 
 // `nvec` scalar vectors (vec_stride words apart) may share one launch: vector v, window w is handled as local window

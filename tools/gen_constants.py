@@ -374,4 +374,7 @@ print(arr("GLV_N11_32", limbs(N11, 32, 5)) + "  // -sign(b2) a1 mod 2^160")
 print(arr("GLV_N12_32", limbs(N12, 32, 5)) + "  // -sign(-b1) a2 mod 2^160")
 print(arr("GLV_N21_32", limbs(N21, 32, 5)) + "  // -sign(b2) b1 mod 2^160")
 print(arr("GLV_N22_32", limbs(N22, 32, 5)) + "  // -sign(-b1) b2 mod 2^160")
+print("// the generator (order r), Montgomery form: what an identity record of a base set is stored as (MSM_HIP_BASES_ZERO_IS_IDENTITY)")
+print(arr("FQ_GEN_X29", limbs29(GEN[0] * R261 % P)))
+print(arr("FQ_GEN_Y29", limbs29(GEN[1] * R261 % P)))
 print("}  // namespace MSM_FIELD_NS")
