@@ -88,33 +88,56 @@ constexpr int NREDUCE = 2;  // reduce streams (slot k uses stream k % NREDUCE): 
                             // then owns 3 streams; streams beyond the process's hardware queues (GPU_MAX_HW_QUEUES) share
                             // them: correct, with less overlap.
 
-// What a launch is made of, decided once from its request (plan_launch) and read by its buffer sizing (ensure_work), both stages of its enqueue
-// (enqueue_sort, enqueue_reduce), the host finish and the stage read-back hooks
-struct LaunchPlan {
+// What a caller asks of one launch.  The defaults are one plain whole MSM of 16-bit windows over the first n bases into slot 0, its sums to the
+// host, so a call site names only what differs.  plan_launch checks it and makes the LaunchPlan.
+struct LaunchRequest {
+  const void* scalars = nullptr;      // device: nvec contiguous vectors of n scalars in the context's scalar format
+  size_t n = 0;
+  int slot = 0;
+  int nvec = 1;
+  void* sums_dev = nullptr;           // device memory for the window sums; null: the slot's own buffer, and from there the host
   LaunchMode mode = MODE_PLAIN;
+  int w_begin = 0, w_end = NWIN;      // windows [w_begin, w_end) of every vector, in units of `wbits`-bit windows (MODE_WIDE: all T digits)
+  int wbits = WBITS;                  // (MODE_WIDE: the tables' digit width)
+  int v_begin = 0, v_count = 0;       // MODE_WIDE, v_count != 0: a SHARE of the virtual windows -- [v_begin, v_begin + v_count) of every vector, whose sums are
+                                      // (window sum, plain total) pairs, 2 records per local window.  0: whole MSMs, all 2^(C-16) virtual windows
+  bool sparse = false;                // a sparse launch: input j is (scalar j, base indices[j]) and n counts entries (SparseIdx) -- one whole MSM, into
+  const uint32_t* indices = nullptr;  // the slot, over the resident bases from record 0; not on wide tables.  The n indices are device memory
+  size_t base_off = 0;                // point i of the launch is base base_off + i (the parts of msm_hip_run)
+  bool sync = false;                  // a synchronous call (run = launch + finish at once): nothing will be pipelined behind this launch
+
+  LaunchRequest(const void* scalars_ = nullptr, size_t n_ = 0, int slot_ = 0, int nvec_ = 1, void* sums_dev_ = nullptr)
+      : scalars(scalars_), n(n_), slot(slot_), nvec(nvec_), sums_dev(sums_dev_) {}
+  LaunchRequest& windows(LaunchMode mode_, int begin, int end, int bits = WBITS) {
+    mode = mode_, w_begin = begin, w_end = end, wbits = bits;
+    return *this;
+  }
+  LaunchRequest& wide(int bits, int vbegin, int vcount) {  // all digits of `bits`-bit wide tables
+    v_begin = vbegin, v_count = vcount;
+    return windows(MODE_WIDE, 0, wide_tables_of(bits), bits);
+  }
+};
+
+// What a launch is made of: its request as plan_launch settled it, and everything decided once from that -- read by the launch's buffer sizing
+// (ensure_work), both stages of its enqueue (enqueue_sort, enqueue_reduce), the host finish and the stage read-back hooks
+struct LaunchPlan : LaunchRequest {   // (settled: wbits = the window bits of everything behind the recode, 16 for MODE_WIDE; v_count = the virtual windows run)
   int nb = 0;                         // MODE_NARROW: bytes per scalar
-  size_t n = 0, base_off = 0;         // point i of the launch is base base_off + i
-  int nvec = 1;                       // scalar vectors (contiguous) of the launch
-  int w_begin = 0, w_count_vec = 0;   // windows [w_begin, w_begin + w_count_vec) of every vector, in the request's window bits (MODE_WIDE: the T digits)
+  int w_count_vec = 0;                // windows [w_begin, w_begin + w_count_vec) of every vector, in the request's window bits (MODE_WIDE: the T digits)
   int wide_bits = 0;                  // MODE_WIDE: the tables' digit width
-  int v_begin = 0, v_count = 0;       // MODE_WIDE: virtual windows [v_begin, v_begin + v_count) of every vector (whole MSMs: all of them)
   bool pairs = false;                 // MODE_WIDE, a share of the virtual windows: the launch leaves (window sum, plain total) record pairs
-  uint32_t* sums_dev = nullptr;       // device window sums; null: the slot's own buffer, and from there the host
-  int wbits = WBITS;                  // window bits of everything behind the recode (MODE_WIDE: 16)
   uint32_t half = 0, ncoarse = 0;     // bucket slots per window; coarse bins that can hold entries
   int w_count = 0;                    // local windows (bucket sets) of the launch
   int nwin = 0, combine_bits = 0;     // host finish: window sums per MSM, and the bits between consecutive windows
   bool whole = false;                 // every vector's windows make a whole MSM that the host finish can combine
   size_t n_sc = 0, n_entries = 0;     // inputs of the recode; entries one local window may receive
-  int full_windows = 0;               // windows of one whole MSM in this mode: the sort arrays are sized for at least that many
+  int full_windows = 0;               // local windows of one whole MSM in this mode: the sort arrays are sized for at least that many
   bool digits = false;                // the first pass keeps the digit planes for the debug read-back
   bool planes = false, share_shape = false, list_path = false;  // use_planes; the share kernels of the wide tables (k_scatter_wide<C, true>, k_scatter_list)
   uint32_t tiles = 0, tile_len = 0, subtiles = 0;  // tiles of scalars of the two global sort passes; LIST_SUB sub-tiles
   uint32_t chunks = 0, chunk_len = 0;              // SMVP chunks per local window and their (longest) length
   size_t stride = 0;                               // per-window stride of the entry arrays
-  bool sparse = false;                             // a sparse launch: input j is (scalar j, base indices[j]); n counts entries (SparseIdx)
-  const uint32_t* indices = nullptr;               // sparse: the n base indices (device)
   bool mask = false;                               // the bases hold identity records: the scalars are first copied with theirs zeroed (k_mask_identity)
+  bool fine_hist = false;                          // written by the sort stage: it ran k_fine_hist
 };
 
 struct Slot {
@@ -179,7 +202,6 @@ struct msm_hip_ctx {
   int last_hip_error = 0;
 
   uint32_t* d_bases = nullptr;  // n_bases x 16 words
-  size_t launch_base_off = 0;   // consumed by the next launch: it runs over the bases [off, off + n) (internal: the parts of msm_hip_run)
   size_t n_bases = 0, cap_bases = 0;  // points per table; capacity in point records (16 x n_bases with fixed-base tables)
   bool precomputed = false;           // d_bases holds the 16 tables 2^(16 w) P_i (MSM_HIP_BASES_PRECOMPUTE)
   int wide_bits_choice = 0;           // msm_hip_set_wide_bits: the digit width the next wide base set gets (0: by the number of bases)
@@ -203,7 +225,6 @@ struct msm_hip_ctx {
   uint64_t* d_negbits = nullptr; // with the planes of a launch: one sign bit per input of every vector
   size_t cap_planes = 0;         // capacity (u16 entries) of d_digits; d_negbits holds cap_planes / 64 + 2 MAXLW words
   bool debug = false;
-  bool sync_call = false;  // set by the synchronous entry points (run = launch + finish at once) around their launch: nothing will be pipelined behind it
   int timing_level = 2;  // 0: no stage events, 1: only around the SMVP kernel, 2: every stage boundary
   uint32_t* d_counts = nullptr;      // [W][tiles][128]
   uint32_t* d_bin_total = nullptr;   // [W][128]
@@ -231,8 +252,6 @@ struct msm_hip_ctx {
   int last_slot = 0;
   int last_logr = 0;                // ... the LOG_R of its k_bpr_rowcol variant (pick_rowcol), and whether its stitch + reduce ran on the main stream
   bool last_inline_reduce = false;  //     (test hook msm_hip_test_env_report)
-  bool last_fine_hist = false;      // ... and whether its sort ran k_fine_hist
-  bool sort_fine_hist = false;      // (the sort stage's, taken over by the reduce stage of the same launch)
   float stage_ms[10] = {};
 };
 
@@ -636,35 +655,29 @@ int check_run_args(msm_hip_ctx* ctx, const void* scalars, size_t n, bool sparse 
   return MSM_HIP_OK;
 }
 
-// The one place a launch request is checked and shaped: windows [w_begin, w_end) -- in units of `wbits`-bit windows -- of `nvec` scalar vectors
-// into `slot`, their sums to `sums_dev` (device memory) or, when null, to the slot's pinned buffer.  Consumes ctx->launch_base_off.
-// (MODE_WIDE: called with the tables' digit width and all T digits; everything behind the recode sees local windows of 16 bits.  v_count != 0: a
-//  SHARE of the virtual windows -- [v_begin, v_begin + v_count) of every vector; its sums are (window sum, plain total) pairs, 2 records per local
-//  window.  0: whole MSMs, all 2^(C-16) virtual windows)
-// `sparse`: n entries (scalar j, base indices[j]) -- one whole MSM, into the slot, over the resident bases from record 0; not on wide tables.
-int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* scalars, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
-                void* sums_dev, int v_begin, int v_count, bool sparse = false, const uint32_t* indices = nullptr) {
+// The one place a launch request is checked and shaped
+int plan_launch(msm_hip_ctx* ctx, const LaunchRequest& r, LaunchPlan& p) {
+  const LaunchMode mode = r.mode;
+  const size_t n = r.n;
+  const int nvec = r.nvec, w_begin = r.w_begin, w_end = r.w_end, wbits = r.wbits;
   const bool merge = mode == MODE_TABLES, halves = mode == MODE_HALVES, wide = mode == MODE_WIDE;
-  const bool pairs = wide && v_count != 0;
+  const bool pairs = wide && r.v_count != 0;
   const int nb = ctx && mode == MODE_NARROW ? narrow_bytes(ctx->scalar_format) : 0;
-  int rc = check_run_args(ctx, scalars, n, sparse);
-  const size_t base_off = ctx ? ctx->launch_base_off : 0;
-  if (ctx) ctx->launch_base_off = 0;
-  if (rc) return rc;
-  if (sparse && (wide || (!indices && n) || nvec != 1 || sums_dev || base_off || w_begin != 0 ||
-                 w_end != (nb ? narrow_windows(wbits, nb) : merge ? NWIN : nwin_of(wbits, halves))))
-    return MSM_HIP_ERR_INVALID_ARG;
-  if (!sparse && base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
-  if (slot < 0 || slot >= NSLOT || w_begin < 0 || w_end > (nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves)) || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
+  if (const int rc = check_run_args(ctx, r.scalars, n, r.sparse)) return rc;
+  // windows of one whole MSM in this mode, in the request's units (fixed-base tables: the 16, or wide_tables_of(C) = nwin_of(C), digits of a scalar)
+  const int whole_windows = nb ? narrow_windows(wbits, nb) : merge ? NWIN : nwin_of(wbits, halves);
+  if (r.sparse && (wide || (!r.indices && n) || nvec != 1 || r.sums_dev || r.base_off || w_begin != 0 || w_end != whole_windows)) return MSM_HIP_ERR_INVALID_ARG;
+  if (!r.sparse && r.base_off + n > ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
+  if (r.slot < 0 || r.slot >= NSLOT || w_begin < 0 || w_end > whole_windows || w_begin >= w_end) return MSM_HIP_ERR_INVALID_ARG;
   // narrow scalars: whole MSMs only, over the plain records, from a pointer aligned to the scalar's size
-  if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != narrow_windows(wbits, nb) || sums_dev || base_off || nvec * w_end > narrow_max_windows(nb) ||
+  if (mode == MODE_NARROW && (!nb || w_begin != 0 || w_end != whole_windows || r.sums_dev || r.base_off || nvec * w_end > narrow_max_windows(nb) ||
                               (byte_windows(nb) && wbits != BYTE_WBITS) ||
-                              reinterpret_cast<uintptr_t>(scalars) % (uintptr_t)nb)) return MSM_HIP_ERR_INVALID_ARG;
-  if (wide && (nvec < 1 || w_begin != 0 || wbits != ctx->wide_bits || w_end != wide_tables_of(wbits))) return MSM_HIP_ERR_INVALID_ARG;
-  if (wide && !pairs && (nvec * wide_vwin_of(ctx->wide_bits) > 24 || sums_dev)) return MSM_HIP_ERR_INVALID_ARG;
-  if (pairs && (v_begin < 0 || v_count < 0 || v_begin + v_count > wide_vwin_of(ctx->wide_bits))) return MSM_HIP_ERR_INVALID_ARG;
-  if (!wide && v_count) return MSM_HIP_ERR_INVALID_ARG;
-  if (wide && !pairs) v_count = wide_vwin_of(ctx->wide_bits);
+                              reinterpret_cast<uintptr_t>(r.scalars) % (uintptr_t)nb)) return MSM_HIP_ERR_INVALID_ARG;
+  if (wide && (nvec < 1 || w_begin != 0 || wbits != ctx->wide_bits || w_end != whole_windows)) return MSM_HIP_ERR_INVALID_ARG;
+  if (wide && !pairs && (nvec * wide_vwin_of(ctx->wide_bits) > 24 || r.sums_dev)) return MSM_HIP_ERR_INVALID_ARG;
+  if (pairs && (r.v_begin < 0 || r.v_count < 0 || r.v_begin + r.v_count > wide_vwin_of(ctx->wide_bits))) return MSM_HIP_ERR_INVALID_ARG;
+  if (!wide && r.v_count) return MSM_HIP_ERR_INVALID_ARG;
+  const int v_count = wide && !pairs ? wide_vwin_of(ctx->wide_bits) : r.v_count;
   const int w_count_vec = w_end - w_begin;
   // fixed-base tables (`merge`): the w_count_vec windows of a vector feed one bucket set -- one local window of up to n * w_count_vec entries per
   // vector -- whose entries index the tables (window w of point i = record w * n_bases + i).  Wide tables: the same indexing; each vector's bucket
@@ -674,34 +687,28 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
   if (nvec < 1 || w_count > MAXLW) return MSM_HIP_ERR_INVALID_ARG;
 
   p = LaunchPlan{};
-  p.mode = mode;
+  static_cast<LaunchRequest&>(p) = r;
   p.nb = nb;
-  p.n = n;
-  p.base_off = base_off;
-  p.nvec = nvec;
-  p.w_begin = w_begin;
   p.w_count_vec = w_count_vec;
   p.wide_bits = wide ? ctx->wide_bits : 0;
-  p.v_begin = v_begin;
   p.v_count = v_count;
   p.pairs = pairs;
-  p.sums_dev = static_cast<uint32_t*>(sums_dev);
-  p.wbits = wide ? WBITS : wbits;
+  p.wbits = wide ? WBITS : wbits;  // (everything behind the recode sees local windows of 16 bits)
   p.half = 1u << (p.wbits - 1);
   p.ncoarse = p.half / FINE;
   p.w_count = w_count;
   // fixed-base launches leave ONE sum per vector (every table already carries its power of two): nothing to combine but the copy
-  p.nwin = merge ? 1 : wide ? v_count : nb ? narrow_windows(wbits, nb) : nwin_of(wbits, halves);
+  p.nwin = merge ? 1 : wide ? v_count : whole_windows;
   p.combine_bits = byte_windows(nb) ? 8 : p.wbits;  // (byte windows: window j weighs 2^(8 j))
-  p.whole = !pairs && w_count_vec == (wide ? wide_tables_of(wbits) : nb ? p.nwin : nwin_of(wbits, halves));
+  p.whole = !pairs && w_count_vec == whole_windows;
   // endomorphism (`halves`): the recode runs over 2n halves of 16 B (the first pass splits the scalars) against 2n points -- P_i and, n_bases records
   // further on, phi(P_i) -- in half as many windows
   p.n_sc = halves ? 2 * n : n;
   p.n_entries = merge || wide ? n * (size_t)w_count_vec : p.n_sc;  // (wide: what ONE virtual window may receive)
-  p.full_windows = wide ? wide_vwin_of(ctx->wide_bits) : merge ? 1 : halves ? nwin_of(wbits, true) : nb ? w_count_vec : NWIN;
+  p.full_windows = wide ? wide_vwin_of(ctx->wide_bits) : merge ? 1 : whole_windows;  // local windows
   p.digits = ctx->debug && !merge && !wide && !byte_windows(nb);
   // window shares (a few of a scalar's windows per vector): the first pass leaves digit planes, the second reads them (k_scatter_planes)
-  p.planes = use_planes(ctx, mode, w_count_vec, p.wbits, sparse);
+  p.planes = use_planes(ctx, mode, w_count_vec, p.wbits, r.sparse);
   // shares of at most WIDE_SHARE_VWIN_MAX virtual windows of wide tables: the first pass leaves compact lists of the share's entries per sub-tile of
   // LIST_SUB scalars (k_count_wide_list / k_scatter_list); tiles are then whole sub-tiles.  MSM_HIP_WIDE_SHARE_LISTS=0: the two-pass shape (A/B aid)
   p.share_shape = pairs && v_count <= WIDE_SHARE_VWIN_MAX;
@@ -721,10 +728,29 @@ int plan_launch(msm_hip_ctx* ctx, LaunchPlan& p, LaunchMode mode, const void* sc
     p.chunks = chunks_for(p.n_entries, p.chunk_len);
   }
   p.stride = stride_for(p.n_entries);
-  p.sparse = sparse;
-  p.indices = indices;
   p.mask = ctx->n_identity != 0;
   return MSM_HIP_OK;
+}
+
+// `r` (its n and nvec) as a WHOLE MSM on this context: the mode, window bits and windows that the scalar format, then the mode the bases are held in,
+// give it -- narrow scalars, wide tables, 16-bit tables, the endomorphism, plain windows.  The one place that rule lives: the dense and the sparse
+// entry points, the batch runners' group size (batch_group) and the one-shot call all ask here.
+// Nothing to compute (n == 0: identity sums) is the plain 16-bit request whatever the format and the bases, and so is a request no mode has room
+// for (nvec x 16 windows beyond MAXLW), which plan_launch then rejects -- as it rejects narrow and wide windows beyond their limits.
+LaunchRequest whole_msm_request(const msm_hip_ctx* ctx, LaunchRequest r) {
+  if (r.n == 0) return r.windows(MODE_PLAIN, 0, NWIN);
+  if (const int nb = narrow_bytes(ctx->scalar_format)) {  // over the plain records, which every base mode keeps
+    const int wbits = byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, r.n, r.nvec, false, nb);
+    return r.windows(MODE_NARROW, 0, narrow_windows(wbits, nb), wbits);
+  }
+  if (ctx->wide_bits) return r.wide(ctx->wide_bits, 0, 0);             // an MSM is 2^(C-16) local windows, of which a launch holds at most 24
+  if (ctx->precomputed) return r.windows(MODE_TABLES, 0, NWIN);         // one bucket set per vector
+  if (ctx->endo && r.nvec * nwin_of(16, true) <= MAXLW) {  // half-length scalars over 2n points
+    const int wbits = pick_window_bits(ctx, r.n, r.nvec, true);
+    return r.windows(MODE_HALVES, 0, nwin_of(wbits, true), wbits);
+  }
+  const int wbits = r.nvec * NWIN <= MAXLW ? pick_window_bits(ctx, r.n, r.nvec) : WBITS;
+  return r.windows(MODE_PLAIN, 0, nwin_of(wbits), wbits);
 }
 
 // f(std::integral_constant<decltype(V), V>{}) for the V among V0, Vs... that equals the runtime value `v` -- the last one for any other value:
@@ -740,7 +766,7 @@ void dispatch(decltype(V0) v, F&& f) {
 // debug read-back's ordering).  The slot's previous occupant (bucket reduce + copies on the reduce stream) must have drained; its error word was
 // re-zeroed at the end of that chain.  Stage events cost a few microseconds of queue time each, so only the ones the current timing level asks
 // for are recorded.
-int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t* d_scalars) {
+int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_scalars) {
   const bool merge = p.mode == MODE_TABLES, halves = p.mode == MODE_HALVES, wide = p.mode == MODE_WIDE;
   const bool bytes = byte_windows(p.nb);  // U8 / U16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
   const size_t merge_nb = merge || wide ? ctx->n_bases : 0;
@@ -888,8 +914,8 @@ int enqueue_sort(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s, const uint32_t*
     const uint32_t* part_hist = nullptr;
     const bool hist_useful = p.nb || ctx->fine_hist_min_n != FINE_BIG + 1 || p.n_entries / p.ncoarse * 4 > (size_t)FINE_BIG * 3 || ctx->skew_credit > 0;
     if (ctx->skew_credit > 0 && !p.nb) ctx->skew_credit--;
-    ctx->sort_fine_hist = p.n_entries >= ctx->fine_hist_min_n && hist_useful;
-    if (ctx->sort_fine_hist) {
+    p.fine_hist = p.n_entries >= ctx->fine_hist_min_n && hist_useful;
+    if (p.fine_hist) {
       hipLaunchKernelGGL(k_fine_hist, dim3(p.ncoarse, p.w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_fine, p.stride, ctx->d_coarse_ptr,
                          ctx->d_part_hist);
       AFTER_KERNEL(ctx, "k_fine_hist", st);
@@ -956,13 +982,13 @@ int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   // a synchronous call with nothing else in flight (msm_hip_run_*: the caller waits for this launch before it issues another): the stitch and
   // the bucket reduce follow the SMVP on the MAIN stream -- no cross-stream hand-off (an event wait costs ~10 us more than an in-stream kernel
   // boundary), and no next launch exists whose sort the separate stream would let overlap.  MSM_HIP_INLINE_REDUCE=0: always the reduce stream.
-  if (inline_reduce_on() && ctx->sync_call) {
+  if (inline_reduce_on() && p.sync) {
     bool others = false;
     for (const Slot& o : ctx->slot) others = others || (&o != &s && o.pending);
     if (!others) rs = st;
   }
   const bool to_host = !p.sums_dev;
-  uint32_t* wsums_out = to_host ? reinterpret_cast<uint32_t*>(s.d_wsums) : p.sums_dev;
+  uint32_t* wsums_out = static_cast<uint32_t*>(to_host ? s.d_wsums : p.sums_dev);
   uint32_t* d_err = reinterpret_cast<uint32_t*>(s.d_wsums + WSUM_BYTES);
   uint32_t* d_chunk_len = s.d_big_queue + BIGQ_CHUNK_LEN;
   const int tl = ctx->timing_level;
@@ -1039,7 +1065,6 @@ int enqueue_reduce(msm_hip_ctx* ctx, const LaunchPlan& p, Slot& s) {
   ctx->last_slot = (int)(&s - ctx->slot);
   ctx->last_logr = rowcol.logr;
   ctx->last_inline_reduce = rs == st;
-  ctx->last_fine_hist = ctx->sort_fine_hist;
   return MSM_HIP_OK;
 }
 
@@ -1166,9 +1191,10 @@ size_t batch_group(msm_hip_ctx* ctx, size_t n, size_t batch) {
   // (window size of a grouped launch: pick_window_bits with nvec > 1)
   // (wide tables: an MSM is 2^(C-16) local windows, and its launch leaves bit-plane sums for at most 24 of them: 24 / 12 / 3 / 1 MSMs at 16 / 17 / 19 / 20 bits)
   // (narrow scalars: their own windows, over the plain records whatever the base mode)
-  const int nb = narrow_bytes(ctx->scalar_format);
-  const size_t fit = nb ? (size_t)(narrow_max_windows(nb) / narrow_windows(byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, n, 2, false, nb), nb))
-                        : ctx->wide_bits ? (size_t)(24 / wide_vwin_of(ctx->wide_bits)) : ctx->precomputed ? (size_t)MAXLW : (size_t)(MAXLW / nwin_of(pick_window_bits(ctx, n, 2, ctx->endo), ctx->endo));
+  const LaunchRequest w = whole_msm_request(ctx, LaunchRequest(nullptr, n, 0, 2));  // (grouped: the window bits of nvec > 1)
+  const int per_msm = w.mode == MODE_TABLES ? 1 : w.mode == MODE_WIDE ? wide_vwin_of(w.wbits) : w.w_end;  // local windows
+  const int room = w.mode == MODE_NARROW ? narrow_max_windows(narrow_bytes(ctx->scalar_format)) : w.mode == MODE_WIDE ? 24 : MAXLW;
+  const size_t fit = (size_t)(room / per_msm);
   size_t g = n ? ((size_t)1 << 20) / n : 1;
   if (g > fit) g = fit;
   if (g > batch) g = batch;
@@ -1349,32 +1375,57 @@ int no_context_code() {
   return hipGetDeviceCount(&count) != hipSuccess || count <= 0 ? MSM_HIP_ERR_NO_DEVICE : MSM_HIP_ERR_INVALID_ARG;
 }
 
-// one launch into `slot` (the request as plan_launch takes it): plan, buffers, sort, reduce
-int launch_impl(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int w_begin, int w_end, int wbits, int slot,
-                void* window_sums_dev, LaunchMode mode = MODE_PLAIN, int v_begin = 0, int v_count = 0, bool sparse = false,
-                const uint32_t* indices = nullptr) {
+// one launch into the request's slot: plan, buffers, sort, reduce
+int launch_impl(msm_hip_ctx* ctx, const LaunchRequest& r) {
   LaunchPlan p;
-  int rc = plan_launch(ctx, p, mode, scalars_dev, n, nvec, w_begin, w_end, wbits, slot, window_sums_dev, v_begin, v_count, sparse, indices);
+  int rc = plan_launch(ctx, r, p);
   if (rc) return rc;
   ON_DEVICE(ctx);
-  Slot& s = ctx->slot[slot];
+  Slot& s = ctx->slot[r.slot];
   if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;  // its result was never collected (msm_hip_finish / msm_hip_slot_sync)
   if ((rc = setup_slot(ctx, s))) return rc;
   s.plan = p;
   s.parts = false;
-  s.to_host = window_sums_dev == nullptr;
-  if (n == 0) {  // identity window sums, nothing to compute
+  s.to_host = r.sums_dev == nullptr;
+  if (r.n == 0) {  // identity window sums, nothing to compute
     s.pending = true;
     s.timed = false;
     memset(s.h_wsums, 0, WSUM_BYTES + 4);
-    if (window_sums_dev) {
-      HIP_TRY(ctx, hipMemsetAsync(window_sums_dev, 0, (size_t)p.w_count * (p.pairs ? 2 : 1) * ctx->jb, ctx->reduce_stream[slot % NREDUCE]));
-      HIP_TRY(ctx, hipEventRecord(s.done, ctx->reduce_stream[slot % NREDUCE]));
+    if (r.sums_dev) {
+      HIP_TRY(ctx, hipMemsetAsync(r.sums_dev, 0, (size_t)p.w_count * (p.pairs ? 2 : 1) * ctx->jb, ctx->reduce_stream[r.slot % NREDUCE]));
+      HIP_TRY(ctx, hipEventRecord(s.done, ctx->reduce_stream[r.slot % NREDUCE]));
     }
     return MSM_HIP_OK;
   }
-  if ((rc = ensure_work(ctx, p, s)) || (rc = enqueue_sort(ctx, p, s, static_cast<const uint32_t*>(scalars_dev)))) return rc;
+  if ((rc = ensure_work(ctx, p, s)) || (rc = enqueue_sort(ctx, p, s, static_cast<const uint32_t*>(r.scalars)))) return rc;
   return enqueue_reduce(ctx, p, s);
+}
+
+// A dense request in the reference's 16 windows: whole MSMs whose sums stay in the slot (finish / finish_batch combines them) take the shape
+// whole_msm_request gives them -- the window size follows n --, everything else runs as the plain 16-bit windows asked for
+// (not with narrow scalars, the format of this launch: the window-sharding calls index the 16 windows of 32-byte scalars)
+int launch_dense(msm_hip_ctx* ctx, LaunchRequest r) {
+  if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
+  const bool whole = r.w_begin == 0 && r.w_end == NWIN && !r.sums_dev && r.nvec >= 1;
+  if (!whole && narrow_bytes(ctx->scalar_format)) return MSM_HIP_ERR_INVALID_ARG;
+  return launch_impl(ctx, whole ? whole_msm_request(ctx, r) : r);
+}
+
+// Sparse: one whole MSM of r.n entries in the mode the resident bases and the scalar format call for, as launch_dense picks it for as many points
+// (not on wide tables: out of scope)
+int launch_sparse(msm_hip_ctx* ctx, LaunchRequest r) {
+  if (!ctx) return no_context_code();
+  if (ctx->wide_bits) return MSM_HIP_ERR_INVALID_ARG;
+  r.sparse = true;
+  return launch_impl(ctx, whole_msm_request(ctx, r));
+}
+
+// a synchronous call: `launch` (launch_dense, launch_sparse, launch_host) of `r` into slot 0 with nothing pipelined behind it, and its finish at once
+int run_sync(msm_hip_ctx* ctx, int (*launch)(msm_hip_ctx*, LaunchRequest), LaunchRequest r, uint8_t* out_xyz) {
+  r.slot = 0;
+  r.sync = true;
+  const int rc = launch(ctx, r);
+  return rc ? rc : msm_hip_finish(ctx, 0, out_xyz);
 }
 }  // namespace
 
@@ -1382,35 +1433,14 @@ extern "C" {
 
 int msm_hip_launch_windows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int w_begin, int w_end,
                                               int slot, void* window_sums_dev) {
-  if (!ctx) return MSM_HIP_ERR_INVALID_ARG;
-  if (const int nb = narrow_bytes(ctx->scalar_format)) {
-    // narrow scalars (the format of this launch): whole MSMs only -- the window-sharding calls index the 16 windows of 32-byte scalars
-    if (w_begin != 0 || w_end != NWIN || window_sums_dev || nvec < 1) return MSM_HIP_ERR_INVALID_ARG;
-    if (n == 0) return launch_impl(ctx, scalars_dev, n, nvec, 0, NWIN, WBITS, slot, nullptr);  // (identity sums)
-    const int wbits = byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, n, nvec, false, nb);
-    return launch_impl(ctx, scalars_dev, n, nvec, 0, narrow_windows(wbits, nb), wbits, slot, nullptr, MODE_NARROW);
-  }
-  // whole MSMs whose sums stay in the slot (finish / finish_batch combines them): the window size follows n
-  if (w_begin == 0 && w_end == NWIN && window_sums_dev == nullptr && nvec >= 1 && ctx->wide_bits && n > 0)
-    return launch_impl(ctx, scalars_dev, n, nvec, 0, wide_tables_of(ctx->wide_bits), ctx->wide_bits, slot, nullptr, MODE_WIDE);  // wide fixed-base tables (one MSM per launch)
-  if (w_begin == 0 && w_end == NWIN && window_sums_dev == nullptr && nvec >= 1 && ctx->precomputed && n > 0)
-    return launch_impl(ctx, scalars_dev, n, nvec, 0, NWIN, WBITS, slot, nullptr, MODE_TABLES);  // fixed-base tables: one bucket set per vector
-  if (w_begin == 0 && w_end == NWIN && window_sums_dev == nullptr && nvec >= 1 && ctx->endo && n > 0 && nvec * nwin_of(16, true) <= MAXLW) {
-    const int wbits = pick_window_bits(ctx, n, nvec, true);  // endomorphism: half-length scalars over 2n points
-    return launch_impl(ctx, scalars_dev, n, nvec, 0, nwin_of(wbits, true), wbits, slot, nullptr, MODE_HALVES);
-  }
-  if (w_begin == 0 && w_end == NWIN && window_sums_dev == nullptr && nvec >= 1 && nvec * NWIN <= MAXLW) {
-    const int wbits = pick_window_bits(ctx, n, nvec);
-    return launch_impl(ctx, scalars_dev, n, nvec, 0, nwin_of(wbits), wbits, slot, nullptr);
-  }
-  return launch_impl(ctx, scalars_dev, n, nvec, w_begin, w_end, WBITS, slot, window_sums_dev);
+  return launch_dense(ctx, LaunchRequest(scalars_dev, n, slot, nvec, window_sums_dev).windows(MODE_PLAIN, w_begin, w_end));
 }
 
 int msm_hip_launch_half_windows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int hw_begin, int hw_end,
                                                    int slot, void* window_sums_dev) {
   if (!ctx || narrow_bytes(ctx->scalar_format)) return MSM_HIP_ERR_INVALID_ARG;
   if (!ctx->endo && ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;  // needs bases set with MSM_HIP_BASES_ENDOMORPHISM
-  return launch_impl(ctx, scalars_dev, n, nvec, hw_begin, hw_end, WBITS, slot, window_sums_dev, MODE_HALVES);
+  return launch_impl(ctx, LaunchRequest(scalars_dev, n, slot, nvec, window_sums_dev).windows(MODE_HALVES, hw_begin, hw_end));
 }
 
 int msm_hip_launch_vwindows_batch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int nvec, int v_begin, int v_end, int slot,
@@ -1418,7 +1448,7 @@ int msm_hip_launch_vwindows_batch_device(msm_hip_ctx* ctx, const void* scalars_d
   if (!ctx || narrow_bytes(ctx->scalar_format)) return MSM_HIP_ERR_INVALID_ARG;
   if (!ctx->wide_bits) return ctx->n_bases || !n ? MSM_HIP_ERR_INVALID_ARG : MSM_HIP_ERR_NO_BASES;  // needs bases set with MSM_HIP_BASES_PRECOMPUTE_WIDE
   if (v_begin < 0 || v_end <= v_begin) return MSM_HIP_ERR_INVALID_ARG;
-  return launch_impl(ctx, scalars_dev, n, nvec, 0, wide_tables_of(ctx->wide_bits), ctx->wide_bits, slot, sums_dev, MODE_WIDE, v_begin, v_end - v_begin);
+  return launch_impl(ctx, LaunchRequest(scalars_dev, n, slot, nvec, sums_dev).wide(ctx->wide_bits, v_begin, v_end - v_begin));
 }
 
 int msm_hip_launch_windows_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int w_begin, int w_end, int slot,
@@ -1426,36 +1456,19 @@ int msm_hip_launch_windows_device(msm_hip_ctx* ctx, const void* scalars_dev, siz
   return msm_hip_launch_windows_batch_device(ctx, scalars_dev, n, 1, w_begin, w_end, slot, window_sums_dev);
 }
 
-int msm_hip_launch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int slot) {
-  return msm_hip_launch_windows_device(ctx, scalars_dev, n, 0, NWIN, slot, nullptr);
-}
+int msm_hip_launch_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, int slot) { return launch_dense(ctx, LaunchRequest(scalars_dev, n, slot)); }
 
-// Sparse: one whole MSM of nnz entries in the mode the resident bases and the scalar format call for, as msm_hip_launch_device picks it for nnz
-// points (not on wide tables).
 int msm_hip_launch_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot) {
-  if (!ctx) return no_context_code();
-  if (ctx->wide_bits) return MSM_HIP_ERR_INVALID_ARG;  // (out of scope: sparse launches over wide tables)
-  if (nnz == 0) return launch_impl(ctx, scalars_dev, 0, 1, 0, NWIN, WBITS, slot, nullptr, MODE_PLAIN, 0, 0, true, indices_dev);  // (identity)
-  if (const int nb = narrow_bytes(ctx->scalar_format)) {  // narrow scalars: the plain records idx_j, as the dense narrow path
-    const int wbits = byte_windows(nb) ? BYTE_WBITS : pick_window_bits(ctx, nnz, 1, false, nb);
-    return launch_impl(ctx, scalars_dev, nnz, 1, 0, narrow_windows(wbits, nb), wbits, slot, nullptr, MODE_NARROW, 0, 0, true, indices_dev);
-  }
-  if (ctx->precomputed) return launch_impl(ctx, scalars_dev, nnz, 1, 0, NWIN, WBITS, slot, nullptr, MODE_TABLES, 0, 0, true, indices_dev);
-  if (ctx->endo) {
-    const int wbits = pick_window_bits(ctx, nnz, 1, true);
-    return launch_impl(ctx, scalars_dev, nnz, 1, 0, nwin_of(wbits, true), wbits, slot, nullptr, MODE_HALVES, 0, 0, true, indices_dev);
-  }
-  const int wbits = pick_window_bits(ctx, nnz, 1);
-  return launch_impl(ctx, scalars_dev, nnz, 1, 0, nwin_of(wbits), wbits, slot, nullptr, MODE_PLAIN, 0, 0, true, indices_dev);
+  LaunchRequest r(scalars_dev, nnz, slot);
+  r.indices = indices_dev;
+  return launch_sparse(ctx, r);
 }
 
 int msm_hip_run_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, uint8_t out_xyz[96]) {
   if (ctx && !out_xyz) return MSM_HIP_ERR_INVALID_ARG;
-  if (ctx) ctx->sync_call = true;
-  const int rc = msm_hip_launch_sparse_device(ctx, indices_dev, scalars_dev, nnz, 0);
-  if (ctx) ctx->sync_call = false;
-  if (rc) return rc;
-  return msm_hip_finish(ctx, 0, out_xyz);
+  LaunchRequest r(scalars_dev, nnz);
+  r.indices = indices_dev;
+  return run_sync(ctx, launch_sparse, r, out_xyz);
 }
 
 int msm_hip_slot_wait_stream(msm_hip_ctx* ctx, int slot, void* foreign_stream) {
@@ -1513,64 +1526,53 @@ int msm_hip_finish(msm_hip_ctx* ctx, int slot, uint8_t out_xyz[96]) {
 
 int msm_hip_run_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, uint8_t out_xyz[96]) {
   if (!out_xyz || !ctx) return MSM_HIP_ERR_INVALID_ARG;
-  ctx->sync_call = true;
-  int rc = msm_hip_launch_device(ctx, scalars_dev, n, 0);
-  ctx->sync_call = false;
-  if (rc) return rc;
-  return msm_hip_finish(ctx, 0, out_xyz);
+  return run_sync(ctx, launch_dense, LaunchRequest(scalars_dev, n), out_xyz);
 }
 
 }  // extern "C"
 
 namespace {
-// host scalars -> slot `s`'s own staging buffer (idle, since the slot is not pending; its capacity counts 32-byte scalars) on copy stream `cs`, so
-// that the copy overlaps whatever the main and reduce streams still hold of earlier launches (a caller that alternates two slots gets the copy of
-// MSM i+1 under the device work of MSM i); the main stream waits for it on the device.  From pageable memory the call returns when the bytes have
-// left the caller's buffer; from pinned memory (hipHostMalloc / hipHostRegister) at once -- the buffer must then stay untouched until finish /
-// slot_sync.  `count` scalars, of which `bytes` cross the link.
-int stage_host_scalars(msm_hip_ctx* ctx, Slot& s, hipStream_t cs, const void* scalars_host, size_t count, size_t bytes) {
-  const int rc = grow(ctx, s.cap_host_scalars, count, false, [&](size_t c) { return dev_alloc(ctx, s.d_host_scalars, c * 8); });
+// The host inputs of a launch -> slot `s`'s own staging buffer (the slot must be idle, so nothing is reading it; set up here on first use; its
+// capacity counts 32-byte scalars) on copy stream `cs` (null: the context's own, created on first use), so that the copy overlaps whatever the main
+// and reduce streams still hold of earlier launches (a caller that alternates two slots gets the copy of MSM i+1 under the device work of MSM i);
+// the main stream waits for it on the device.  From pageable memory the call returns when the bytes have left the caller's buffer; from pinned
+// memory (hipHostMalloc / hipHostRegister) at once -- the buffer must then stay untouched until finish / slot_sync.
+// `sbytes` bytes of scalars to s.d_host_scalars and, for a sparse launch, its nnz indices behind them (256-byte aligned), to *d_idx.
+int stage_host(msm_hip_ctx* ctx, Slot& s, const void* scalars_host, size_t sbytes, hipStream_t cs = nullptr, const uint32_t* indices_host = nullptr,
+               size_t nnz = 0, const uint32_t** d_idx = nullptr) {
+  if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
+  int rc = setup_slot(ctx, s);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(s.d_host_scalars, scalars_host, bytes, hipMemcpyHostToDevice, cs));
+  if (!cs) {
+    if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    cs = ctx->copy_stream;
+  }
+  const size_t off = (sbytes + 255) & ~(size_t)255, total = indices_host ? off + nnz * 4 : sbytes;
+  if ((rc = grow(ctx, s.cap_host_scalars, (total + 31) / 32, false, [&](size_t c) { return dev_alloc(ctx, s.d_host_scalars, c * 8); }))) return rc;
+  uint8_t* base = reinterpret_cast<uint8_t*>(s.d_host_scalars);
+  HIP_TRY(ctx, hipMemcpyAsync(base, scalars_host, sbytes, hipMemcpyHostToDevice, cs));
+  if (indices_host) {
+    HIP_TRY(ctx, hipMemcpyAsync(base + off, indices_host, nnz * 4, hipMemcpyHostToDevice, cs));
+    *d_idx = reinterpret_cast<const uint32_t*>(base + off);
+  }
   HIP_TRY(ctx, hipEventRecord(s.staged, cs));
   HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
   return MSM_HIP_OK;
 }
 
-// host scalars -> the slot's own staging buffer -> windows [w_begin, w_end) of one MSM into `slot`
-// (windows in units of the reference's 16-bit windows; `auto_bits`: a whole MSM whose window size follows n)
-int launch_host_windows(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, int w_begin, int w_end, int slot, void* window_sums_dev,
-                        bool auto_bits = false) {
-  int rc = check_run_args(ctx, scalars_host, n);
+// one whole MSM from host scalars (r.scalars; narrow formats cross the link as they are, never widened on the host): staged, then as launch_dense
+int launch_host(msm_hip_ctx* ctx, LaunchRequest r) {
+  int rc = check_run_args(ctx, r.scalars, r.n);
   if (rc) return rc;
-  if (slot < 0 || slot >= NSLOT) return MSM_HIP_ERR_INVALID_ARG;
-  // narrow scalars: n x 1 .. 8 bytes cross the link as they are (never widened on the host); whole MSMs only
-  const int nb = narrow_bytes(ctx->scalar_format);
-  if (nb && !auto_bits) return MSM_HIP_ERR_INVALID_ARG;
+  if (r.slot < 0 || r.slot >= NSLOT) return MSM_HIP_ERR_INVALID_ARG;
   ON_DEVICE(ctx);
-  Slot& s = ctx->slot[slot];
-  if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
-  if (n == 0) return launch_impl(ctx, scalars_host, 0, 1, w_begin, w_end, WBITS, slot, window_sums_dev);
-  if ((rc = setup_slot(ctx, s))) return rc;
-  if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  if ((rc = stage_host_scalars(ctx, s, ctx->copy_stream, scalars_host, n, n * (nb ? (size_t)nb : 32)))) return rc;
-  if (auto_bits) return msm_hip_launch_windows_batch_device(ctx, s.d_host_scalars, n, 1, 0, NWIN, slot, nullptr);
-  return launch_impl(ctx, s.d_host_scalars, n, 1, w_begin, w_end, WBITS, slot, window_sums_dev);
-}
-
-// a sparse launch's host inputs -> slot `s`'s staging buffer, in one piece: the nnz scalars of `sbytes` bytes, then (256-byte aligned) the nnz
-// indices; returns the device address of the indices.  Ordered as stage_host_scalars.
-int stage_host_sparse(msm_hip_ctx* ctx, Slot& s, const uint32_t* indices_host, const void* scalars_host, size_t nnz, size_t sbytes, const uint32_t*& d_idx) {
-  const size_t off = (nnz * sbytes + 255) & ~(size_t)255, total = off + nnz * 4;
-  const int rc = grow(ctx, s.cap_host_scalars, (total + 31) / 32, false, [&](size_t c) { return dev_alloc(ctx, s.d_host_scalars, c * 8); });
-  if (rc) return rc;
-  uint8_t* base = reinterpret_cast<uint8_t*>(s.d_host_scalars);
-  HIP_TRY(ctx, hipMemcpyAsync(base, scalars_host, nnz * sbytes, hipMemcpyHostToDevice, ctx->copy_stream));
-  HIP_TRY(ctx, hipMemcpyAsync(base + off, indices_host, nnz * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-  HIP_TRY(ctx, hipEventRecord(s.staged, ctx->copy_stream));
-  HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, s.staged, 0));
-  d_idx = reinterpret_cast<const uint32_t*>(base + off);
-  return MSM_HIP_OK;
+  Slot& s = ctx->slot[r.slot];
+  if (r.n) {
+    const int nb = narrow_bytes(ctx->scalar_format);
+    if ((rc = stage_host(ctx, s, r.scalars, r.n * (nb ? (size_t)nb : 32)))) return rc;
+    r.scalars = s.d_host_scalars;
+  }
+  return launch_dense(ctx, r);
 }
 
 // first point of part k of n points split into `parts` ranges (the first n % parts ranges take one more)
@@ -1579,9 +1581,7 @@ inline size_t part_first(size_t n, int parts, int k) { return n / parts * k + st
 
 extern "C" {
 
-int msm_hip_launch(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, int slot) {
-  return launch_host_windows(ctx, scalars_host, n, 0, NWIN, slot, nullptr, true);
-}
+int msm_hip_launch(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, int slot) { return launch_host(ctx, LaunchRequest(scalars_host, n, slot)); }
 
 int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t out_xyz[96]) {
   if (!out_xyz || !ctx) return MSM_HIP_ERR_INVALID_ARG;
@@ -1599,9 +1599,9 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
     int rc = MSM_HIP_OK, launched = 0;
     for (int k = 0; k < parts && !rc; k++) {
       const size_t first = part_first(n, parts, k), next = part_first(n, parts, k + 1);
-      ctx->launch_base_off = first;
-      rc = msm_hip_launch(ctx, scalars_host + first * 32, next - first, k);
-      ctx->launch_base_off = 0;
+      LaunchRequest r(scalars_host + first * 32, next - first, k);
+      r.base_off = first;
+      rc = launch_host(ctx, r);
       if (!rc) launched++;
     }
     for (int k = 0; k < launched; k++) {
@@ -1611,11 +1611,7 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
     if (!rc && !ctx->ops->combine_windows(sums, parts, 0, out_xyz)) rc = MSM_HIP_ERR_NONCANONICAL;  // (window_bits = 0: the plain sum)
     return rc;
   }
-  ctx->sync_call = true;
-  int rc = msm_hip_launch(ctx, scalars_host, n, 0);
-  ctx->sync_call = false;
-  if (rc) return rc;
-  return msm_hip_finish(ctx, 0, out_xyz);
+  return run_sync(ctx, launch_host, LaunchRequest(scalars_host, n), out_xyz);
 }
 
 // Host inputs of a sparse MSM: the indices are checked here, before anything is enqueued; one upload of both arrays into slot 0's staging buffer
@@ -1627,15 +1623,11 @@ int msm_hip_run_sparse(msm_hip_ctx* ctx, const uint32_t* indices_host, const uin
   if (ctx->n_bases == 0) return MSM_HIP_ERR_NO_BASES;
   for (size_t j = 0; j < nnz; j++)
     if (indices_host[j] >= ctx->n_bases) return MSM_HIP_ERR_INVALID_ARG;
-  Slot& s = ctx->slot[0];
-  if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
   ON_DEVICE(ctx);
-  int rc = setup_slot(ctx, s);
-  if (rc) return rc;
-  if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+  Slot& s = ctx->slot[0];
   const int nb = narrow_bytes(ctx->scalar_format);
   const uint32_t* d_idx = nullptr;
-  if ((rc = stage_host_sparse(ctx, s, indices_host, scalars_host, nnz, nb ? (size_t)nb : 32, d_idx))) return rc;
+  if (const int rc = stage_host(ctx, s, scalars_host, nnz * (nb ? (size_t)nb : 32), nullptr, indices_host, nnz, &d_idx)) return rc;
   return msm_hip_run_sparse_device(ctx, d_idx, s.d_host_scalars, nnz, out_xyz);
 }
 
@@ -1779,26 +1771,23 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
   int rc = reserve_bases(ctx, n, flags);  // (waits for the main stream: nothing is reading the old bases)
   if (rc) return rc;
   Slot& s = ctx->slot[0];
-  if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
-  if ((rc = setup_slot(ctx, s))) return rc;
   if (!ctx->bases_ready) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->bases_ready, hipEventDisableTiming));
   // 1. the scalars, and their sort
-  if ((rc = stage_host_scalars(ctx, s, cs, scalars_host, n, n * 32))) return rc;
+  if ((rc = stage_host(ctx, s, scalars_host, n * 32, cs))) return rc;
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_err, 0, 4, cs));  // (ahead of every chunk's copy, hence of every conversion)
-  ctx->n_bases = n;  // (what the launch checks n against; the records themselves follow below)
+  ctx->n_bases = n;  // (what the launch checks n against, and with `endo` what shapes it; the records themselves follow below)
   ctx->endo = endo;
-  const int wbits = pick_window_bits(ctx, n, 1, endo);
-  ctx->sync_call = true;
+  LaunchRequest req = whole_msm_request(ctx, LaunchRequest(s.d_host_scalars, n));
+  req.sync = true;
   LaunchPlan p;
   auto sort = [&]() -> int {
-    int r = plan_launch(ctx, p, endo ? MODE_HALVES : MODE_PLAIN, s.d_host_scalars, n, 1, 0, nwin_of(wbits, endo), wbits, 0, nullptr, 0, 0);
+    int r = plan_launch(ctx, req, p);
     if (!r) r = ensure_work(ctx, p, s);
     if (!r) r = enqueue_sort(ctx, p, s, s.d_host_scalars);
     if (!r) HIP_TRY(ctx, hipGetLastError());
     return r;
   };
   if ((rc = sort())) {
-    ctx->sync_call = false;
     ctx->n_bases = 0;
     return rc;
   }
@@ -1828,7 +1817,6 @@ int oneshot_enqueue(msm_hip_ctx* ctx, hipStream_t cs, const uint8_t* xy_host, co
   //    and the result is discarded)
   *queued = true;
   rc = enqueue_reduce(ctx, p, s);
-  ctx->sync_call = false;
   *he_out = he;
   return rc;
 }
@@ -2094,7 +2082,7 @@ int msm_hip_test_env_report(const msm_hip_ctx* ctx, char* out, size_t cap) {
     put("last_wide_top_shift", ctx->last.mode == MODE_WIDE ? wide_top_shift(ctx->curve, ctx->last.wide_bits) : 0);
     put("last_logr", ctx->last_logr);
     put("last_inline_reduce", ctx->last_inline_reduce);
-    put("last_fine_hist", ctx->last_fine_hist);
+    put("last_fine_hist", ctx->last.fine_hist);
     put("last_identity_mask", ctx->last.mask);
   }
   return fits ? (int)len : MSM_HIP_ERR_INVALID_ARG;

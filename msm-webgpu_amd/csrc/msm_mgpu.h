@@ -120,16 +120,11 @@ int mgpu_enqueue_on_device(msm_hip_mgpu* m, int d, int k, const void* scalars, b
   if (host_scalars) {  // all vectors of the launch into the slot's staging buffer, on the copy stream
     ON_DEVICE(ctx);
     Slot& s = ctx->slot[k];
-    if (s.pending) return MSM_HIP_ERR_SLOT_BUSY;
-    if ((rc = setup_slot(ctx, s))) return rc;
-    if (!ctx->copy_stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    const size_t count = (size_t)nvec * n;
-    if ((rc = stage_host_scalars(ctx, s, ctx->copy_stream, scalars, count, count * 32))) return rc;
+    if ((rc = stage_host(ctx, s, scalars, (size_t)nvec * n * 32))) return rc;
     dev = s.d_host_scalars;
   }
-  void* sums = m->rccl ? ms.d_send[d] : nullptr;  // host gather: the sums leave through the context slot's pinned buffer
-  if (ms.wide_bits) rc = launch_impl(ctx, dev, n, nvec, 0, wide_tables_of(ms.wide_bits), ms.wide_bits, k, sums, MODE_WIDE, b, e - b);
-  else rc = launch_impl(ctx, dev, n, nvec, b, e, WBITS, k, sums, halves ? MODE_HALVES : MODE_PLAIN);
+  LaunchRequest r(dev, n, k, nvec, m->rccl ? ms.d_send[d] : nullptr);  // (host gather: the sums leave through the context slot's pinned buffer)
+  rc = launch_impl(ctx, ms.wide_bits ? r.wide(ms.wide_bits, b, e - b) : r.windows(halves ? MODE_HALVES : MODE_PLAIN, b, e));
   launched = rc == MSM_HIP_OK;
   return rc;
 }
