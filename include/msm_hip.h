@@ -190,6 +190,19 @@ int msm_hip_set_bases_device(msm_hip_ctx* ctx, const void* xy_dev, size_t n, uin
 #define MSM_HIP_SCALARS_U16 3u
 #define MSM_HIP_SCALARS_U32 4u
 #define MSM_HIP_SCALARS_U64 5u
+/* Signed and 128-bit narrow scalars (added within ABI version 7).  MSM_HIP_SCALAR_U128: n x 16 bytes of unsigned little-endian integers -- challenges,
+ * random-linear-combination weights, products of two 64-bit values.  MSM_HIP_SCALAR_SIGNED is a flag: OR-ed onto MSM_HIP_SCALARS_U8 .. U64 or
+ * MSM_HIP_SCALAR_U128 it makes the same bytes two's-complement integers -- I8 .. I64 are 18 .. 21, I128 is 24.  The result is the sum of
+ * v_i * P_i with v_i as an integer: a negative v_i contributes -(|v_i| * P_i), which for bases of order r is what the 32-byte scalar v_i mod r
+ * gives.  |v| <= 2^127 < r on every curve, so no value is rejected; the minimum, -2^(8 w - 1), is legal.  The device recodes the magnitude
+ * with the windows of the width (I8 / I16: one window per byte of |v|; I32 / I64: 3 / 5 signed 16-bit windows; U128 / I128: 9, or 10 / 11 at 14 /
+ * 12 bits) and carries the sign as bit 31 of every sort entry of that value, where the endomorphism's negative halves carry theirs.
+ * Everything said above of U8 .. U64 holds: the whole-MSM entry points and the three sparse calls only (the window-sharding ones return
+ * MSM_HIP_ERR_INVALID_ARG), device scalars aligned to their width (16 bytes for the 128-bit formats), a vector's stride n x width bytes, the
+ * plain records in every base mode, MSM_HIP_BASES_ZERO_IS_IDENTITY, every curve, the format read by each launch.  The flag is not combinable
+ * with CANONICAL or MONT256, and every value not named here stays MSM_HIP_ERR_INVALID_ARG. */
+#define MSM_HIP_SCALAR_SIGNED 16u   /* flag: OR onto MSM_HIP_SCALARS_U8 .. U64 or MSM_HIP_SCALAR_U128 */
+#define MSM_HIP_SCALAR_U128   8u    /* n x 16 B unsigned little-endian */
 int msm_hip_set_scalar_format(msm_hip_ctx* ctx, uint32_t format);
 
 /* ---- window size (the reference hard-codes chunk_size = 16 for n >= 2^16, src/cuzk/msm.rs:79-82).

@@ -109,11 +109,19 @@ class MsmContext {
   void scalars_mont256(bool on) {
     check(msm_hip_set_scalar_format(ctx_, on ? MSM_HIP_SCALARS_MONT256 : MSM_HIP_SCALARS_CANONICAL), "msm_hip_set_scalar_format");
   }
-  // narrow scalars: 1 / 2 / 4 / 8 bytes per scalar (MSM_HIP_SCALARS_U8 .. U64; msm_bytes then takes n x bytes), 32 = the canonical 32-byte form
+  // narrow scalars: 1 / 2 / 4 / 8 / 16 bytes per scalar (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128; msm_bytes then takes n x bytes), 32 = the
+  // canonical 32-byte form
   void set_scalar_width(int bytes) {
     const uint32_t f = bytes == 1 ? MSM_HIP_SCALARS_U8 : bytes == 2 ? MSM_HIP_SCALARS_U16 : bytes == 4 ? MSM_HIP_SCALARS_U32
-                     : bytes == 8 ? MSM_HIP_SCALARS_U64 : bytes == 32 ? MSM_HIP_SCALARS_CANONICAL : 0xffffffffu;
+                     : bytes == 8 ? MSM_HIP_SCALARS_U64 : bytes == 16 ? MSM_HIP_SCALAR_U128 : bytes == 32 ? MSM_HIP_SCALARS_CANONICAL : 0xffffffffu;
     check(msm_hip_set_scalar_format(ctx_, f), "msm_hip_set_scalar_format");
+  }
+  // ... or, is_signed, the same narrow widths as two's-complement integers (MSM_HIP_SCALAR_SIGNED: I8 .. I64, I128); 32 bytes cannot be signed
+  void set_scalar_width(int bytes, bool is_signed) {
+    if (!is_signed) return set_scalar_width(bytes);
+    const uint32_t f = bytes == 1 ? MSM_HIP_SCALARS_U8 : bytes == 2 ? MSM_HIP_SCALARS_U16 : bytes == 4 ? MSM_HIP_SCALARS_U32
+                     : bytes == 8 ? MSM_HIP_SCALARS_U64 : bytes == 16 ? MSM_HIP_SCALAR_U128 : 0xffffffffu;
+    check(msm_hip_set_scalar_format(ctx_, f == 0xffffffffu ? f : f | MSM_HIP_SCALAR_SIGNED), "msm_hip_set_scalar_format");
   }
   G1 msm_bytes(const uint8_t* scalars, size_t n) {
     G1 r;

@@ -247,19 +247,29 @@ def _as_device_u8(t, row, what):
 # narrow scalar formats (include/msm_hip.h: MSM_HIP_SCALARS_U8 .. U64): bytes per scalar -> format value, and the unsigned dtype of that width
 SCALAR_WIDTHS = {1: 2, 2: 3, 4: 4, 8: 5}
 _UNSIGNED_OF_WIDTH = {1: "uint8", 2: "uint16", 4: "uint32", 8: "uint64"}
+# signed and 128-bit narrow formats (MSM_HIP_SCALAR_SIGNED, MSM_HIP_SCALAR_U128): the flag, the 16-byte format, and every (width, signed) -> format value
+SCALAR_SIGNED = 16
+SCALAR_U128 = 8
+SCALAR_FORMATS = {(w, sg): (SCALAR_U128 if w == 16 else SCALAR_WIDTHS[w]) | (SCALAR_SIGNED if sg else 0) for w in (1, 2, 4, 8, 16) for sg in (False, True)}
+_SIGNED_OF_WIDTH = {1: "int8", 2: "int16", 4: "int32", 8: "int64"}
 
 
-def _as_device_scalars(t, width, what="scalars"):
+def _as_device_scalars(t, width, what="scalars", signed=False):
     """A CUDA tensor of scalars of `width` bytes -> (uint8 view, number of scalars).  32: the 32-byte forms (uint8 only, as always); a narrow
-    width: uint8 (a multiple of `width` bytes) or the unsigned dtype of that width, read as its little-endian bytes."""
+    width: uint8 (a multiple of `width` bytes) or the integer dtype of that width and of the format's signedness, read as its little-endian
+    bytes.  16 bytes: uint8 only (torch has no 128-bit dtype)."""
     if width == 32:
         return _as_device_u8(t, 32, what)
     if not (isinstance(t, torch.Tensor) and t.is_cuda):
         raise TypeError("%s must be a CUDA(HIP) tensor" % what)
     if t.dtype != torch.uint8:
-        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype.is_signed or t.dtype == torch.bool:
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise TypeError("%s: %s is not an integer dtype" % (what, t.dtype))
+        if not signed and t.dtype.is_signed:
             raise TypeError("%s: %s is not an unsigned integer dtype (narrow scalars are unsigned)" % (what, t.dtype))
-        if t.dtype != getattr(torch, _UNSIGNED_OF_WIDTH[width]):
+        if signed and not t.dtype.is_signed:
+            raise TypeError("%s: %s is not a signed integer dtype (the scalar format is signed; uint8 rows are taken as bytes)" % (what, t.dtype))
+        if t.dtype != getattr(torch, (_SIGNED_OF_WIDTH if signed else _UNSIGNED_OF_WIDTH).get(width, "uint8")):
             raise ValueError("%s: dtype %s does not hold %d-byte scalars" % (what, t.dtype, width))
         if not t.is_contiguous():
             raise ValueError("%s must be contiguous" % what)
@@ -308,7 +318,8 @@ class MsmContext:
         self.device = int(device)
         self.n_bases = 0
         self.wide_bits_choice = 0
-        self.scalar_width = 32  # bytes per scalar of the following runs (set_scalar_format)
+        self.scalar_width = 32  # bytes per scalar of the following runs (set_scalar_format) ...
+        self.scalar_signed = False  # ... and whether they are two's-complement integers
         self._keepalive = {}  # slot -> tensors the slot's launch still reads / writes; released when the slot is collected
 
     def _order_after_torch(self, *tensors):
@@ -370,10 +381,10 @@ class MsmContext:
 
     def msm(self, scalars):
         """sum_i scalars[i] * bases[i] -> G1.  scalars: bytes (n x 32 B; n x width B under a narrow format) or a CUDA tensor (uint8; under a
-        narrow format also the unsigned dtype of its width)."""
+        narrow format also the integer dtype of its width: unsigned, or signed under a signed format)."""
         out = C.create_string_buffer(self.jb)
         if isinstance(scalars, torch.Tensor) and scalars.is_cuda:
-            t, n = _as_device_scalars(scalars, self.scalar_width)
+            t, n = _as_device_scalars(scalars, self.scalar_width, signed=self.scalar_signed)
             self._order_after_torch(t)
             _check(lib().msm_hip_run_device(self._h, t.data_ptr(), n, out), "msm_hip_run_device")
         else:
@@ -383,7 +394,7 @@ class MsmContext:
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under
-        a narrow format, where the unsigned dtype of that width is accepted too -- or host bytes of the same layout -> [G1, ...]."""
+        a narrow format, where the integer dtype of that width is accepted too -- or host bytes of the same layout -> [G1, ...]."""
         w = self.scalar_width
         if isinstance(scalars_dev, (bytes, bytearray)):
             b = bytes(scalars_dev)
@@ -393,7 +404,7 @@ class MsmContext:
             out = C.create_string_buffer(self.jb * batch)
             _check(lib().msm_hip_run_batch(self._h, b, n, batch, out), "msm_hip_run_batch")
             return [G1(out.raw[self.jb * k:self.jb * (k + 1)], self.modulus) for k in range(batch)]
-        t, rows = _as_device_scalars(scalars_dev, w)
+        t, rows = _as_device_scalars(scalars_dev, w, signed=self.scalar_signed)
         if n <= 0 or rows % n:
             raise ValueError("scalars must hold a whole number of n-element vectors")
         batch = rows // n
@@ -410,7 +421,7 @@ class MsmContext:
         out = C.create_string_buffer(self.jb)
         if isinstance(scalars, torch.Tensor) and scalars.is_cuda:
             ix = _device_indices(indices)
-            t, nnz = _as_device_scalars(scalars, self.scalar_width)
+            t, nnz = _as_device_scalars(scalars, self.scalar_width, signed=self.scalar_signed)
             if ix.numel() != nnz:
                 raise ValueError("%d indices for %d scalars" % (ix.numel(), nnz))
             self._order_after_torch(t)
@@ -427,7 +438,7 @@ class MsmContext:
         """msm_sparse's device work into a result slot (0..3), returning at once (msm_hip_launch_sparse_device); finish(slot) collects it.
         Device tensors only."""
         ix = _device_indices(indices)
-        t, nnz = _as_device_scalars(scalars, self.scalar_width)
+        t, nnz = _as_device_scalars(scalars, self.scalar_width, signed=self.scalar_signed)
         if ix.numel() != nnz:
             raise ValueError("%d indices for %d scalars" % (ix.numel(), nnz))
         self._order_after_torch(t)
@@ -436,7 +447,7 @@ class MsmContext:
 
     def launch(self, scalars_dev, slot=0):
         """Enqueue the device work of one MSM into a result slot (0..3) and return at once."""
-        t, n = _as_device_scalars(scalars_dev, self.scalar_width)
+        t, n = _as_device_scalars(scalars_dev, self.scalar_width, signed=self.scalar_signed)
         self._order_after_torch(t)
         _check(lib().msm_hip_launch_device(self._h, t.data_ptr(), n, slot), "msm_hip_launch_device")
         self._keepalive[slot] = t
@@ -654,17 +665,21 @@ class MsmContext:
         return lib().msm_hip_uses_endomorphism(self._h) == 1
 
     # -- stage read-back (parity tests)
-    def set_scalar_format(self, mont256=False, width=32):
+    def set_scalar_format(self, mont256=False, width=32, signed=False):
         """mont256 False: canonical little-endian scalars (default); True: s * 2^256 mod r words (R = 2^256 Montgomery limbs).
-        width: bytes per scalar -- 32, or 1 / 2 / 4 / 8 for narrow unsigned scalars (MSM_HIP_SCALARS_U8 .. U64: witness columns of small
-        values; whole-MSM calls only).  A narrow width cannot be combined with mont256."""
-        if width not in (1, 2, 4, 8, 32):
-            raise ValueError("scalar width must be 1, 2, 4, 8 or 32 bytes, not %r" % (width,))
+        width: bytes per scalar -- 32, or 1 / 2 / 4 / 8 / 16 for narrow scalars (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128: witness columns
+        of small values, 128-bit challenges; whole-MSM calls only).  signed: the narrow values are two's-complement integers
+        (MSM_HIP_SCALAR_SIGNED: I8 .. I128), a negative one contributing -(|v| * P).  A narrow width cannot be combined with mont256, and only
+        a narrow width can be signed."""
+        if width not in (1, 2, 4, 8, 16, 32):
+            raise ValueError("scalar width must be 1, 2, 4, 8, 16 or 32 bytes, not %r" % (width,))
         if mont256 and width != 32:
             raise ValueError("mont256 scalars are 32 bytes wide")
-        fmt = SCALAR_WIDTHS[width] if width != 32 else (1 if mont256 else 0)
+        if signed and width == 32:
+            raise ValueError("signed scalars are 1, 2, 4, 8 or 16 bytes wide")
+        fmt = SCALAR_FORMATS[(width, bool(signed))] if width != 32 else (1 if mont256 else 0)
         _check(lib().msm_hip_set_scalar_format(self._h, fmt), "msm_hip_set_scalar_format")
-        self.scalar_width = width
+        self.scalar_width, self.scalar_signed = width, bool(signed)
 
     def skew_credit(self):
         """launches left that run k_fine_hist because an earlier 32-byte launch met a huge coarse bin (test hook)"""

@@ -63,15 +63,27 @@ enum LaunchMode {
   MODE_HALVES = 2,  // endomorphism: 127-bit halves k1, k2 over the 2n points P_i, phi(P_i) (MSM_HIP_BASES_ENDOMORPHISM, csrc/glv.h)
   MODE_WIDE = 3,    // wide fixed-base tables: ceil(255 / C) digits of C = 16 .. 20 bits per scalar, one bucket set of 2^(C-1) slots run as 2^(C-16) virtual windows of 2^15
                     // (MSM_HIP_BASES_PRECOMPUTE_WIDE; msm_kernels.h: k_count_wide)
-  MODE_NARROW = 4,  // narrow scalars (MSM_HIP_SCALARS_U8 .. U64): the narrow_windows(C, bytes) windows of n x 1 .. 8 B unsigned integers over the
-                    // plain records 0 .. n-1, which every base mode keeps (msm_kernels.h: k_count<C, SW, false, NB>)
+  MODE_NARROW = 4,  // narrow scalars (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128, and their MSM_HIP_SCALAR_SIGNED forms): the
+                    // narrow_windows(C, bytes) windows of n x 1 .. 16 B integers over the plain records 0 .. n-1, which every base mode keeps
+                    // (msm_kernels.h: k_count<C, SW, false, NB>)
 };
 
-// bytes of a narrow scalar format (MSM_HIP_SCALARS_U8 .. U64); 0 for the 32-byte formats
-inline int narrow_bytes(uint32_t format) { return format >= MSM_HIP_SCALARS_U8 && format <= MSM_HIP_SCALARS_U64 ? 1 << (format - MSM_HIP_SCALARS_U8) : 0; }
-// U8 / U16 run as byte windows (one per byte, unsigned digits 1 .. 255, a one-level counting sort: msm_kernels.h, k_byte_count ...) on the 12-bit
-// bucket grid -- the smallest the reduce kernels have, 2^11 slots of which 255 can fill; U32 / U64 as truncated signed C-bit windows (C from n)
-// through the two-level sort
+// bytes of a narrow scalar format (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128, each with or without MSM_HIP_SCALAR_SIGNED); 0 for the
+// 32-byte formats and for every value that is no format at all (the flag alone or on a 32-byte format, unused numbers)
+inline int narrow_bytes(uint32_t format) {
+  switch (format & ~MSM_HIP_SCALAR_SIGNED) {
+    case MSM_HIP_SCALARS_U8: return 1;
+    case MSM_HIP_SCALARS_U16: return 2;
+    case MSM_HIP_SCALARS_U32: return 4;
+    case MSM_HIP_SCALARS_U64: return 8;
+    case MSM_HIP_SCALAR_U128: return 16;
+    default: return 0;
+  }
+}
+inline bool narrow_signed(uint32_t format) { return narrow_bytes(format) && (format & MSM_HIP_SCALAR_SIGNED); }  // two's-complement values
+// U8 / U16 (I8 / I16) run as byte windows (one per byte of the magnitude, digits 1 .. 255, a one-level counting sort: msm_kernels.h, k_byte_count
+// ...) on the 12-bit bucket grid -- the smallest the reduce kernels have, 2^11 slots of which 255 can fill; the wider formats as truncated signed
+// C-bit windows (C from n) through the two-level sort
 inline bool byte_windows(int nb) { return nb == 1 || nb == 2; }
 constexpr int BYTE_WBITS = 12;
 inline int narrow_windows(int wbits, int nb) { return byte_windows(nb) ? nb : narrow_nwin_of(wbits, nb); }
@@ -121,7 +133,9 @@ struct LaunchRequest {
 // What a launch is made of: its request as plan_launch settled it, and everything decided once from that -- read by the launch's buffer sizing
 // (ensure_work), both stages of its enqueue (enqueue_sort, enqueue_reduce), the host finish and the stage read-back hooks
 struct LaunchPlan : LaunchRequest {   // (settled: wbits = the window bits of everything behind the recode, 16 for MODE_WIDE; v_count = the virtual windows run)
-  int nb = 0;                         // MODE_NARROW: bytes per scalar
+  int nb = 0;                         // MODE_NARROW: bytes per scalar ...
+  bool nb_signed = false;             // ... and whether they are two's-complement (MSM_HIP_SCALAR_SIGNED)
+  int nb_kernel() const { return nb_signed ? -nb : nb; }  // the format as the scalar-loading kernels name it (msm_kernels.h: narrow_width)
   int w_count_vec = 0;                // windows [w_begin, w_begin + w_count_vec) of every vector, in the request's window bits (MODE_WIDE: the T digits)
   int wide_bits = 0;                  // MODE_WIDE: the tables' digit width
   bool pairs = false;                 // MODE_WIDE, a share of the virtual windows: the launch leaves (window sum, plain total) record pairs
@@ -238,7 +252,7 @@ struct msm_hip_ctx {
   uint32_t* d_scalar_conv = nullptr;  // canonical copies of scalars handed over in R = 2^256 Montgomery form (one launch's worth); behind them, a
                                       // masked launch's copy of its scalars with those of identity bases zeroed (k_mask_identity)
   size_t cap_scalar_conv = 0;         // in 32-byte scalars
-  uint32_t scalar_format = 0;         // MSM_HIP_SCALARS_CANONICAL / MSM_HIP_SCALARS_MONT256 / MSM_HIP_SCALARS_U8 .. U64 (read by each launch)
+  uint32_t scalar_format = 0;         // MSM_HIP_SCALARS_CANONICAL / MONT256 / U8 .. U64 / MSM_HIP_SCALAR_U128 [| MSM_HIP_SCALAR_SIGNED] (read by each launch)
   int window_bits = 0;                // 0: chosen from n for whole-MSM launches (pick_window_bits); else 12 / 14 / 16
   uint32_t* d_part_hist = nullptr;  // [MAXLW][128][FINE_SPLIT][256] sub-range histograms of huge coarse bins (k_fine_hist), on first use
   size_t fine_hist_min_n = FINE_BIG + 1;  // any n that can produce a coarse bin beyond FINE_BIG: run k_fine_hist (3 us when none does)
@@ -689,6 +703,7 @@ int plan_launch(msm_hip_ctx* ctx, const LaunchRequest& r, LaunchPlan& p) {
   p = LaunchPlan{};
   static_cast<LaunchRequest&>(p) = r;
   p.nb = nb;
+  p.nb_signed = nb && narrow_signed(ctx->scalar_format);
   p.w_count_vec = w_count_vec;
   p.wide_bits = wide ? ctx->wide_bits : 0;
   p.v_count = v_count;
@@ -768,7 +783,7 @@ void dispatch(decltype(V0) v, F&& f) {
 // for are recorded.
 int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_scalars) {
   const bool merge = p.mode == MODE_TABLES, halves = p.mode == MODE_HALVES, wide = p.mode == MODE_WIDE;
-  const bool bytes = byte_windows(p.nb);  // U8 / U16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
+  const bool bytes = byte_windows(p.nb);  // U8 / U16, I8 / I16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
   const size_t merge_nb = merge || wide ? ctx->n_bases : 0;
   hipStream_t st = ctx->stream;
   const dim3 grid(p.tiles, p.nvec), block(256);
@@ -782,7 +797,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   const bool mont = ctx->scalar_format == MSM_HIP_SCALARS_MONT256 && !p.nb;
   if (p.mask) {  // identity records among the bases: a copy of the scalars with theirs zeroed, before anything validates or converts them (stage 0)
     uint8_t* masked = reinterpret_cast<uint8_t*>(ctx->d_scalar_conv) + (mont ? (size_t)p.nvec * p.n * 32 : 0);  // (behind the canonical copies)
-    dispatch<32, 8, 4, 2, 1>(p.nb ? p.nb : 32, [&](auto w) {
+    dispatch<32, 16, 8, 4, 2, 1>(p.nb ? p.nb : 32, [&](auto w) {  // (by width: zeroing does not ask about the sign)
       hipLaunchKernelGGL(k_mask_identity<decltype(w)::value>, dim3(blocks_for(p.n, 256), p.nvec), dim3(256), 0, st, (const uint8_t*)d_scalars, masked, p.n,
                          p.base_off, (const uint64_t*)ctx->d_id_bits, (uint32_t)ctx->n_bases, p.sparse ? p.indices : (const uint32_t*)nullptr);
     });
@@ -797,8 +812,18 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   }
   const unsigned gpos_bytes = (unsigned)(merge ? p.nvec : p.nvec * p.w_count_vec) * NCOARSE * 4;  // k_scatter_coarse's run cursors (dynamic LDS)
   const int top_shift = wide ? wide_top_shift(ctx->curve, p.wide_bits) : 0;
-  // words per input of the two-level sort: 8 (32-byte scalars), 4 (the endomorphism's halves) or 1 / 2 (U32 / U64: NB = 4 / 8 bytes)
-  const int sw = p.nb ? p.nb / 4 : halves ? 4 : 8;
+  // inputs of the two-level sort: 32-byte scalars (8 words) or the endomorphism's halves (4), or narrow scalars of 4 / 8 / 16 bytes (1 / 2 / 4
+  // words), unsigned or signed.  f(C, SW, NB) for the kernel parameters of this launch.
+  const int sw = halves ? 4 : 8;
+  auto sort_input = [&](auto f) {
+    dispatch<16, 14, 12>(p.wbits, [&](auto c) {
+      dispatch<4, 8, 16, -4, -8, -16, 0>(p.nb_kernel(), [&](auto b) {
+        constexpr int NB = decltype(b)::value;
+        if constexpr (NB != 0) f(c, std::integral_constant<int, (narrow_width(NB) + 3) / 4>{}, b);
+        else dispatch<8, 4>(sw, [&](auto w) { f(c, w, b); });
+      });
+    });
+  };
   // first pass: recode + coarse histogram (+ digit planes: 1 = debug read-back, 2 = the second pass reads them).  Endomorphism launches:
   // the same kernel splits every scalar k = k1 + k2 lambda itself and leaves the halves (interleaved: input 2 j = k1 of scalar j, 2 j + 1 =
   // k2; a vector's 2n halves take the room of its n scalars, vector stride n * 8 words either way) for a scalar-reading second pass.
@@ -819,7 +844,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
                            p.v_begin, p.v_count);
     });
   } else if (bytes) {
-    dispatch<1, 2>(p.nb, [&](auto b) {
+    dispatch<1, 2, -1, -2>(p.nb_kernel(), [&](auto b) {
       if (p.sparse)
         hipLaunchKernelGGL((k_byte_count<decltype(b)::value, SparseIdx>), grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.tile_len, p.tiles, ctx->d_counts, sp);
       else
@@ -836,16 +861,17 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
                          p.planes ? nullptr : ctx->d_halves, d_err, merge_nb);
     d_scalars = ctx->d_halves;
   } else {
-    dispatch<16, 14, 12>(p.wbits, [&](auto c) {
-      dispatch<8, 2, 1>(sw, [&](auto w) {
-        constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
+    sort_input([&](auto c, auto w, auto b) {
+      constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = decltype(b)::value;
+      if constexpr (NB != 0 || SW == 8) {  // (the halves were counted above, by the pass that splits them)
+        const size_t vec_stride = p.n * (NB ? narrow_width(NB) : 8);
         if (p.sparse)
           hipLaunchKernelGGL((k_count<C, SW, false, NB, SparseIdx>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec,
-                             p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
+                             p.nvec, vec_stride, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
         else
           hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
-                             p.n * (NB ? NB : 8), ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
-      });
+                             vec_stride, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
+      }
     });
   }
   AFTER_KERNEL(ctx, "k_count", st);
@@ -873,7 +899,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
                        p.tile_len, p.tiles, p.w_count, p.w_count_vec, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
                        (uint32_t)ctx->n_bases, p.chunks, p.chunk_len, d_chunk_len);
   } else if (bytes) {
-    dispatch<1, 2>(p.nb, [&](auto b) {
+    dispatch<1, 2, -1, -2>(p.nb_kernel(), [&](auto b) {
       if (p.sparse)
         hipLaunchKernelGGL((k_byte_scatter<decltype(b)::value, SparseIdx>), grid, block, 0, st, (const uint8_t*)d_scalars, p.n, p.stride, p.tile_len, p.tiles,
                            p.w_count, ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len, sp);
@@ -882,18 +908,17 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
                            ctx->d_counts, ctx->d_bin_total, s.d_col_ptr, p.half, ctx->d_val, p.chunks, p.chunk_len, d_chunk_len);
     });
   } else {
-    dispatch<16, 14, 12>(p.wbits, [&](auto c) {
-      dispatch<8, 4, 2, 1>(sw, [&](auto w) {
-        constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = SW < 4 ? 4 * SW : 0;
-        if (p.sparse)
-          hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB, SparseIdx>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
-                             p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
-                             merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len, sp);
-        else
-          hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
-                             p.w_count_vec, p.nvec, p.n * (NB ? NB : 8), ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
-                             merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
-      });
+    sort_input([&](auto c, auto w, auto b) {
+      constexpr int C = decltype(c)::value, SW = decltype(w)::value, NB = decltype(b)::value;
+      const size_t vec_stride = p.n * (NB ? narrow_width(NB) : 8);
+      if (p.sparse)
+        hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB, SparseIdx>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
+                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                           merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len, sp);
+      else
+        hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
+                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                           merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
     });
   }
   AFTER_KERNEL(ctx, "k_scatter_coarse", st);
@@ -1588,7 +1613,7 @@ int msm_hip_run(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t
   // Parts (round 5): 32 n bytes over the host link come before anything can run.  From 2^19 points on the call is the sum of sub-MSMs over
   // ranges of the points, one result slot each: part k + 1's scalars arrive while part k is sorted and accumulated, and the results are added
   // on the host.  (Not with fixed-base tables: their launches are shaped by the table count.)
-  // (Nor with narrow scalars: 1 - 8 bytes per point leave no upload worth hiding.)
+  // (Nor with narrow scalars: 1 - 16 bytes per point leave no upload worth hiding, and the parts below step through 32-byte scalars.)
   int parts = ctx->precomputed || ctx->wide_bits || narrow_bytes(ctx->scalar_format) || !scalars_host ? 1 : upload_parts(n, NSLOT, 20, 22);  // (2^20: 2.44 -> 2.38 ms, 2^22: 8.61 -> 6.91; 2^19: slower)
   for (int k = 0; k < parts; k++)
     if (ctx->slot[k].pending) parts = 1;  // the caller has launches of its own in flight: the plain path (which reports a busy slot 0)

@@ -59,12 +59,15 @@ constexpr int JAC_WORDS = 3 * CW;   // a Jacobian record x || y || z: 96 B (144 
 // additions per point for 16 x / 4 x fewer buckets.  The host picks C from n (msm_hip.hip: pick_window_bits).
 // SW = words per scalar the recode reads: 8 (a 254-bit scalar) or 4 (one 127-bit half of the endomorphism split, csrc/glv.h:
 // magnitude in bits 0 .. 126, sign in bit 127).
-// NB != 0: narrow scalars (MSM_HIP_SCALARS_U8 .. U64) of NB bytes, unsigned, in SW = 1 (NB <= 4) or 2 (NB = 8) words: 8 NB bits, and
-// NWIN = (8 NB + C) / C windows -- 1 / 2 / 3 / 5 at 16 bits; the top window of U16 .. U64 holds only the recode's carry.
+// NB != 0: narrow scalars (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128) of NB bytes, unsigned, in SW = 1 (NB <= 4), 2 (NB = 8) or 4 (NB = 16)
+// words: 8 NB bits, and NWIN = (8 NB + C) / C windows -- 1 / 2 / 3 / 5 / 9 at 16 bits (NB = 16: 10 at 14 bits, 11 at 12); the top window of
+// U16 .. U128 holds only the recode's carry.  NB = 16 is not the SW = 4 half-scalar (NB = 0: 127 bits, its sign in bit 127).
+// The signed formats (MSM_HIP_SCALAR_SIGNED) recode the MAGNITUDE |v| <= 2^(8 NB - 1) with the configuration of their width; the kernels that
+// load scalars name such a format by a negative NB (narrow_width below) and carry the sign where the endomorphism's halves carry theirs.
 template <int C, int SW = 8, int NB = 0>
 struct WinCfg {
   static_assert((C >= 10 && C <= 16) || (C >= 17 && C <= 20), "window bits (17 .. 20: the digits of the wide fixed-base tables, k_count_wide)");
-  static_assert(NB ? (SW == (NB + 3) / 4 && (NB == 1 || NB == 2 || NB == 4 || NB == 8)) : (SW == 8 || SW == 4), "scalar words");
+  static_assert(NB ? (SW == (NB + 3) / 4 && (NB == 1 || NB == 2 || NB == 4 || NB == 8 || NB == 16)) : (SW == 8 || SW == 4), "scalar words");
   static constexpr int BITS = C;
   static constexpr int SBITS = NB ? 8 * NB : SW == 8 ? 254 : 127;  // bits of the scalar (magnitude)
   static constexpr int NWIN = (SBITS + C) / C;             // 16: 16 | 8, 14: 19 | 10, 12: 22 | 11
@@ -74,6 +77,8 @@ struct WinCfg {
 };
 __host__ __device__ constexpr int nwin_of(int bits, bool halves = false) { return ((halves ? 127 : 254) + bits) / bits; }
 __host__ __device__ constexpr int narrow_nwin_of(int bits, int nb) { return (8 * nb + bits) / bits; }  // windows of an nb-byte narrow scalar
+// The NB parameter of the kernels that load narrow scalars: +w for w-byte unsigned integers, -w for w-byte two's-complement ones
+__host__ __device__ constexpr int narrow_width(int nb) { return nb < 0 ? -nb : nb; }
 
 // (exponent tables live in constant memory; filled from the generated constexpr arrays)
 template <int N>
@@ -388,10 +393,39 @@ __device__ __forceinline__ void ld_narrow(const uint8_t* v, size_t i, uint32_t s
   if constexpr (NB == 1) s[0] = v[i];
   else if constexpr (NB == 2) s[0] = reinterpret_cast<const uint16_t*>(v)[i];
   else if constexpr (NB == 4) s[0] = reinterpret_cast<const uint32_t*>(v)[i];
-  else {
+  else if constexpr (NB == 8) {
     const uint2 a = reinterpret_cast<const uint2*>(v)[i];
     s[0] = a.x;
     s[1] = a.y;
+  } else {
+    static_assert(NB == 16, "narrow scalar width");
+    const uint4 a = reinterpret_cast<const uint4*>(v)[i];
+    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w;
+  }
+}
+// the same for NB-byte two's-complement integers: s receives the magnitude |v| (the minimum's, 2^(8 NB - 1), fits the NB bytes unsigned),
+// `neg` the sign
+template <int NB>
+__device__ __forceinline__ void ld_narrow_signed(const uint8_t* v, size_t i, uint32_t s[(NB + 3) / 4], uint32_t& neg) {
+  constexpr int SW = (NB + 3) / 4;
+  ld_narrow<NB>(v, i, s);
+  neg = (s[SW - 1] >> ((8 * NB - 1) & 31)) & 1u;
+  uint64_t c = neg;  // -v = ~v + 1 within 8 NB bits
+#pragma unroll
+  for (int k = 0; k < SW; k++) {
+    c += s[k] ^ (0u - neg);
+    s[k] = (uint32_t)c;
+    c >>= 32;
+  }
+  if constexpr (NB < 4) s[0] &= (1u << (8 * NB)) - 1u;
+}
+// scalar i of a narrow vector in the format NB names (narrow_width): magnitude and sign
+template <int NB>
+__device__ __forceinline__ void ld_narrow_fmt(const uint8_t* v, size_t i, uint32_t s[(narrow_width(NB) + 3) / 4], uint32_t& neg) {
+  if constexpr (NB < 0) ld_narrow_signed<-NB>(v, i, s, neg);
+  else {
+    ld_narrow<NB>(v, i, s);
+    neg = 0;
   }
 }
 // the recode's input: a scalar (8 words) or one half of the endomorphism split (4 words; `neg` receives its sign)
@@ -494,7 +528,7 @@ __global__ void __launch_bounds__(256) k_scalars_from_mont256(const uint32_t* __
 template <int NB>
 __global__ void __launch_bounds__(256) k_mask_identity(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, size_t n, size_t base_off,
                                                        const uint64_t* __restrict__ id_bits, uint32_t n_bases, const uint32_t* __restrict__ idx) {
-  static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 8 || NB == 32, "scalar width");
+  static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 8 || NB == 16 || NB == 32, "scalar width");
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const size_t e = (size_t)blockIdx.y * n + j;
@@ -516,6 +550,10 @@ __global__ void __launch_bounds__(256) k_mask_identity(const uint8_t* __restrict
     }
     d[0] = a;
     d[1] = b;
+  } else if constexpr (NB == 16) {
+    uint4 a = make_uint4(0u, 0u, 0u, 0u);
+    if (!zero) a = reinterpret_cast<const uint4*>(in)[e];
+    reinterpret_cast<uint4*>(out)[e] = a;
   } else {
     using T = std::conditional_t<NB == 1, uint8_t, std::conditional_t<NB == 2, uint16_t, std::conditional_t<NB == 4, uint32_t, uint64_t>>>;
     T v = 0;
@@ -540,7 +578,8 @@ __global__ void __launch_bounds__(256) k_mask_identity(const uint8_t* __restrict
 // INTERLEAVED positions, so that a tile of positions is a tile of scalars and one LDS histogram serves both halves.  The halves go to
 // `halves_out` (position p at word 4 p: the same 32 B the scalar took) for k_scatter_coarse<C, 4>; negbits[v][h][n / 128 rounded up]: bit j of
 // half h's array is the sign of half h of scalar j.
-// NB != 0 (narrow scalars, MSM_HIP_SCALARS_U8 .. U64): `scalars` holds nvec x n x NB packed bytes, `vec_stride` counts BYTES, SW = (NB + 3) / 4.
+// NB != 0 (narrow scalars, MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128): `scalars` holds nvec x n x |NB| packed bytes, `vec_stride` counts BYTES,
+// SW = (|NB| + 3) / 4.  NB < 0 (MSM_HIP_SCALAR_SIGNED): two's-complement values -- the magnitude is recoded, the sign goes where a half's goes.
 // Sparse (a SparseIdx argument; one vector): scalar j whose index is out of range reads as zero, and the launch's error word gets ERRBIT_BAD_INDEX.
 __device__ __forceinline__ SparseIdx sparse_arg() { return SparseIdx{nullptr, 0u, nullptr}; }  // (a dense instantiation: never read)
 __device__ __forceinline__ SparseIdx sparse_arg(SparseIdx s) { return s; }
@@ -553,6 +592,7 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
   static_assert(!SPLIT || SW == 4, "the split produces 4-word halves");
   static_assert(!SPLIT || NB == 0, "narrow scalars are never split");
   constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  constexpr int NW = narrow_width(NB);  // bytes of a narrow scalar, whatever its signedness
   const SparseIdx sp = sparse_arg(sparse...);
   uint32_t bad_idx = 0;
   // merge_nb != 0 (fixed-base tables, see k_precompute_tables): every window of vector v feeds ONE bucket set, local window v
@@ -571,7 +611,7 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
   // one recoded input: histogram and plane entries of its local windows
   auto emit = [&](int v, size_t pos, const uint32_t* tb, uint32_t neg) {
 #pragma unroll
-    for (int w = 0; w < WinCfg<C, SW, NB>::NWIN; w++) {
+    for (int w = 0; w < WinCfg<C, SW, NW>::NWIN; w++) {
       const int lw = w - w_begin;
       if (lw >= 0 && lw < w_count) {
         const int le = merge_nb ? v : v * w_count + lw;
@@ -627,17 +667,18 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
       for (size_t i0 = base; i0 < end; i0 += 256) {
         const size_t i = i0 + tid;
         if (i >= end) continue;
-        uint32_t s[SW], tb[WinCfg<C, SW, NB>::WORDS];
-        ld_narrow<NB>(nv, i, s);
+        uint32_t s[SW], tb[WinCfg<C, SW, NW>::WORDS], neg;
+        ld_narrow_fmt<NB>(nv, i, s, neg);
         if constexpr (SPARSE) {
           if (sp.idx[i] >= sp.n_bases) {
             bad_idx = 1;
+            neg = 0;
 #pragma unroll
             for (int k = 0; k < SW; k++) s[k] = 0;
           }
         }
-        (void)bias_scalar<C, SW, NB>(s, tb);  // (every unsigned NB-byte value fits: no input is rejected)
-        emit(v, i, tb, 0u);
+        (void)bias_scalar<C, SW, NW>(s, tb);  // (every NB-byte value or magnitude fits: no input is rejected)
+        emit(v, i, tb, neg);
       }
     } else {
       for (size_t i0 = base; i0 < end; i0 += 256) {
@@ -740,7 +781,7 @@ constexpr int SCAT_SUB = 2048;  // scalars staged per block iteration (8 per thr
 // declared statically, three workgroups fitted a CU whatever the launch's size; the half-scalar form is held to 128 registers (four waves per SIMD):
 // 1290 -> 1148 us at 2^24.  (Tried and dropped: splitting the scalars again here instead of reading the halves the first pass wrote -- 1 GB less
 // traffic at 2^24, and 1522 us instead of 1148 with the first pass no faster: profiles/r05_sort.txt.)
-// NB != 0: narrow scalars (the layout of k_count<C, SW, false, NB>; vec_stride in bytes)
+// NB != 0: narrow scalars (the layout of k_count<C, SW, false, NB>; vec_stride in bytes; NB < 0: signed, the sign in `negs`)
 // Sparse (a SparseIdx argument): input i carries base idx[i] (halves: idx[i / 2], + half_shift for k2) instead of its position, and an input
 // whose index is out of range reads as a zero scalar, as in k_count
 template <int C, int SW, int NB = 0, typename... Sparse>
@@ -758,7 +799,8 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
   // 282 VGPRs + 26 AGPRs at 16 bits (one wave per SIMD) and a 304-byte scratch object at 12 bits (round 3)
   constexpr int PER = SW == 8 ? 4 : 8;
   constexpr int SUB = 256 * PER;
-  using Cfg = WinCfg<C, SW, NB>;
+  using Cfg = WinCfg<C, SW, narrow_width(NB)>;
+  constexpr bool HALVES = SW == 4 && NB == 0;  // (128-bit narrow scalars have 4 words too)
   static_assert(SUB <= SCAT_SUB, "LDS staging arrays");
   // SW = 4 (endomorphism halves, interleaved by k_count<C, 4, true>): input 2 j is k1 of scalar j and multiplies base j; input 2 j + 1 is
   // k2 and multiplies phi(P_j), record half_shift = n_bases + j
@@ -820,17 +862,17 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
       for (int k = 0; k < SW; k++) raw[k] = 0;  // an all-zero scalar recodes to all-zero digits: no entries
       bool live = i < tile_end;
       if constexpr (SPARSE) {
-        const uint32_t x = live ? sp.idx[SW == 4 ? i >> 1 : i] : 0u;
+        const uint32_t x = live ? sp.idx[HALVES ? i >> 1 : i] : 0u;
         live = live && x < sp.n_bases;
-        rec[j] = x + ((SW == 4 && (i & 1u)) ? half_shift : 0u);
+        rec[j] = x + ((HALVES && (i & 1u)) ? half_shift : 0u);
       }
       if constexpr (NB != 0) {
-        if (live) ld_narrow<NB>(reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride, i, raw);
+        if (live) ld_narrow_fmt<NB>(reinterpret_cast<const uint8_t*>(scalars) + (size_t)v * vec_stride, i, raw, neg);
       } else {
         if (live) ld_scalar<SW>(scalars + (size_t)v * vec_stride + i * SW, raw, neg);
       }
       negs |= neg << j;
-      (void)bias_scalar<C, SW, NB>(raw, sc[j]);
+      (void)bias_scalar<C, SW, narrow_width(NB)>(raw, sc[j]);
     }
 #pragma unroll
     for (int w = 0; w < Cfg::NWIN; w++) {
@@ -860,7 +902,7 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
           const uint32_t e = lstart[bin] + rank[j];
           uint32_t pos = (uint32_t)(sub + (size_t)j * 256 + tid);
           if constexpr (SPARSE) pos = rec[j];
-          else if constexpr (SW == 4) pos = (pos >> 1) + ((pos & 1u) ? half_shift : 0u);
+          else if constexpr (HALVES) pos = (pos >> 1) + ((pos & 1u) ? half_shift : 0u);
           st_val[e] = (idx_base + pos) | (((code >> 15) ^ ((negs >> j) & 1u)) << 31);
           st_fine[e] = (uint8_t)(slot & 0xffu);
           st_dst[e] = gpos[lw * NCOARSE + bin] + rank[j];
@@ -880,13 +922,15 @@ __global__ void __launch_bounds__(256, (SW == 4 || NB != 0 ? 4 : 1)) k_scatter_c
   }
 }
 
-// ---- byte windows (narrow U8 / U16 scalars: MSM_HIP_SCALARS_U8, MSM_HIP_SCALARS_U16) -------------------------------------------------------
+// ---- byte windows (narrow U8 / U16 scalars: MSM_HIP_SCALARS_U8, MSM_HIP_SCALARS_U16, and their signed forms) -------------------------------
 // A window is one byte of the scalar (U8: 1 window, U16: 2 -- low byte, high byte), its digit the byte itself: unsigned, bucket slot = value
 // (1 .. 255; a zero byte emits no entry).  With 256 slots a one-level counting sort suffices -- no coarse bins, so a few-distinct-values vector
 // (booleans: every entry in slot 1) never meets k_sort_fine's huge-bin fallback.  The four kernels leave exactly what k_sort_fine leaves:
 // val_idxs grouped by slot (point index, sign bit 0), col_ptr over the launch's whole bucket grid (slots 256 .. half hold the window's total:
 // empty), the SMVP's chunk table and chunk-length word.  Everything behind them (SMVP, stitch, bucket reduce on the 12-bit grid) is unchanged;
 // the host weighs window j by 2^(8 j).  No field arithmetic: instantiated once, in BN254's unit.
+// Signed forms (NB = -1, -2: I8 / I16): the digits are the bytes of |v| -- at most 128 in I8's byte and I16's high byte, so the 255 slots
+// suffice -- and every entry of a negative value carries its sign in bit 31, which the SMVP subtracts on.
 // Layouts: counts[lw][tile][256] and bin_total[lw][256] in the arrays of the coarse sort, which hold BYTE_MAXLW windows of 256 bins.
 constexpr int BYTE_BINS = 256;
 constexpr int BYTE_MAXLW = MAXLW * NCOARSE / BYTE_BINS;  // local windows a byte-window launch may carry (32)
@@ -896,19 +940,31 @@ __device__ __forceinline__ uint32_t ld_byte_scalar(const uint8_t* v, size_t i) {
   if constexpr (NB == 1) return v[i];
   else return reinterpret_cast<const uint16_t*>(v)[i];
 }
-// counting pass: grid (tiles, nvec); a 256-bin LDS histogram per (tile, window).  scalars: nvec x n x NB bytes.
+// ... of the format NB names (narrow_width): the magnitude, and the sign in `neg`
+template <int NB>
+__device__ __forceinline__ uint32_t ld_byte_scalar_fmt(const uint8_t* v, size_t i, uint32_t& neg) {
+  uint32_t s = ld_byte_scalar<narrow_width(NB)>(v, i);
+  neg = 0;
+  if constexpr (NB < 0) {
+    neg = s >> (8 * -NB - 1);
+    if (neg) s = (0u - s) & ((1u << (8 * -NB)) - 1u);
+  }
+  return s;
+}
+// counting pass: grid (tiles, nvec); a 256-bin LDS histogram per (tile, window).  scalars: nvec x n x |NB| bytes (NB < 0: signed -- the bytes of |v|).
 // Sparse (a SparseIdx argument, as k_count): an entry whose index is out of range counts as a zero scalar and sets ERRBIT_BAD_INDEX in sp.err
 template <int NB, typename... Sparse>
 __global__ void __launch_bounds__(256) k_byte_count(const uint8_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
                                                     uint32_t* __restrict__ counts, Sparse... sparse) {
   constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  constexpr int NW = narrow_width(NB);
   const SparseIdx sp = sparse_arg(sparse...);
-  __shared__ uint32_t hist[NB * BYTE_BINS];
+  __shared__ uint32_t hist[NW * BYTE_BINS];
   const int tid = threadIdx.x, v = blockIdx.y;
 #pragma unroll
-  for (int j = 0; j < NB; j++) hist[j * BYTE_BINS + tid] = 0;
+  for (int j = 0; j < NW; j++) hist[j * BYTE_BINS + tid] = 0;
   __syncthreads();
-  const uint8_t* sv = scalars + (size_t)v * n * NB;
+  const uint8_t* sv = scalars + (size_t)v * n * NW;
   const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
   for (size_t i = base + tid; i < end; i += 256) {
     if constexpr (SPARSE) {
@@ -917,16 +973,17 @@ __global__ void __launch_bounds__(256) k_byte_count(const uint8_t* __restrict__ 
         continue;
       }
     }
-    const uint32_t s = ld_byte_scalar<NB>(sv, i);
+    uint32_t neg;
+    const uint32_t s = ld_byte_scalar_fmt<NB>(sv, i, neg);
 #pragma unroll
-    for (int j = 0; j < NB; j++) {
+    for (int j = 0; j < NW; j++) {
       const uint32_t b = (s >> (8 * j)) & 0xffu;
       if (b) atomicAdd(&hist[j * BYTE_BINS + b], 1u);
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < NB; j++) counts[((size_t)(v * NB + j) * tiles + blockIdx.x) * BYTE_BINS + tid] = hist[j * BYTE_BINS + tid];
+  for (int j = 0; j < NW; j++) counts[((size_t)(v * NW + j) * tiles + blockIdx.x) * BYTE_BINS + tid] = hist[j * BYTE_BINS + tid];
 }
 // scan over the tiles: one wave per (window, bin) -- counts[lw][tile][bin] becomes the bin's entries in earlier tiles, bin_total[lw][bin] its size
 __global__ void __launch_bounds__(256) k_byte_scan(uint32_t* __restrict__ counts, uint32_t tiles, uint32_t* __restrict__ bin_total) {
@@ -952,6 +1009,7 @@ __global__ void __launch_bounds__(256) k_byte_scan(uint32_t* __restrict__ counts
 // vector v's windows over the whole grid of `half` slots, workgroup (0, 0) the launch's SMVP chunk length (the fullest of its w_count windows).
 // Entries are placed with LDS cursors (order within a slot: unspecified, as everywhere).
 // Sparse (a SparseIdx argument): entry i carries base idx[i]; an out-of-range one is skipped, as k_byte_count skipped it.
+// NB < 0 (I8 / I16): the entries of a negative value carry bit 31.
 template <int NB, typename... Sparse>
 __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict__ scalars, size_t n, size_t stride, uint32_t tile_len, uint32_t tiles,
                                                       int w_count, const uint32_t* __restrict__ counts, const uint32_t* __restrict__ bin_total,
@@ -959,14 +1017,15 @@ __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict_
                                                       uint32_t chunks, uint32_t host_chunk_len, uint32_t* __restrict__ chunk_len_dev,
                                                       Sparse... sparse) {
   constexpr bool SPARSE = sizeof...(Sparse) != 0;
+  constexpr int NW = narrow_width(NB);
   const SparseIdx sp = sparse_arg(sparse...);
-  __shared__ uint32_t cur[NB * BYTE_BINS];
+  __shared__ uint32_t cur[NW * BYTE_BINS];
   __shared__ uint32_t wave_tot[4];
   __shared__ uint32_t wtotal, max_total;
   const int tid = threadIdx.x, v = blockIdx.y;
   if (tid == 0) max_total = 0;
-  for (int j = 0; j < NB; j++) {
-    const int lw = v * NB + j;
+  for (int j = 0; j < NW; j++) {
+    const int lw = v * NW + j;
     const uint32_t bt = bin_total[lw * BYTE_BINS + tid];
     const uint32_t excl = block_excl_scan_256(bt, wave_tot);
     cur[j * BYTE_BINS + tid] = excl + counts[((size_t)lw * tiles + blockIdx.x) * BYTE_BINS + tid];
@@ -987,7 +1046,7 @@ __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict_
     __syncthreads();
     if (tid == 0) *chunk_len_dev = smvp_chunk_len(max_total, chunks, host_chunk_len);
   }
-  const uint8_t* sv = scalars + (size_t)v * n * NB;
+  const uint8_t* sv = scalars + (size_t)v * n * NW;
   const size_t base = (size_t)blockIdx.x * tile_len, end = base + tile_len < n ? base + tile_len : n;
   for (size_t i = base + tid; i < end; i += 256) {
     uint32_t rec = (uint32_t)i;
@@ -995,11 +1054,13 @@ __global__ void __launch_bounds__(256) k_byte_scatter(const uint8_t* __restrict_
       rec = sp.idx[i];
       if (rec >= sp.n_bases) continue;
     }
-    const uint32_t s = ld_byte_scalar<NB>(sv, i);
+    uint32_t neg;
+    const uint32_t s = ld_byte_scalar_fmt<NB>(sv, i, neg);
+    rec |= neg << 31;
 #pragma unroll
-    for (int j = 0; j < NB; j++) {
+    for (int j = 0; j < NW; j++) {
       const uint32_t b = (s >> (8 * j)) & 0xffu;
-      if (b) val_idxs[(size_t)(v * NB + j) * stride + atomicAdd(&cur[j * BYTE_BINS + b], 1u)] = rec;
+      if (b) val_idxs[(size_t)(v * NW + j) * stride + atomicAdd(&cur[j * BYTE_BINS + b], 1u)] = rec;
     }
   }
 }
