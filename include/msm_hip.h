@@ -266,6 +266,45 @@ int msm_hip_run_sparse(msm_hip_ctx* ctx, const uint32_t* indices_host, const uin
 int msm_hip_run_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, uint8_t out_xyz[96]);
 int msm_hip_launch_sparse_device(msm_hip_ctx* ctx, const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot);
 
+/* ---- batch scalar multiplication: n group elements out, not one sum.  (Added within ABI version 7.)
+ *        mul_each : out[i] = s_i * P_i            for the first n resident bases, n <= n_bases of the last set_bases
+ *        mul_base : out[i] = s_i * P_base_index   base_index < n_bases; n is independent of n_bases, 1 <= n <= 2^28
+ *      Both read the plain records 0 .. n_bases-1, which every base mode keeps: they work after plain, endomorphism, 16-bit-table and wide-table
+ *      set_bases alike.
+ *      - Scalars: n x 32 B in the context's format, MSM_HIP_SCALARS_CANONICAL or MSM_HIP_SCALARS_MONT256; with a narrow, signed or 128-bit format
+ *        set on the context the calls return MSM_HIP_ERR_INVALID_ARG.  A scalar >= r (compared on the device) makes the call return
+ *        MSM_HIP_ERR_NONCANONICAL -- nothing of the output is then meaningful -- and the context stays usable.
+ *      - Output: n records of the curve's point size (64, 96, 128 or 192 B), x || y, every coordinate a canonical little-endian integer below p.
+ *        The identity is the ALL-ZERO record, the MSM_HIP_BASES_ZERO_IS_IDENTITY encoding: the output of a _device call can go straight into
+ *        msm_hip_set_bases_device(..., MSM_HIP_BASES_ZERO_IS_IDENTITY).  s_i = 0 gives the identity; so does an identity base (a base set uploaded
+ *        with that flag) whatever its scalar, which is then not validated either.
+ *      - Which ladder runs.  On the curves of prime order (BN254 G1, Grumpkin, Pallas, Vesta) always the endomorphism's: a joint ladder of 127 steps
+ *        over the halves of s_i (csrc/scalar_mul.h).  On BLS12-381 G1 and both G2 groups the plain ladder of one step per bit of r, which gives the integer
+ *        multiple for ANY point of the curve (the library's convention for points outside the subgroup), unless MSM_HIP_MUL_BASES_ORDER_R is
+ *        passed: the caller then vouches that the bases have order r, as for MSM_HIP_BASES_ENDOMORPHISM, and the endomorphism's ladder runs.  On a
+ *        curve of prime order the flag is accepted and ignored.
+ *      - Results are made affine with shared inversions: one field inversion per 16 outputs.
+ *      - Execution: enqueued on the engine's main stream in tiles of 2^20 outputs; the call returns when the output is complete.  The _device forms
+ *        read the scalars and write the output in place (both 16-byte aligned; msm_hip_wait_stream orders their producer); the host forms stage
+ *        one tile at a time.  Device scratch kept by the context: 2 coordinates + 64 B per output of a tile (128 MiB at most on BN254 G1, 320 MiB on
+ *        BLS12-381 G2; the host forms add a staged tile: + 96 .. 224 B per output).
+ *      - n == 0: MSM_HIP_OK, nothing written.  MSM_HIP_ERR_INVALID_ARG: a null pointer with n > 0, n > n_bases (mul_each), base_index >= n_bases,
+ *        scalar and output ranges that overlap, an unknown flag bit, n > 2^28.  MSM_HIP_ERR_NO_BASES before set_bases; MSM_HIP_ERR_NO_DEVICE with
+ *        no device.
+ *      - mul_base and its fixed-base table.  From 2^17 outputs on, mul_base does not run the ladder: it builds, on the device, the table
+ *        T_w[j] = j * 2^(C w) * P_base_index for j = 1 .. 2^(C-1) and w < W = (bits of r + 1 + C) / C, recodes every scalar into W signed C-bit digits
+ *        and adds W gathered table entries -- no doublings (W = 16 additions at C = 16 on BN254 G1, 17 where r has 255 bits).  C is 12 below 2^23
+ *        outputs, 14 below 2^24, else 16; below 2^17 the ladder runs with the base broadcast.  These are the measured crossovers on BN254 G1
+ *        (profiles/mul_each.txt).  The context keeps ONE table, keyed by (base_index, C, ladder that built it): a held table is reused by every later
+ *        call with the same base, whatever n (it beats the ladder from the smallest n on), replaced on a change of key and dropped by set_bases.
+ *        Its device memory is W * 2^(C-1) point records: on BN254 G1 2.8 MiB at C = 12, 9.5 MiB at C = 14, 32 MiB at C = 16; on BLS12-381 G2 3.2 x
+ *        that.  The first call with a key pays the build: 1.3 ms (C = 12) to 5.5 ms (C = 16) on BN254 G1. ---- */
+#define MSM_HIP_MUL_BASES_ORDER_R 1u
+int msm_hip_mul_each(msm_hip_ctx* ctx, const uint8_t* scalars_host, size_t n, uint8_t* out_xy_host, uint32_t flags);
+int msm_hip_mul_each_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags);
+int msm_hip_mul_base(msm_hip_ctx* ctx, size_t base_index, const uint8_t* scalars_host, size_t n, uint8_t* out_xy_host, uint32_t flags);
+int msm_hip_mul_base_device(msm_hip_ctx* ctx, size_t base_index, const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags);
+
 /* ---- batch: `batch` independent scalar vectors (batch x n x 32 B, contiguous, device memory) over the resident bases;
  *      out: batch x 96 B.  Internally a software pipeline over the result slots (BASELINE.json config 5: many MSMs over
  *      one shared base). ---- */
@@ -463,6 +502,17 @@ int msm_hip_mgpu_inject_fault(msm_hip_mgpu* m, int device_index, int launches);
 /* test hook: the part policy of the one-shot call (msm_hip_msm_curve: `parts` sub-MSMs over ranges of the points when n >= min_points; 0, 0 restores
  * the default of 2 parts from 2^19 points on) -- so that a test reaches the multi-part path with inputs the oracle finishes in seconds. */
 int msm_hip_test_oneshot_parts(int parts, size_t min_points);
+
+/* test hook: what the last msm_hip_mul_each / msm_hip_mul_base call of the context ran -- path: 0 no ladder (nothing yet, or an identity base
+ * broadcast), 1 the plain ladder, 2 the endomorphism's, 3 the fixed-base table the context already held, 4 the table, built by that call;
+ * table_bits: the table's digit width C (0: a ladder ran); chunk: outputs per shared inversion.  Null pointers are skipped. */
+int msm_hip_test_mul_last(const msm_hip_ctx* ctx, int* path, int* table_bits, int* chunk);
+/* test hook: the table policy of msm_hip_mul_base -- table_min_n != 0: the table runs exactly when n >= table_min_n (1 forces it, SIZE_MAX
+ * forbids it); table_bits != 0 (4 .. 16): with that digit width instead of the cost model's.  0, 0 restores the policy. */
+int msm_hip_test_mul_policy(msm_hip_ctx* ctx, size_t table_min_n, int table_bits);
+/* test hook: which ladder the following msm_hip_mul_* calls of the context run -- 0 the policy above, 1 always the plain ladder, 2 always the
+ * endomorphism's: for the oracle check of the ladder a curve's policy never picks, and for timing one against the other in one process. */
+int msm_hip_test_mul_ladder(msm_hip_ctx* ctx, int ladder);
 #endif /* MSM_HIP_TEST_HOOKS */
 
 const char* msm_hip_strerror(int code);

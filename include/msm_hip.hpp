@@ -172,6 +172,33 @@ class MsmContext {
   void launch_sparse_device(const uint32_t* indices_dev, const void* scalars_dev, size_t nnz, int slot) {
     check(msm_hip_launch_sparse_device(ctx_, indices_dev, scalars_dev, nnz, slot), "msm_hip_launch_sparse_device");
   }
+  /// Batch scalar multiplication (msm_hip_mul_each ...): n affine records x || y of the context's curve, the identity as the all-zero record.
+  /// mul_each: out[i] = scalars[i] * base i; mul_base: out[i] = scalars[i] * base `base_index`.  n x 32-byte scalars in the context's format;
+  /// `flags`: MSM_HIP_MUL_BASES_ORDER_R.  The _device forms read and write device memory in place.
+  size_t point_bytes() const {
+    switch (msm_hip_ctx_curve(ctx_)) {
+      case MSM_HIP_CURVE_BLS12_381: return 96;
+      case MSM_HIP_CURVE_BN254_G2: return 128;
+      case MSM_HIP_CURVE_BLS12_381_G2: return 192;
+      default: return 64;
+    }
+  }
+  std::vector<uint8_t> mul_each(const uint8_t* scalars, size_t n, uint32_t flags = 0) {
+    std::vector<uint8_t> out(n * point_bytes());
+    check(msm_hip_mul_each(ctx_, scalars, n, out.data(), flags), "msm_hip_mul_each");
+    return out;
+  }
+  void mul_each_device(const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags = 0) {
+    check(msm_hip_mul_each_device(ctx_, scalars_dev, n, out_xy_dev, flags), "msm_hip_mul_each_device");
+  }
+  std::vector<uint8_t> mul_base(size_t base_index, const uint8_t* scalars, size_t n, uint32_t flags = 0) {
+    std::vector<uint8_t> out(n * point_bytes());
+    check(msm_hip_mul_base(ctx_, base_index, scalars, n, out.data(), flags), "msm_hip_mul_base");
+    return out;
+  }
+  void mul_base_device(size_t base_index, const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags = 0) {
+    check(msm_hip_mul_base_device(ctx_, base_index, scalars_dev, n, out_xy_dev, flags), "msm_hip_mul_base_device");
+  }
   G1 finish(int slot) {
     G1 r;
     check(msm_hip_finish(ctx_, slot, r.xyz.data()), "msm_hip_finish");

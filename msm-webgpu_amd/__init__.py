@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     MsmContext,
     MsmHipError,
     MultiGpuMsm,
+    bytes_to_points,
     compute_msm,
     lib,
     points_to_bytes,
@@ -23,4 +24,4 @@ from .api import (  # noqa: F401
 from .build import build  # noqa: F401
 
 __all__ = ["G1", "MsmContext", "MultiGpuMsm", "MsmHipError", "compute_msm", "run_webgpu_msm", "points_to_bytes", "scalars_to_bytes",
-           "sample_points", "sample_scalars", "build", "lib", "BASES_ZERO_IS_IDENTITY"]
+           "sample_points", "sample_scalars", "build", "lib", "BASES_ZERO_IS_IDENTITY", "bytes_to_points"]

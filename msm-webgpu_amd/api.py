@@ -81,6 +81,13 @@ def lib():
         L.msm_hip_run_sparse.argtypes = [vp, vp, u8p, sz, u8p]
         L.msm_hip_run_sparse_device.argtypes = [vp, vp, vp, sz, u8p]
         L.msm_hip_launch_sparse_device.argtypes = [vp, vp, vp, sz, i]
+        L.msm_hip_mul_each.argtypes = [vp, u8p, sz, u8p, C.c_uint32]
+        L.msm_hip_mul_each_device.argtypes = [vp, vp, sz, vp, C.c_uint32]
+        L.msm_hip_mul_base.argtypes = [vp, sz, u8p, sz, u8p, C.c_uint32]
+        L.msm_hip_mul_base_device.argtypes = [vp, sz, vp, sz, vp, C.c_uint32]
+        L.msm_hip_test_mul_last.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+        L.msm_hip_test_mul_ladder.argtypes = [vp, i]
+        L.msm_hip_test_mul_policy.argtypes = [vp, sz, i]
         L.msm_hip_wait_stream.argtypes = [vp, vp]
         L.msm_hip_finish.argtypes = [vp, i, u8p]
         L.msm_hip_run_windows_device.argtypes = [vp, vp, sz, i, i, vp]
@@ -167,6 +174,25 @@ def points_to_bytes(points, zero_is_identity=False):
             raise ValueError("coordinate out of range")
         out += int(x).to_bytes(32, "little") + int(y).to_bytes(32, "little")
     return bytes(out)
+
+
+def bytes_to_points(b, curve="bn254"):
+    """n records x || y of a curve's wire format -> [(x, y) | None, ...]: canonical integers (pairs (c0, c1) on a G2 curve), None for an
+    all-zero record (the identity, as mul_each / mul_base write it).  The inverse of points_to_bytes(..., zero_is_identity=True) on BN254."""
+    b = bytes(b)
+    cb = coord_bytes(curve)
+    if len(b) % (2 * cb):
+        raise ValueError("points must be n x %d bytes" % (2 * cb))
+    h = cb // 2 if curve in ("bn254_g2", "bls12_381_g2") else cb
+    out = []
+    for k in range(0, len(b), 2 * cb):
+        rec = b[k:k + 2 * cb]
+        if not any(rec):
+            out.append(None)
+            continue
+        v = [int.from_bytes(rec[j:j + h], "little") for j in range(0, 2 * cb, h)]
+        out.append((v[0], v[1]) if h == cb else ((v[0], v[1]), (v[2], v[3])))
+    return out
 
 
 def scalars_to_bytes(scalars):
@@ -391,6 +417,68 @@ class MsmContext:
             b, n = self._host_scalars(scalars)
             _check(lib().msm_hip_run(self._h, b, n, out), "msm_hip_run")
         return G1(out.raw, self.modulus)
+
+    # -- batch scalar multiplication: n points out
+    MUL_BASES_ORDER_R = 1  # MSM_HIP_MUL_BASES_ORDER_R
+
+    def _mul(self, index, scalars, bases_order_r, out):
+        if self.scalar_width != 32:
+            raise ValueError("mul_each / mul_base take 32-byte scalars (canonical or mont256), not the %d-byte format set on the context" % self.scalar_width)
+        flags = self.MUL_BASES_ORDER_R if bases_order_r else 0
+        if isinstance(scalars, torch.Tensor) and scalars.is_cuda:
+            t, n = _as_device_u8(scalars, 32, "scalars")
+            if out is None:
+                out = torch.empty((n, self.pb), dtype=torch.uint8, device=t.device)
+            elif not (isinstance(out, torch.Tensor) and out.is_cuda):
+                raise TypeError("out must be a CUDA(HIP) uint8 tensor, as the scalars are")
+            elif out.dtype != torch.uint8 or tuple(out.shape) != (n, self.pb) or not out.is_contiguous() or out.device != t.device:
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d, %d) on %s" % (n, self.pb, t.device))
+            self._order_after_torch(t)
+            if index is None:
+                _check(lib().msm_hip_mul_each_device(self._h, t.data_ptr(), n, out.data_ptr(), flags), "msm_hip_mul_each_device")
+            else:
+                _check(lib().msm_hip_mul_base_device(self._h, index, t.data_ptr(), n, out.data_ptr(), flags), "msm_hip_mul_base_device")
+            return out
+        if out is not None:
+            raise TypeError("out is for device scalars; host scalars return bytes")
+        b, n = self._host_scalars(scalars)
+        buf = C.create_string_buffer(self.pb * n)
+        if index is None:
+            _check(lib().msm_hip_mul_each(self._h, b, n, buf, flags), "msm_hip_mul_each")
+        else:
+            _check(lib().msm_hip_mul_base(self._h, index, b, n, buf, flags), "msm_hip_mul_base")
+        return buf.raw
+
+    def mul_each(self, scalars, bases_order_r=False, out=None):
+        """[scalars[i] * bases[i]] for the first n resident bases (msm_hip_mul_each): n affine records x || y, the identity as the all-zero
+        record (bytes_to_points reads them; a device result can go straight into set_bases(..., zero_is_identity=True)).  Host bytes in give
+        bytes out; a CUDA uint8 tensor in gives a CUDA uint8 tensor [n, pb] out (`out`: a preallocated one).  32-byte scalar formats only.
+        bases_order_r: on BLS12-381 and the G2 curves, vouch that the bases have order r, so that the endomorphism's ladder may run."""
+        return self._mul(None, scalars, bases_order_r, out)
+
+    def mul_base(self, index, scalars, bases_order_r=False, out=None):
+        """[scalars[i] * bases[index]] (msm_hip_mul_base): as mul_each with one resident base for every scalar; n is free of n_bases."""
+        index = int(index)
+        if index < 0:
+            raise ValueError("base index %d is negative" % index)
+        return self._mul(index, scalars, bases_order_r, out)
+
+    def mul_last(self):
+        """(path, table_bits, chunk) of the last mul_each / mul_base call (test hook msm_hip_test_mul_last): path 0 none, 1 plain ladder, 2 endomorphism, 3 table held, 4 table built"""
+        v = [C.c_int(), C.c_int(), C.c_int()]
+        _check(lib().msm_hip_test_mul_last(self._h, *[C.byref(x) for x in v]), "msm_hip_test_mul_last")
+        return tuple(x.value for x in v)
+
+    def mul_policy(self, table_min_n=0, table_bits=0):
+        """test hook msm_hip_test_mul_policy: mul_base's table runs exactly when n >= table_min_n (1 forces it, "never" forbids it), with digit
+        width table_bits (0: the cost model's); 0, 0 restores the policy"""
+        if table_min_n == "never":
+            table_min_n = C.c_size_t(-1).value
+        _check(lib().msm_hip_test_mul_policy(self._h, int(table_min_n), int(table_bits)), "msm_hip_test_mul_policy")
+
+    def mul_force_ladder(self, ladder):
+        """test hook msm_hip_test_mul_ladder: 0 the policy, 1 always the plain ladder, 2 always the endomorphism's"""
+        _check(lib().msm_hip_test_mul_ladder(self._h, int(ladder)), "msm_hip_test_mul_ladder")
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

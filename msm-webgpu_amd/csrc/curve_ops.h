@@ -15,6 +15,14 @@ struct CurveOps {
   void (*convert_points_zero_id)(const uint32_t*, uint32_t*, size_t, uint32_t, uint32_t*, uint64_t*, uint32_t*);
   void (*precompute_tables)(uint32_t*, size_t, size_t, int, int, int);
   void (*endo_points)(uint32_t*, size_t, size_t, size_t);
+  // batch scalar multiplication (msm_hip_mul_each / msm_hip_mul_base): k_mul_each<false> (plain ladder), k_mul_each<true> (endomorphism), k_mul_normalize
+  void (*mul_each[2])(const uint32_t*, const uint32_t*, size_t, size_t, uint32_t, const uint64_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t);
+  void (*mul_normalize)(uint32_t*, const uint32_t*, uint32_t*, size_t);
+  int mul_chunk;    // results that share one inversion in k_mul_normalize
+  // ... the fixed-base table of msm_hip_mul_base: k_mul_table_scalars, k_mul_fixed; bit length of r (the table has (r_bits + 1 + C) / C windows)
+  void (*mul_table_scalars)(int, size_t, size_t, uint32_t*);
+  void (*mul_fixed)(const uint32_t*, int, const uint32_t*, size_t, uint32_t*, uint32_t*, uint32_t*);
+  int r_bits;
   // k_count<C, 4, true> for C = 12 / 14 / 16: the first sort pass of endomorphism launches, which splits the scalars itself (csrc/glv.h)
   void (*count_split[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t);
   // ... and of sparse endomorphism launches (k_count<C, 4, true, 0, SparseIdx>: the split of scalar j, whose base is idx[j])
@@ -53,7 +61,7 @@ struct CurveOps {
   int (*to_affine64)(const uint8_t*, uint8_t*);
 };
 #define MSM_CURVE_OPS(K, F)                                                                                                              \
-  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
+  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_mul_each<false>, K::k_mul_each<true>}, K::k_mul_normalize, F::SMUL_CHUNK, K::k_mul_table_scalars, K::k_mul_fixed, F::SMUL_R_BITS, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
    {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
    K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
    K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \
@@ -61,7 +69,7 @@ struct CurveOps {
 
 // A G2 unit (coordinates in Fq2, csrc/fq2.h): the same table (its point sampler draws multiples of the subgroup's generator)
 #define MSM_CURVE_OPS_FQ2(K, F)                                                                                                          \
-  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
+  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_mul_each<false>, K::k_mul_each<true>}, K::k_mul_normalize, F::SMUL_CHUNK, K::k_mul_table_scalars, K::k_mul_fixed, F::SMUL_R_BITS, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
    {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
    K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
    K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \

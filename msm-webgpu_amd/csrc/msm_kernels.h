@@ -22,7 +22,9 @@
 #ifndef MSM_CURVE_UNIT
 #pragma once
 #include "g1.h"
+#include "glv.h"
 #endif
+#include "scalar_mul.h"
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -341,6 +343,69 @@ __global__ void __launch_bounds__(256) k_precompute_tables(uint32_t* __restrict_
     st_fq(bases + ((size_t)w * nb + i) * PT_WORDS + CW, y);
     acc = g1_from_affine(x, y);
   }
+}
+
+// ------------------------------------------------------------------------------------------------ batch scalar multiplication
+// msm_hip_mul_each / msm_hip_mul_base (csrc/scalar_mul.h has the arithmetic and the counts): out[i] = s_i * P_i over the plain records, or
+// s_i * P_base with one base broadcast.  Two kernels per tile of outputs:
+//   k_mul_each<ENDO>   one output per lane: the ladder, then the Jacobian record -- X' || Y' into the output record itself, Z into zbuf
+//   k_mul_normalize    lane-serial chunks of SMUL_CHUNK results, 256 apart (consecutive lanes: consecutive records), one Fermat inversion per
+//                      chunk: 1 / 16 inversion per output; the prefix products go to a scratch array laid out like zbuf
+// A base marked in `id_bits` (MSM_HIP_BASES_ZERO_IS_IDENTITY; null: no such base) gives the identity whatever its scalar, which is not even
+// compared with r; elsewhere a scalar >= r sets ERRBIT_NONCANONICAL (the host returns the error: nothing of the output is then meaningful).
+template <bool ENDO>
+__global__ void __launch_bounds__(256) k_mul_each(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ scalars, size_t n, size_t base_first,
+                                                  uint32_t broadcast, const uint64_t* __restrict__ id_bits, uint32_t* __restrict__ out_xy,
+                                                  uint32_t* __restrict__ zbuf, uint32_t* __restrict__ err, uint32_t check_r) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t b = broadcast ? base_first : base_first + i;
+  const bool ident = id_bits != nullptr && ((id_bits[b >> 6] >> (b & 63u)) & 1u) != 0;
+  g1_xyzz r = g1_identity();
+  if (!ident) {
+    uint32_t k[8];
+    ld8(scalars + i * 8, k);
+    if (check_r && smul_geq_r(k)) {  // (check_r = 0: the table build, whose scalars j 2^(C w) are integers up to 2^256)
+      atomicOr(err, ERRBIT_NONCANONICAL);
+    } else {
+      const fq px = ld_fq(bases + b * PT_WORDS), py = ld_fq(bases + b * PT_WORDS + CW);
+      r = ENDO ? smul_endo(px, py, k) : smul_plain(px, py, k, check_r ? SMUL_R_BITS : SMUL_FULL_BITS);
+    }
+  }
+  smul_store_jacobian(out_xy, zbuf, i, r);
+}
+
+// The fixed-base form of msm_hip_mul_base (csrc/scalar_mul.h, smul_fixed): the scalars of the table's entries, entry e = (w << (C - 1)) + j - 1 ...
+// (entries first .. first + count - 1 into out[0 .. count - 1]: the build runs tile by tile)
+__global__ void __launch_bounds__(256) k_mul_table_scalars(int c, size_t first, size_t count, uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const size_t e = first + i;
+  uint32_t k[8];
+  smul_table_scalar(c, (int)(e >> (c - 1)), (uint32_t)(e & ((1u << (c - 1)) - 1u)) + 1u, k);
+  st8(out + i * 8, k);
+}
+// ... and one output per lane from the finished table (packed Montgomery records, all-zero = identity): W gathered mixed additions, no doublings
+__global__ void __launch_bounds__(256) k_mul_fixed(const uint32_t* __restrict__ table, int c, const uint32_t* __restrict__ scalars, size_t n,
+                                                   uint32_t* __restrict__ out_xy, uint32_t* __restrict__ zbuf, uint32_t* __restrict__ err) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[8];
+  ld8(scalars + i * 8, k);
+  g1_xyzz r = g1_identity();
+  if (smul_geq_r(k)) atomicOr(err, ERRBIT_NONCANONICAL);
+  else r = smul_fixed(table, c, k);
+  smul_store_jacobian(out_xy, zbuf, i, r);
+}
+
+__global__ void __launch_bounds__(256) k_mul_normalize(uint32_t* __restrict__ xy, const uint32_t* __restrict__ zbuf, uint32_t* __restrict__ prefix, size_t n) {
+  const size_t block_first = (size_t)blockIdx.x * (256 * SMUL_CHUNK);
+  const size_t first = block_first + threadIdx.x;
+  const size_t block_end = block_first + 256 * SMUL_CHUNK;
+  const size_t end = block_end < n ? block_end : n;
+  if (first >= end) return;
+  const fq prod = smul_norm_forward(zbuf, prefix, first, 256, end);
+  smul_norm_backward(xy, zbuf, prefix, first, 256, end, fq_inv(prod));
 }
 
 // ------------------------------------------------------------------------------------------------ stage 1+2: recode + sort
