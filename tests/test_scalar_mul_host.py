@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+from tests import small_order
 from tests.edge_scalars import edge_values
 from tests.util import rng
 
@@ -198,6 +199,41 @@ def test_fixed_base_digit_recode_and_table_lookup(tmp_path_factory, curve):
     out = C.create_string_buffer(pb * 3)
     assert H.h_smul_fixed(1, 4, p, b32(m.R) + b32(7) + b32((1 << 256) - 1), 3, out) == 2
     assert out.raw[pb:2 * pb] == expected(cx, p, b32(7))
+
+
+@pytest.mark.parametrize("curve", list(small_order.COFACTOR_CURVES))
+def test_bases_of_small_order(tmp_path_factory, curve):
+    # A base T of prime order f = 3 .. 10177 (tests/small_order.py) is a legal input on a curve with a cofactor: k T is the integer multiple,
+    # (k mod f) T.  The plain ladder's accumulator then runs through +-T and the identity all the time, and most records of a fixed-base table
+    # (j 2^(C w) T, j up to 2^(C-1)) are identities when f is small.  On BLS12-381 G1 the point of order 3 is (0, +-2): x = 0 in a record that
+    # is NOT the identity.  Expected values: repeated addition in the big-integer model; the C oracle is pinned to the same bytes.
+    H, cx, m = harness(tmp_path_factory, curve)
+    pb = 2 * cx.coord_bytes()
+    big = cx.coord_bytes() > 48
+    r_ = m.R
+    for f in small_order.ORDERS[curve]:
+        t = small_order.torsion_point(curve, f)
+        if curve == "bls12_381" and f == 3:
+            assert t in ((0, 2), (0, m.P - 2))
+            t = (0, 2)
+        mult = small_order.multiples(m, f, t)
+        rnd = rng(90 + f)
+        ks = [0, 1, 2, 3, f - 1, f, f + 1, 2 * f, r_ - 1, r_ - 2, (r_ - 1) // 2, 0x8000, 0xFFFF, 0x7FFF8000] + [rnd.randrange(r_) for _ in range(20)]
+        n = len(ks)
+        p = small_order.enc(m, t)
+        sc = b"".join(b32(k) for k in ks)
+        want = b"".join(small_order.enc(m, mult[k % f]) for k in ks)
+        assert want[:pb] == bytes(pb) and want[5 * pb:6 * pb] == bytes(pb) and want[pb:2 * pb] == p
+        assert expected(cx, p * n, sc) == want, (curve, f, "the C oracle")
+        out = C.create_string_buffer(pb * n)
+        assert H.h_smul(0, p * n, sc, n, 3, out) == 0
+        bad = [hex(ks[i]) for i in range(n) if out.raw[pb * i:pb * i + pb] != want[pb * i:pb * i + pb]]
+        assert not bad, (curve, f, "plain ladder", bad[:4])
+        for c in (4, 5) if big else (4, 5, 7):
+            out = C.create_string_buffer(pb * n)
+            assert H.h_smul_fixed(0, c, p, sc, n, out) == 0
+            bad = [hex(ks[i]) for i in range(n) if out.raw[pb * i:pb * i + pb] != want[pb * i:pb * i + pb]]
+            assert not bad, (curve, f, "table", c, bad[:4])
 
 
 def test_fixed_base_table_outside_the_subgroup(tmp_path_factory):
