@@ -24,9 +24,9 @@ struct CurveOps {
   void (*mul_fixed)(const uint32_t*, int, const uint32_t*, size_t, uint32_t*, uint32_t*, uint32_t*);
   int r_bits;
   // k_count<C, 4, true> for C = 12 / 14 / 16: the first sort pass of endomorphism launches, which splits the scalars itself (csrc/glv.h)
-  void (*count_split[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t);
+  void (*count_split[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t);
   // ... and of sparse endomorphism launches (k_count<C, 4, true, 0, SparseIdx>: the split of scalar j, whose base is idx[j])
-  void (*count_split_sparse[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t,
+  void (*count_split_sparse[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t,
                                 SparseIdx);
   void (*scalars_from_mont256)(const uint32_t*, uint32_t*, size_t, uint32_t*);
   void (*smvp_chunks)(const uint32_t*, const uint32_t*, const uint32_t*, size_t, uint32_t, const uint32_t*, const uint32_t*, uint32_t*, uint32_t*,

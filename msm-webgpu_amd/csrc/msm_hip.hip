@@ -242,6 +242,8 @@ struct msm_hip_ctx {
   int timing_level = 2;  // 0: no stage events, 1: only around the SMVP kernel, 2: every stage boundary
   uint32_t* d_counts = nullptr;      // [W][tiles][128]
   uint32_t* d_bin_total = nullptr;   // [W][128]
+  uint32_t* d_bin_fill = nullptr;    // [W][128] the same for launches whose first pass is k_count, which fills it with atomics: zero between launches (k_sort_fine)
+  bool bin_fill_dirty = true;        // ... unless a launch was abandoned between the two: the next one clears it first
   uint32_t* d_coarse_ptr = nullptr;  // [W][129]
   uint32_t* d_tmp_val = nullptr;     // [W][stride] coarse-bin order
   uint8_t* d_tmp_fine = nullptr;     // [W][stride]
@@ -845,6 +847,13 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   // sparse launches: the same passes instantiated with one more argument (msm_kernels.h: SparseIdx) -- the count passes guard the indices, the
   // scatter passes write them in place of the positions
   const SparseIdx sp{p.indices, (uint32_t)ctx->n_bases, d_err};
+  // k_count leaves the prefix over tiles and the bin totals itself (bin_fill); the other first passes are followed by a scan kernel
+  const bool fused_scan = !wide && !bytes;
+  const uint32_t* bin_total = fused_scan ? ctx->d_bin_fill : ctx->d_bin_total;
+  if (fused_scan) {
+    if (ctx->bin_fill_dirty) HIP_TRY(ctx, hipMemsetAsync(ctx->d_bin_fill, 0, (size_t)MAXLW * NCOARSE * 4, st));
+    ctx->bin_fill_dirty = true;  // (until this launch's k_sort_fine is in the stream)
+  }
   if (wide) {
     dispatch<16, 17, 18, 19, 20>(p.wide_bits, [&](auto c) {
       constexpr int C = decltype(c)::value;
@@ -866,10 +875,10 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
     const int k = p.wbits == 16 ? 2 : p.wbits == 14 ? 1 : 0;
     if (p.sparse)
       hipLaunchKernelGGL(ctx->ops->count_split_sparse[k], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec, p.n * 8,
-                         ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, ctx->d_halves, d_err, merge_nb, sp);
+                         ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, (uint64_t*)nullptr, ctx->d_halves, d_err, merge_nb, sp);
     else
       hipLaunchKernelGGL(ctx->ops->count_split[k], grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin,
-                         p.w_count_vec, p.nvec, p.n * 8, ctx->d_counts, plane_out, plane_mode, p.planes ? ctx->d_negbits : nullptr,
+                         p.w_count_vec, p.nvec, p.n * 8, ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, p.planes ? ctx->d_negbits : nullptr,
                          p.planes ? nullptr : ctx->d_halves, d_err, merge_nb);
     d_scalars = ctx->d_halves;
   } else {
@@ -879,18 +888,18 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
         const size_t vec_stride = p.n * (NB ? narrow_width(NB) : 8);
         if (p.sparse)
           hipLaunchKernelGGL((k_count<C, SW, false, NB, SparseIdx>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec,
-                             p.nvec, vec_stride, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
+                             p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
         else
           hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
-                             vec_stride, ctx->d_counts, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
+                             vec_stride, ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
       }
     });
   }
   AFTER_KERNEL(ctx, "k_count", st);
   HIP_TRY(ctx, mark(1));
   if (bytes) hipLaunchKernelGGL(k_byte_scan, dim3(BYTE_BINS / 4, p.w_count), dim3(256), 0, st, ctx->d_counts, p.tiles, ctx->d_bin_total);
-  else hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, p.w_count), dim3(256), 0, st, ctx->d_counts, p.tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
-  AFTER_KERNEL(ctx, "k_scan_tiles", st);
+  else if (!fused_scan) hipLaunchKernelGGL(k_scan_tiles, dim3(NCOARSE / 4, p.w_count), dim3(256), 0, st, ctx->d_counts, p.tiles, ctx->d_bin_total);  // all 128 bins: the scatter scans them
+  if (!fused_scan) AFTER_KERNEL(ctx, "k_scan_tiles", st);
   HIP_TRY(ctx, mark(2));
   if (p.list_path) {  // shares of at most WIDE_SHARE_VWIN_MAX virtual windows: from the first pass's lists
     hipLaunchKernelGGL(k_scatter_list, dim3(p.tiles, p.w_count), dim3(256), 0, st, (const uint32_t*)ctx->d_val, (const uint32_t*)ctx->d_list_len, p.stride,
@@ -908,7 +917,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
     });
   } else if (p.planes) {
     hipLaunchKernelGGL(k_scatter_planes, dim3(p.tiles), dim3(256), 0, st, ctx->d_digits, halves ? ctx->d_negbits : (const uint64_t*)nullptr, p.n_sc, p.stride,
-                       p.tile_len, p.tiles, p.w_count, p.w_count_vec, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                       p.tile_len, p.tiles, p.w_count, p.w_count_vec, ctx->d_counts, bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
                        (uint32_t)ctx->n_bases, p.chunks, p.chunk_len, d_chunk_len);
   } else if (bytes) {
     dispatch<1, 2, -1, -2>(p.nb_kernel(), [&](auto b) {
@@ -925,11 +934,11 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
       const size_t vec_stride = p.n * (NB ? narrow_width(NB) : 8);
       if (p.sparse)
         hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB, SparseIdx>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
-                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
                            merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len, sp);
       else
         hipLaunchKernelGGL((k_scatter_coarse<C, SW, NB>), grid, block, gpos_bytes, st, d_scalars, p.n_sc, p.stride, p.tile_len, p.tiles, p.w_begin,
-                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
+                           p.w_count_vec, p.nvec, vec_stride, ctx->d_counts, bin_total, ctx->d_coarse_ptr, ctx->d_tmp_val, ctx->d_tmp_fine,
                            merge_nb, (uint32_t)p.n, halves ? (uint32_t)ctx->n_bases : 0u, p.chunks, p.chunk_len, d_chunk_len);
     });
   }
@@ -940,7 +949,9 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   // launch's main stream; skewed scalars that make such a bin after all take the sharers' own histograms (k_sort_fine's fallback path)
   // ... ADAPTIVELY (later in round 5): few distinct / small / equal scalars (witness vectors) fill huge bins at any size, and the fallback costs their
   // fine sort 2 - 2.5 x (profiles/r05_skew_hist.txt): k_sort_fine reports a huge bin in the slot's status word, and the 64 launches after such a
-  // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once)
+  // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once).  The report means SKEW:
+  // a bin of more than HUGE_BIN_MEANS mean bins -- the top window of endomorphism halves reaches two means, which at 2^20 is FINE_BIG, and used to
+  // keep the kernel in every launch of uniform scalars; such bins are shared without histograms at no measurable cost (msm_kernels.h: k_sort_fine)
   // Narrow scalars always run it and leave the credit alone: their top window holds only the recode's carry (U8: all entries) -- one huge bin by
   // construction, which says nothing about the context's later 32-byte launches
   if (bytes) {  // byte windows: the scatter has grouped the entries by slot already; only the SMVP's chunk table is left
@@ -959,8 +970,9 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
       part_hist = ctx->d_part_hist;
     }
     hipLaunchKernelGGL(k_sort_fine, dim3(p.ncoarse, p.w_count, FINE_SPLIT), dim3(256), 0, st, ctx->d_tmp_val, ctx->d_tmp_fine, p.stride, ctx->d_coarse_ptr,
-                       s.d_col_ptr, ctx->d_val, p.chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err);
+                       s.d_col_ptr, ctx->d_val, p.chunks, d_chunk_len, ctx->d_chunk_slot, part_hist, d_err, fused_scan ? ctx->d_bin_fill : (uint32_t*)nullptr);
     AFTER_KERNEL(ctx, "k_sort_fine", st);
+    if (fused_scan) ctx->bin_fill_dirty = false;
   }
   if (ctx->debug) {  // deterministic transpose for the stage read-back: every slot's run in ascending order
     hipLaunchKernelGGL(k_order_runs, dim3(blocks_for(p.n_entries, 256), p.w_count), dim3(256), 0, st, s.d_col_ptr, ctx->d_val, ctx->d_tmp_val, p.stride, p.half);
@@ -1335,6 +1347,7 @@ int msm_hip_ctx_create_curve(msm_hip_ctx** out, int device_id, int curve) {
   if (hipEventCreateWithFlags(&ctx->input_ready, hipEventDisableTiming) != hipSuccess) return fail(MSM_HIP_ERR_HIP);
   if ((rc = dev_alloc(ctx, ctx->d_counts, (size_t)MAXLW * MAX_TILES * NCOARSE))) return fail(rc);
   if ((rc = dev_alloc(ctx, ctx->d_bin_total, (size_t)MAXLW * NCOARSE))) return fail(rc);
+  if ((rc = dev_alloc(ctx, ctx->d_bin_fill, (size_t)MAXLW * NCOARSE))) return fail(rc);
   if ((rc = dev_alloc(ctx, ctx->d_coarse_ptr, (size_t)MAXLW * (NCOARSE + 1)))) return fail(rc);
   if ((rc = dev_alloc(ctx, ctx->d_err, 2))) return fail(rc);  // the error word, and the identity count of a base conversion
   // result slots (buckets, piece arrays, events) are set up by the first launch that uses them: setup_slot / ensure_work
@@ -1349,7 +1362,7 @@ void msm_hip_ctx_destroy(msm_hip_ctx* ctx) {
   if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
   for (hipStream_t r : ctx->reduce_stream)
     if (r) (void)hipStreamSynchronize(r);
-  void* bufs[] = {ctx->d_list_len, ctx->d_bases,   ctx->d_halves, ctx->d_batch_stage, ctx->d_scalar_conv, ctx->d_part_hist, ctx->d_digits, ctx->d_negbits, ctx->d_counts,     ctx->d_bin_total, ctx->d_coarse_ptr,
+  void* bufs[] = {ctx->d_list_len, ctx->d_bases,   ctx->d_halves, ctx->d_batch_stage, ctx->d_scalar_conv, ctx->d_part_hist, ctx->d_digits, ctx->d_negbits, ctx->d_counts,     ctx->d_bin_total, ctx->d_bin_fill, ctx->d_coarse_ptr,
                   ctx->d_tmp_val, ctx->d_tmp_fine, ctx->d_val,    ctx->d_chunk_slot, ctx->d_err,       ctx->d_stage, ctx->d_id_bits, ctx->d_mul, ctx->d_mul_table};
   for (void* b : bufs)
     if (b) (void)hipFree(b);

@@ -209,7 +209,7 @@ constexpr uint32_t ERRBIT_NONCANONICAL = 1u;
 constexpr uint32_t ERRBIT_NOT_ON_CURVE = 2u;
 constexpr uint32_t ERRBIT_SCALAR_CARRY = 4u;
 constexpr uint32_t ERRBIT_BAD_INDEX = 8u;  // a sparse launch's base index was not below the number of resident bases (SparseIdx)
-constexpr uint32_t INFOBIT_HUGE_BIN = 0x100u;  // not an error: the fine sort met a coarse bin beyond FINE_BIG (skewed scalars, or large n) -- the host's cue to run k_fine_hist
+constexpr uint32_t INFOBIT_HUGE_BIN = 0x100u;  // not an error: the fine sort met a coarse bin beyond FINE_BIG and beyond HUGE_BIN_MEANS mean bins (skewed scalars) -- the host's cue to run k_fine_hist
 
 // ------------------------------------------------------------------------------------------------ stage 0: bases
 // canonical wire bytes -> packed Montgomery affine (≙ decompose_scalars.template.wgsl:41-70, the point half)
@@ -416,8 +416,9 @@ __global__ void __launch_bounds__(256) k_mul_normalize(uint32_t* __restrict__ xy
 // The reference's transpose (transpose.template.wgsl:32-76) is a counting sort run by 16 threads.  Here it is a
 // two-level LDS counting sort over the 15-bit bucket slot, and the recode is fused into both of its global passes
 // (scalars are re-read instead of materialising 16 digit planes: 32 B per scalar either way):
-//   k_count          per tile of scalars: LDS histogram of the 128 coarse bins (slot >> 8) of every window
-//   k_scan_tiles     per (window, coarse bin): prefix over tiles, bin totals
+//   k_count          per tile of scalars: LDS histogram of the 128 coarse bins (slot >> 8) of every window; the tile's place inside every bin
+//                    (a returning atomic on the bin's fill) and, with the last tile, the bin totals
+//   k_scan_tiles     (wide and list passes only) per (window, coarse bin): prefix over tiles, bin totals
 //   k_scatter_coarse per tile: LDS-ranked scatter of (index | sign << 31, slot & 255) into coarse-bin order
 //   k_sort_fine      per (window, coarse bin): LDS counting sort over its 256 slots -> val_idxs + col_ptr
 // Order inside a slot is the arrival order of LDS atomics; the group sum does not depend on it.
@@ -651,7 +652,7 @@ __device__ __forceinline__ SparseIdx sparse_arg(SparseIdx s) { return s; }
 template <int C, int SW, bool SPLIT = false, int NB = 0, typename... Sparse>
 __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scalars, size_t n, uint32_t tile_len, uint32_t tiles,
                                                int w_begin, int w_count, int nvec, size_t vec_stride,
-                                               uint32_t* __restrict__ counts, uint16_t* __restrict__ planes, int plane_mode,
+                                               uint32_t* __restrict__ counts, uint32_t* __restrict__ bin_fill, uint16_t* __restrict__ planes, int plane_mode,
                                                uint64_t* __restrict__ negbits, uint32_t* __restrict__ halves_out,
                                                uint32_t* __restrict__ err, size_t merge_nb, Sparse... sparse) {
   static_assert(!SPLIT || SW == 4, "the split produces 4-word halves");
@@ -773,11 +774,29 @@ __global__ void __launch_bounds__(256) k_count(const uint32_t* __restrict__ scal
     if (bad_idx) atomicOr(err, ERRBIT_BAD_INDEX);
   }
   __syncthreads();
-  // counts[lw][tile][bin]
-  for (int i = tid; i < le_n * NCOARSE; i += 256)
-    counts[((size_t)(le0 + i / NCOARSE) * tiles + blockIdx.x) * NCOARSE + (i % NCOARSE)] = cnt[le0 * NCOARSE + i];
+  // counts[lw][tile][bin]: where this tile's entries of the bin start inside the bin -- the bin's fill when this workgroup arrives (one returning
+  // device-scope atomic per non-empty (window, bin): bin_fill[lw][bin], zero at launch, ends as the bin's size).  The prefix over tiles that
+  // k_scan_tiles made as a launch of its own (18 - 23 us of every launch's main stream for 2 MB of counters) is gone: the tiles of a bin then lie in
+  // ARRIVAL order instead of tile order, which nothing downstream asks about (the order inside a slot is the arrival order of LDS atomics already).
+  // No workgroup waits for another and none fences: the consumers are later kernels.  k_sort_fine zeroes the word again for the next launch.
+  // (four atomics in flight per thread -- the 8 windows of a launch of halves in one round trip, not four)
+  for (int i0 = tid; i0 < le_n * NCOARSE; i0 += 4 * 256) {
+    uint32_t at[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int i = i0 + k * 256;
+      const uint32_t c = i < le_n * NCOARSE ? cnt[le0 * NCOARSE + i] : 0u;
+      at[k] = c ? atomicAdd(&bin_fill[le0 * NCOARSE + i], c) : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int i = i0 + k * 256;
+      if (i < le_n * NCOARSE) counts[((size_t)(le0 + i / NCOARSE) * tiles + blockIdx.x) * NCOARSE + (i % NCOARSE)] = at[k];
+    }
+  }
 }
 
+// (The passes whose first kernel is not k_count -- wide and list shares -- still scan the tiles here.)
 // One wave per (window, coarse bin): in place, counts[lw][tile][bin] becomes the number of entries of that bin in earlier
 // tiles; bin_total[lw][bin] receives the bin's size.  (The 128 totals of a window are turned into bin starts by every
 // workgroup of k_scatter_coarse for itself: a last-block hand-off here needs agent-scope releases, i.e. L2 write-backs,
@@ -1904,6 +1923,7 @@ __device__ __forceinline__ void lds_count_only(uint32_t* counter, uint32_t key, 
 constexpr int FINE_SPLIT = 8;
 
 constexpr uint32_t FINE_BIG = 32768;  // (a multiple of FINE_CHUNK)
+constexpr uint32_t HUGE_BIN_MEANS = 4;  // a bin beyond FINE_BIG is reported as skew when it holds more than this many mean bins of its window
 static_assert(FINE_BIG % FINE_CHUNK == 0, "sub-ranges are whole chunks");
 
 // Histograms of the FINE_SPLIT sub-ranges of every coarse bin that exceeds FINE_BIG (part_hist[lw][bin][part][256]); launched
@@ -1939,7 +1959,8 @@ __global__ void __launch_bounds__(256) k_fine_hist(const uint8_t* __restrict__ t
 __global__ void __launch_bounds__(256) k_sort_fine(const uint32_t* __restrict__ tmp_val, const uint8_t* __restrict__ tmp_fine, size_t stride,
                                                    const uint32_t* __restrict__ coarse_ptr, uint32_t* __restrict__ col_ptr,
                                                    uint32_t* __restrict__ val_idxs, uint32_t chunks, const uint32_t* __restrict__ chunk_len_dev,
-                                                   uint32_t* __restrict__ chunk_slot, const uint32_t* __restrict__ part_hist, uint32_t* __restrict__ info) {
+                                                   uint32_t* __restrict__ chunk_slot, const uint32_t* __restrict__ part_hist, uint32_t* __restrict__ info,
+                                                   uint32_t* __restrict__ bin_fill) {
   const uint32_t chunk_len = *chunk_len_dev;
   __shared__ uint32_t hist[FINE];
   __shared__ uint32_t before[FINE];  // entries of every slot in front of this workgroup's sub-range
@@ -1956,6 +1977,14 @@ __global__ void __launch_bounds__(256) k_sort_fine(const uint32_t* __restrict__ 
   const uint32_t begin = coarse_ptr[(size_t)lw * (NCOARSE + 1) + bin], end = coarse_ptr[(size_t)lw * (NCOARSE + 1) + bin + 1];
   const bool big = end - begin > FINE_BIG;
   if (!big && part != 0) return;
+  // k_count's fill word of this bin (null: the launch's first pass was another kernel): read for the last time by k_scatter_coarse, zero for the next launch
+  if (bin_fill && part == 0 && tid == 0) bin_fill[lw * NCOARSE + bin] = 0;
+  // The host's cue for k_fine_hist (INFOBIT_HUGE_BIN) is for SKEWED scalars: a bin beyond FINE_BIG that also holds more than HUGE_BIN_MEANS times
+  // the window's mean bin.  The top window of endomorphism halves is not uniform -- its bins reach twice the mean, which at 2^20 points is FINE_BIG
+  // itself -- and used to keep the histograms on for every launch of uniform scalars (22 us each).  Such a bin costs its sharers little without them:
+  // each sweeps at most 4 mean bins of one-byte keys and scatters an eighth of it, about what the workgroup of an ordinary bin does in its two passes.
+  const uint32_t win_total = coarse_ptr[(size_t)lw * (NCOARSE + 1) + NCOARSE];  // (the window's first bin starts at 0)
+  const bool skew_cue = big && (uint64_t)(end - begin) * gridDim.x > (uint64_t)HUGE_BIN_MEANS * win_total;
   // this workgroup's sub-range [my_begin, my_end): the whole bin, or one of FINE_SPLIT pieces (multiples of FINE_CHUNK)
   uint32_t my_begin = begin, my_end = end;
   if (big) {
@@ -1989,7 +2018,7 @@ __global__ void __launch_bounds__(256) k_sort_fine(const uint32_t* __restrict__ 
     }
   } else if (part_hist) {
     // the sub-range histograms were made by k_fine_hist: sum them (and the ones in front of this workgroup's sub-range)
-    if (tid == 0 && part == 0) atomicOr(info, INFOBIT_HUGE_BIN);
+    if (tid == 0 && part == 0 && skew_cue) atomicOr(info, INFOBIT_HUGE_BIN);
     const uint32_t* ph = part_hist + ((size_t)lw * NCOARSE + bin) * FINE_SPLIT * FINE + tid;
     uint32_t all = 0, front = 0;
 #pragma unroll
@@ -2001,7 +2030,7 @@ __global__ void __launch_bounds__(256) k_sort_fine(const uint32_t* __restrict__ 
     hist[tid] = all;
     before[tid] = front;
   } else {
-    if (tid == 0 && part == 0) atomicOr(info, INFOBIT_HUGE_BIN);  // (a huge bin without k_fine_hist's histograms: every sharer sweeps the bin up to its own end)
+    if (tid == 0 && part == 0 && skew_cue) atomicOr(info, INFOBIT_HUGE_BIN);  // (a huge bin without k_fine_hist's histograms: every sharer sweeps the bin up to its own end)
     // FINE_CHUNK entries per sweep step, 16 independent byte loads per thread in flight; a step lies wholly in front of
     // the sub-range or not (my_begin - begin is a multiple of FINE_CHUNK), so every entry is counted once
     uint32_t f[FINE_PER], g[FINE_PER];  // double buffered: the loads of step k + 1 are in flight while step k is counted
@@ -2017,8 +2046,14 @@ __global__ void __launch_bounds__(256) k_sort_fine(const uint32_t* __restrict__ 
         g[j] = i < end ? tf[i] : 0xffffffffu;
       }
       uint32_t* counter = base < my_begin ? before : hist;
+      if (skew_cue) {  // (block-uniform) many entries per slot: wave-aggregated counting
 #pragma unroll
-      for (int j = 0; j < FINE_PER; j++) lds_count_only(counter, f[j] & 0xffu, f[j] != 0xffffffffu);
+        for (int j = 0; j < FINE_PER; j++) lds_count_only(counter, f[j] & 0xffu, f[j] != 0xffffffffu);
+      } else {  // a bin of a few means: counted as an ordinary bin is
+#pragma unroll
+        for (int j = 0; j < FINE_PER; j++)
+          if (f[j] != 0xffffffffu) atomicAdd(&counter[f[j]], 1u);
+      }
 #pragma unroll
       for (int j = 0; j < FINE_PER; j++) f[j] = g[j];
     }
