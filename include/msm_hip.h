@@ -305,6 +305,34 @@ int msm_hip_mul_each_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t n,
 int msm_hip_mul_base(msm_hip_ctx* ctx, size_t base_index, const uint8_t* scalars_host, size_t n, uint8_t* out_xy_host, uint32_t flags);
 int msm_hip_mul_base_device(msm_hip_ctx* ctx, size_t base_index, const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags);
 
+/* ---- group FFT over the resident bases: a monomial SRS into the Lagrange basis, on the device.  (Added within ABI version 7.)
+ *        out[i] = c * sum_{j < n} omega^(i j) * P_j     n = 2^log_n, P_j the first n resident bases, i = 0 .. n-1 in natural order
+ *        c = 1, or n^(-1) mod r with MSM_HIP_FFT_SCALE_INV_N
+ *      With P_j = tau^j G (msm_hip_mul_base), omega^(-1) and the scale flag, out[i] is L_i(tau) G: the SRS in the Lagrange basis, over which a polynomial
+ *      held as its n evaluations is committed by one MSM.  The definition holds for bases of order r (omega is an element of the scalar field: on a
+ *      curve with a cofactor, bases outside the subgroup of order r give the integer multiples of the plain ladder, which no longer form a transform).
+ *      - The plain records 0 .. n-1 are read, which every base mode keeps; the resident bases are not modified.  Bases flagged by
+ *        MSM_HIP_BASES_ZERO_IS_IDENTITY are identities on input.  The scalar format of the context does not matter.
+ *      - omega: 32 bytes, a canonical little-endian integer below r, a PRIMITIVE n-th root of unity: omega^(n/2) == r - 1 for log_n >= 1, omega == 1
+ *        for log_n == 0 (checked on the host with log_n - 1 squarings).  Grumpkin's scalar field has 2-adicity 1: only log_n <= 1 can pass there; the
+ *        other G1 curves allow 28 (BN254) or 32.  log_n <= 28 throughout.
+ *      - Output: n records exactly as msm_hip_mul_each writes them (x || y canonical, the identity as the all-zero record); the _device form writes
+ *        device memory in place (16-byte aligned).  log_n == 0 copies the single base out.
+ *      - flags: MSM_HIP_FFT_SCALE_INV_N, and MSM_HIP_MUL_BASES_ORDER_R with the meaning it has for msm_hip_mul_each (which ladder multiplies by the
+ *        twiddles: the endomorphism's on the curves of prime order, on BLS12-381 G1 only with that flag).
+ *      - Execution: a radix-2 decimation-in-time transform, log_n stages of n / 2 butterflies (a, b) -> (a + w b, a - w b) on the main stream, every stage
+ *        made affine again with the shared inversions of msm_hip_mul_each; the first stage's twiddles are all 1 (additions only), the scale is one more
+ *        ladder pass.  (n / 2) (log_n - 1) scalar multiplications in all (+ n with the scale).  The call returns when the output is complete.
+ *        Device scratch kept by the context: 4 coordinates per element (128 B on the 254 / 255-bit curves: 128 MiB at n = 2^20, 512 MiB at 2^22;
+ *        192 B on BLS12-381 G1), + one point record per element for the host form, + 16 B per element for the n / 2 twiddles, which are cached under
+ *        the key (log_n, omega) and survive msm_hip_set_bases.
+ *      - Errors, all before anything is enqueued (out is untouched): MSM_HIP_ERR_NO_BASES before set_bases; MSM_HIP_ERR_INVALID_ARG for 2^log_n >
+ *        n_bases, log_n < 0, an unknown flag bit, a null or misaligned out, a null omega, omega >= r, omega not primitive, and a context on a G2 curve
+ *        (the Lagrange SRS is a G1 object); MSM_HIP_ERR_NO_DEVICE with no device. ---- */
+#define MSM_HIP_FFT_SCALE_INV_N 2u
+int msm_hip_bases_fft(msm_hip_ctx* ctx, const uint8_t omega[32], int log_n, uint8_t* out_xy_host, uint32_t flags);
+int msm_hip_bases_fft_device(msm_hip_ctx* ctx, const uint8_t omega[32], int log_n, void* out_xy_dev, uint32_t flags);
+
 /* ---- batch: `batch` independent scalar vectors (batch x n x 32 B, contiguous, device memory) over the resident bases;
  *      out: batch x 96 B.  Internally a software pipeline over the result slots (BASELINE.json config 5: many MSMs over
  *      one shared base). ---- */
@@ -507,6 +535,9 @@ int msm_hip_test_oneshot_parts(int parts, size_t min_points);
  * broadcast), 1 the plain ladder, 2 the endomorphism's, 3 the fixed-base table the context already held, 4 the table, built by that call;
  * table_bits: the table's digit width C (0: a ladder ran); chunk: outputs per shared inversion.  Null pointers are skipped. */
 int msm_hip_test_mul_last(const msm_hip_ctx* ctx, int* path, int* table_bits, int* chunk);
+/* test hook: what the last msm_hip_bases_fft call of the context ran -- stages: its butterfly stages (log_n); ladder: 0 none (log_n <= 1 without
+ * the scale: additions only), 1 the plain ladder, 2 the endomorphism's, for the twiddled stages and the scale pass alike */
+int msm_hip_test_fft_last(const msm_hip_ctx* ctx, int* stages, int* ladder);
 /* test hook: the table policy of msm_hip_mul_base -- table_min_n != 0: the table runs exactly when n >= table_min_n (1 forces it, SIZE_MAX
  * forbids it); table_bits != 0 (4 .. 16): with that digit width instead of the cost model's.  0, 0 restores the policy. */
 int msm_hip_test_mul_policy(msm_hip_ctx* ctx, size_t table_min_n, int table_bits);

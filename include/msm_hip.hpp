@@ -199,6 +199,17 @@ class MsmContext {
   void mul_base_device(size_t base_index, const void* scalars_dev, size_t n, void* out_xy_dev, uint32_t flags = 0) {
     check(msm_hip_mul_base_device(ctx_, base_index, scalars_dev, n, out_xy_dev, flags), "msm_hip_mul_base_device");
   }
+  /// Group FFT over the first 2^log_n resident bases (msm_hip_bases_fft): out[i] = c * sum_j omega^(i j) * base j, 2^log_n affine records as mul_each
+  /// writes them.  `omega`: 32 bytes, a primitive 2^log_n-th root of unity mod r; `flags`: MSM_HIP_FFT_SCALE_INV_N (c = 1 / n), MSM_HIP_MUL_BASES_ORDER_R.
+  /// omega^-1 with the scale flag turns a monomial SRS into the Lagrange basis.  G1 curves only.
+  std::vector<uint8_t> bases_fft(const uint8_t omega[32], int log_n, uint32_t flags = 0) {
+    std::vector<uint8_t> out((log_n >= 0 && log_n <= 28 ? (size_t)1 << log_n : 0) * point_bytes());
+    check(msm_hip_bases_fft(ctx_, omega, log_n, out.data(), flags), "msm_hip_bases_fft");
+    return out;
+  }
+  void bases_fft_device(const uint8_t omega[32], int log_n, void* out_xy_dev, uint32_t flags = 0) {
+    check(msm_hip_bases_fft_device(ctx_, omega, log_n, out_xy_dev, flags), "msm_hip_bases_fft_device");
+  }
   G1 finish(int slot) {
     G1 r;
     check(msm_hip_finish(ctx_, slot, r.xyz.data()), "msm_hip_finish");

@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     compute_msm,
     lib,
     points_to_bytes,
+    root_of_unity,
     run_webgpu_msm,
     sample_points,
     sample_scalars,
@@ -24,4 +25,4 @@ from .api import (  # noqa: F401
 from .build import build  # noqa: F401
 
 __all__ = ["G1", "MsmContext", "MultiGpuMsm", "MsmHipError", "compute_msm", "run_webgpu_msm", "points_to_bytes", "scalars_to_bytes",
-           "sample_points", "sample_scalars", "build", "lib", "BASES_ZERO_IS_IDENTITY", "bytes_to_points"]
+           "sample_points", "sample_scalars", "build", "lib", "BASES_ZERO_IS_IDENTITY", "bytes_to_points", "root_of_unity"]

@@ -26,6 +26,25 @@ CURVES = {"bn254": (0, P), "grumpkin": (1, R_BN254), "pallas": (2, PALLAS_P), "v
           "bn254_g2": (5, P), "bls12_381_g2": (6, BLS12_381_P)}  # G2: coordinates in Fq2 = Fq[u] / (u^2 + 1), an element on the wire is c0 || c1
 
 
+# group order r (the scalar field) of the G1 curves: what msm_hip_bases_fft's omega lives in
+BLS12_381_R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+SCALAR_FIELDS = {"bn254": R_BN254, "grumpkin": P, "pallas": VESTA_P, "vesta": PALLAS_P, "bls12_381": BLS12_381_R}
+
+
+def root_of_unity(curve, log_n, inverse=False):
+    """A primitive 2^log_n-th root of unity of a G1 curve's scalar field (its inverse with inverse=True), as an integer: the smallest quadratic
+    non-residue raised to (r - 1) / 2^log_n.  Raises ValueError where 2^log_n does not divide r - 1 (Grumpkin: log_n > 1)."""
+    r = SCALAR_FIELDS[curve]
+    log_n = int(log_n)
+    if log_n < 0 or (r - 1) % (1 << log_n):
+        raise ValueError("the scalar field of %s has no root of unity of order 2^%d" % (curve, log_n))
+    g = 2
+    while pow(g, (r - 1) // 2, r) != r - 1:
+        g += 1
+    w = pow(g, (r - 1) >> log_n, r)
+    return pow(w, r - 2, r) if inverse else w
+
+
 def coord_bytes(curve):
     """Bytes of a coordinate on a curve's wire: 32; 48 for BLS12-381; 64 / 96 for BN254 / BLS12-381 G2 (an Fq2 element) -- points 2 x, Jacobian
     records 3 x that."""
@@ -88,6 +107,9 @@ def lib():
         L.msm_hip_test_mul_last.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
         L.msm_hip_test_mul_ladder.argtypes = [vp, i]
         L.msm_hip_test_mul_policy.argtypes = [vp, sz, i]
+        L.msm_hip_bases_fft.argtypes = [vp, u8p, i, u8p, C.c_uint32]
+        L.msm_hip_bases_fft_device.argtypes = [vp, u8p, i, vp, C.c_uint32]
+        L.msm_hip_test_fft_last.argtypes = [vp, C.POINTER(i), C.POINTER(i)]
         L.msm_hip_wait_stream.argtypes = [vp, vp]
         L.msm_hip_finish.argtypes = [vp, i, u8p]
         L.msm_hip_run_windows_device.argtypes = [vp, vp, sz, i, i, vp]
@@ -479,6 +501,53 @@ class MsmContext:
     def mul_force_ladder(self, ladder):
         """test hook msm_hip_test_mul_ladder: 0 the policy, 1 always the plain ladder, 2 always the endomorphism's"""
         _check(lib().msm_hip_test_mul_ladder(self._h, int(ladder)), "msm_hip_test_mul_ladder")
+
+    # -- group FFT over the resident bases: monomial SRS -> Lagrange basis
+    FFT_SCALE_INV_N = 2  # MSM_HIP_FFT_SCALE_INV_N
+
+    def bases_fft(self, omega, log_n=None, scale=False, bases_order_r=False, out=None, device=False):
+        """[c * sum_j omega^(i j) * bases[j]] for i < n = 2^log_n over the first n resident bases (msm_hip_bases_fft): n affine records as mul_each
+        writes them, in natural order.  omega: an integer (or its 32 little-endian bytes), a primitive n-th root of unity of the scalar field
+        (root_of_unity).  log_n: None takes all the bases, whose number must then be a power of two.  scale: c = 1 / n instead of 1.
+        bases_order_r: as for mul_each.  Returns bytes; with device=True a new CUDA uint8 tensor [n, pb]; with `out`, that preallocated tensor."""
+        if log_n is None:
+            if self.n_bases == 0 or self.n_bases & (self.n_bases - 1):
+                raise ValueError("log_n=None needs a power-of-two number of resident bases, not %d" % self.n_bases)
+            log_n = self.n_bases.bit_length() - 1
+        log_n = int(log_n)
+        w = bytes(omega) if isinstance(omega, (bytes, bytearray)) else int(omega).to_bytes(32, "little")
+        if len(w) != 32:
+            raise ValueError("omega must be an integer or 32 bytes")
+        flags = (self.FFT_SCALE_INV_N if scale else 0) | (self.MUL_BASES_ORDER_R if bases_order_r else 0)
+        n = 1 << log_n if 0 <= log_n <= 28 else 0
+        if out is not None or device:
+            if out is None:
+                out = torch.empty((n, self.pb), dtype=torch.uint8, device="cuda:%d" % self.device)
+            elif not (isinstance(out, torch.Tensor) and out.is_cuda):
+                raise TypeError("out must be a CUDA(HIP) uint8 tensor")
+            elif out.dtype != torch.uint8 or tuple(out.shape) != (n, self.pb) or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor of shape (%d, %d)" % (n, self.pb))
+            self._order_after_torch(out)
+            _check(lib().msm_hip_bases_fft_device(self._h, w, log_n, out.data_ptr() if n else None, flags), "msm_hip_bases_fft_device")
+            return out
+        buf = C.create_string_buffer(self.pb * max(n, 1))
+        _check(lib().msm_hip_bases_fft(self._h, w, log_n, buf, flags), "msm_hip_bases_fft")
+        return buf.raw[:self.pb * n]
+
+    def lagrange_bases(self, log_n=None, bases_order_r=False, out=None, device=False):
+        """The resident monomial SRS [tau^j G] in the Lagrange basis of the 2^log_n-th roots of unity: L_i(tau) G = (1 / n) sum_j omega^(-i j) tau^j G
+        for omega = root_of_unity(curve, log_n) -- bases_fft(omega^-1, scale=True)."""
+        if log_n is None:
+            if self.n_bases == 0 or self.n_bases & (self.n_bases - 1):
+                raise ValueError("log_n=None needs a power-of-two number of resident bases, not %d" % self.n_bases)
+            log_n = self.n_bases.bit_length() - 1
+        return self.bases_fft(root_of_unity(self.curve, log_n, inverse=True), log_n, scale=True, bases_order_r=bases_order_r, out=out, device=device)
+
+    def fft_last(self):
+        """(stages, ladder) of the last bases_fft call (test hook msm_hip_test_fft_last): ladder 0 none, 1 plain, 2 endomorphism"""
+        v = [C.c_int(), C.c_int()]
+        _check(lib().msm_hip_test_fft_last(self._h, *[C.byref(x) for x in v]), "msm_hip_test_fft_last")
+        return tuple(x.value for x in v)
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

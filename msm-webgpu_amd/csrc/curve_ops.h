@@ -59,13 +59,20 @@ struct CurveOps {
   bool (*combine_wide)(const uint8_t*, const uint8_t*, int, uint8_t*);
   bool (*combine_wide_pairs)(const uint8_t*, int, uint8_t*);
   int (*to_affine64)(const uint8_t*, uint8_t*);
+  // group FFT over the resident bases (msm_hip_bases_fft): k_fft_stage<0 / 1 / 2> (additions only, plain ladder, endomorphism), k_fft_normalize,
+  // k_fft_scale<1 / 2>; null in the G2 units, where the transform is not offered.  fr_r: the group order r, 8 words (the host's twiddle arithmetic)
+  void (*fft_stage[3])(const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, int, int, uint32_t, const uint64_t*);
+  void (*fft_normalize)(uint32_t*, const uint32_t*, uint32_t*, size_t);
+  void (*fft_scale[2])(const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, size_t);
+  const uint32_t* fr_r;
 };
 #define MSM_CURVE_OPS(K, F)                                                                                                              \
   {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_mul_each<false>, K::k_mul_each<true>}, K::k_mul_normalize, F::SMUL_CHUNK, K::k_mul_table_scalars, K::k_mul_fixed, F::SMUL_R_BITS, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
    {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
    K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
    K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \
-   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64}
+   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64, \
+   {K::k_fft_stage<0>, K::k_fft_stage<1>, K::k_fft_stage<2>}, K::k_fft_normalize, {K::k_fft_scale<1>, K::k_fft_scale<2>}, F::FR_R32}
 
 // A G2 unit (coordinates in Fq2, csrc/fq2.h): the same table (its point sampler draws multiples of the subgroup's generator)
 #define MSM_CURVE_OPS_FQ2(K, F)                                                                                                          \
@@ -73,7 +80,8 @@ struct CurveOps {
    {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
    K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
    K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \
-   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64}
+   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64, \
+   {nullptr, nullptr, nullptr}, nullptr, {nullptr, nullptr}, F::FR_R32}
 
 // accessors of the separately compiled units (hidden: not part of the C ABI)
 extern "C" {

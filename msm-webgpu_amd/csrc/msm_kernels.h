@@ -408,6 +408,64 @@ __global__ void __launch_bounds__(256) k_mul_normalize(uint32_t* __restrict__ xy
   smul_norm_backward(xy, zbuf, prefix, first, 256, end, fq_inv(prod));
 }
 
+#ifndef MSM_FQ2
+// ------------------------------------------------------------------------------------------------ group FFT over the resident bases
+// msm_hip_bases_fft: out[i] = c * sum_j omega^(i j) P_j over the first n = 2^log_n plain records, a radix-2 decimation-in-time transform whose
+// elements are curve points (csrc/scalar_mul.h, smul_butterfly).  log_n stages; between two stages the elements are packed Montgomery affine
+// records like the resident bases, the identity as the all-zero record:
+//   k_fft_stage<LADDER>  one butterfly per lane, n / 2 lanes.  Stage s pairs elements ia = (k >> s) 2^(s+1) + j and ib = ia + 2^s, j = k mod 2^s,
+//                        with the twiddle omega^(j n / 2^(s+1)) (entry j << (log_n - 1 - s) of the table of the n / 2 powers of omega), and
+//                        leaves a + w b and a - w b as Jacobian records at ia and ib: X' || Y' in the record, Z in zbuf (smul_store_jacobian).
+//                        A lane reads and writes its own two elements only, so a stage may run in place (src == dst).  first != 0: element i is
+//                        resident base bitrev(i), an identity if `id_bits` marks it; every twiddle of that stage is 1: LADDER = 0, additions only.
+//   k_fft_normalize      k_mul_normalize's walk with the backward pass that keeps Montgomery records (smul_norm_backward<true>)
+//   k_fft_scale<LADDER>  dst[i] = k * src[i] for one broadcast scalar (the 1 / n of MSM_HIP_FFT_SCALE_INV_N), again as Jacobian records
+// The last pass of a call is normalised by k_mul_normalize, which writes wire records.
+template <int LADDER>
+__global__ void __launch_bounds__(256) k_fft_stage(const uint32_t* src, uint32_t* dst, uint32_t* zbuf, const uint32_t* __restrict__ twiddles, int log_n,
+                                                   int stage, uint32_t first, const uint64_t* __restrict__ id_bits) {
+  const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= ((size_t)1 << (log_n - 1))) return;
+  const size_t j = k & (((size_t)1 << stage) - 1);
+  const size_t ia = ((k >> stage) << (stage + 1)) + j, ib = ia + ((size_t)1 << stage);
+  size_t ra = ia, rb = ib;
+  bool a_id = false, b_id = false;
+  if (first) {
+    ra = __brev((uint32_t)ia) >> (32 - log_n);
+    rb = __brev((uint32_t)ib) >> (32 - log_n);
+    if (id_bits != nullptr) {
+      a_id = ((id_bits[ra >> 6] >> (ra & 63u)) & 1u) != 0;
+      b_id = ((id_bits[rb >> 6] >> (rb & 63u)) & 1u) != 0;
+    }
+  }
+  uint32_t w[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (LADDER != SMUL_LADDER_NONE) ld8(twiddles + (j << (log_n - 1 - stage)) * 8, w);
+  g1_xyzz sum, diff;
+  smul_butterfly<LADDER>(src + ra * PT_WORDS, a_id, src + rb * PT_WORDS, b_id, w, sum, diff);
+  smul_store_jacobian(dst, zbuf, ia, sum);
+  smul_store_jacobian(dst, zbuf, ib, diff);
+}
+
+__global__ void __launch_bounds__(256) k_fft_normalize(uint32_t* __restrict__ xy, const uint32_t* __restrict__ zbuf, uint32_t* __restrict__ prefix, size_t n) {
+  const size_t block_first = (size_t)blockIdx.x * (256 * SMUL_CHUNK);
+  const size_t first = block_first + threadIdx.x;
+  const size_t block_end = block_first + 256 * SMUL_CHUNK;
+  const size_t end = block_end < n ? block_end : n;
+  if (first >= end) return;
+  const fq prod = smul_norm_forward(zbuf, prefix, first, 256, end);
+  smul_norm_backward<true>(xy, zbuf, prefix, first, 256, end, fq_inv(prod));
+}
+
+template <int LADDER>
+__global__ void __launch_bounds__(256) k_fft_scale(const uint32_t* src, uint32_t* dst, uint32_t* zbuf, const uint32_t* __restrict__ scalar, size_t n) {  // src may alias dst (element-wise)
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k[8];
+  ld8(scalar, k);
+  smul_store_jacobian(dst, zbuf, i, smul_twiddle<LADDER>(src + i * PT_WORDS, false, k));
+}
+#endif
+
 // ------------------------------------------------------------------------------------------------ stage 1+2: recode + sort
 // Signed 16-bit digit recode (≙ decompose_scalars.template.wgsl:83-112, CPU model test/utils.rs:121-161):
 //   d = raw + carry; if d >= 2^15 { d -= 2^16; carry = 1 }  -- computed per window without the serial carry chain.  Signed-magnitude code = sign << 15 | (|d| & 0x7fff):

@@ -237,7 +237,9 @@ FQ_HD fq smul_norm_forward(const uint32_t* z, uint32_t* prefix, size_t first, si
 }
 
 // Backward pass: `inv` = 1 / (the chunk's product).  Record i of `xy` (X' || Y') becomes the affine point x || y as canonical integers,
-// or the all-zero record for the identity.
+// or the all-zero record for the identity.  MONT (the stages of msm_hip_bases_fft): x || y stay in Montgomery form, canonical -- a packed record
+// like the resident bases, the identity still the all-zero record -- and the two conversions are saved: 6 products backward.
+template <bool MONT = false>
 FQ_HD void smul_norm_backward(uint32_t* xy, const uint32_t* z, const uint32_t* prefix, size_t first, size_t stride, size_t end, fq inv) {
   int count = 0;
   while (count < SMUL_CHUNK && first + (size_t)count * stride < end) count++;
@@ -255,9 +257,44 @@ FQ_HD void smul_norm_backward(uint32_t* xy, const uint32_t* z, const uint32_t* p
     inv = fq_mul(inv, zj);
     const fq zi2 = fq_sqr(zi);
     const fq zi3 = fq_mul(zi2, zi);
-    smul_st(rec, fq_from_mont(fq_mul(smul_ld(rec), zi2)));
-    smul_st(rec + FQ_WORDS, fq_from_mont(fq_mul(smul_ld(rec + FQ_WORDS), zi3)));
+    const fq x = fq_mul(smul_ld(rec), zi2), y = fq_mul(smul_ld(rec + FQ_WORDS), zi3);
+    smul_st(rec, MONT ? fq_canonical(x) : fq_from_mont(x));
+    smul_st(rec + FQ_WORDS, MONT ? fq_canonical(y) : fq_from_mont(y));
   }
+}
+
+// ---- the butterfly of the group FFT over the resident bases (msm_hip_bases_fft; kernels: msm_kernels.h, k_fft_stage)
+// Operands are packed Montgomery affine records (x || y, canonical) in which the ALL-ZERO record is the identity ((0, 0) is on none of the curves);
+// `*_identity` marks an operand as the identity whatever its record holds (a resident base flagged in the identity bitmap).
+// LADDER: 0 none (the twiddle is 1: the first stage), 1 smul_plain over the bits of r, 2 smul_endo -- chosen per call as msm_hip_mul_each chooses.
+constexpr int SMUL_LADDER_NONE = 0, SMUL_LADDER_PLAIN = 1, SMUL_LADDER_ENDO = 2;
+
+// t = w * (the point of record b), w < r.  An identity operand runs no ladder.
+template <int LADDER>
+FQ_HD g1_xyzz smul_twiddle(const uint32_t* b, bool b_identity, const uint32_t w[8]) {
+  if (b_identity) return g1_identity();
+  const fq px = smul_ld(b), py = smul_ld(b + FQ_WORDS);
+  if (smul_all_zero(px) && smul_all_zero(py)) return g1_identity();
+  if (LADDER == SMUL_LADDER_NONE) return g1_from_affine(px, py);
+  return LADDER == SMUL_LADDER_ENDO ? smul_endo(px, py, w) : smul_plain(px, py, w, SMUL_R_BITS);
+}
+
+// sum = a + w b, diff = a - w b.  Record a is loaded only after the ladder has returned, so the ladder's live state and the butterfly's never
+// overlap.  Both results come from mixed additions INTO t = w b: sum = t + a, diff = -(t + (-a)), so that a == t (a doubling and the identity),
+// a == -t (the identity and a doubling) and t the identity (a and a, from g1_madd's empty accumulator) are the branches g1_madd already has;
+// a the identity is met here: sum = t, diff = -t.
+template <int LADDER>
+FQ_HD void smul_butterfly(const uint32_t* a, bool a_identity, const uint32_t* b, bool b_identity, const uint32_t w[8], g1_xyzz& sum, g1_xyzz& diff) {
+  sum = smul_twiddle<LADDER>(b, b_identity, w);
+  diff = sum;
+  if (!a_identity) {
+    const fq ax = smul_ld(a), ay = smul_ld(a + FQ_WORDS);
+    if (!(smul_all_zero(ax) && smul_all_zero(ay))) {
+      smul_madd(sum, ax, ay);
+      smul_madd(diff, ax, fq_neg_canonical(ay));
+    }
+  }
+  if (!diff.inf) diff.y = fq_sub<3>(fq_zero(), fq_tidy(diff.y));  // Y < 5p -> exact, < 2p -> -Y < 3p, normal
 }
 
 }  // namespace MSM_FIELD_NS
