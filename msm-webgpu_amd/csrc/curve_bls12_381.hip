@@ -14,9 +14,8 @@
 #define MSM_CURVE_CONSTANTS "bls12_381_constants.h"
 #define MSM_FQ_ASM_HEADER "fq28x14_asm.h"
 #include "curve_unit.h"
-#include "curve_ops.h"
 
 extern "C" const CurveOps* msm_hip_curve_ops_bls12_381(void) {
-  static const CurveOps ops = MSM_CURVE_OPS(msmk_bls12_381, bls12_381);
+  static const CurveOps ops = msmk_bls12_381::curve_ops_table();
   return &ops;
 }

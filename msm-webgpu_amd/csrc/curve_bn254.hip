@@ -1,0 +1,19 @@
+// BN254 G1 (the reference's curve; kernel namespace msmk) as its own translation unit of libmsm_hip.so: the arithmetic headers and the
+// kernels instantiated with this curve's constants (csrc/curve_unit.h, csrc/curve_select.h) and the table through which msm_hip.hip
+// reaches them (csrc/curve_ops.h; filled by msm_kernels.h, curve_ops_table).
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/msm_hip.h"
+#define MSM_FIELD_NS bn254
+#define MSM_KERNEL_NS msmk
+#define MSM_CURVE_CONSTANTS "bn254_constants.h"
+#include "curve_unit.h"
+
+extern "C" const CurveOps* msm_hip_curve_ops_bn254(void) {
+  static const CurveOps ops = msmk::curve_ops_table();
+  return &ops;
+}

@@ -28,9 +28,8 @@
 #include "glv.h"
 #include "msm_kernels.h"
 #undef MSM_CURVE_UNIT
-#include "curve_ops.h"
 
 extern "C" const CurveOps* msm_hip_curve_ops_bn254_g2(void) {
-  static const CurveOps ops = MSM_CURVE_OPS_FQ2(msmk_bn254_g2, bn254_g2);
+  static const CurveOps ops = msmk_bn254_g2::curve_ops_table();
   return &ops;
 }

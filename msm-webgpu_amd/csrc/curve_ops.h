@@ -1,12 +1,12 @@
 // The table through which the host code (msm_hip.hip) reaches one curve's kernels and host arithmetic.  Every curve is compiled as its
-// own translation unit (curve_<name>.hip: csrc/curve_unit.h instantiated with that curve's constants; BN254's unit lives in msm_hip.hip
-// itself, which also takes the field-independent kernels and the layout constants from it) so that the units build in parallel; a unit
-// hands its table over through one accessor.
+// own translation unit (curve_<name>.hip: csrc/curve_unit.h instantiated with that curve's constants) so that the units build in parallel;
+// a unit fills its table by name (msm_kernels.h: curve_ops_table) and hands it over through one accessor.  The recode and the sort are not
+// in it: no field enters them, and msm_hip.hip compiles and launches them itself (sort_kernels.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
-struct SparseIdx;  // (msm_kernels.h)
+#include "msm_layout.h"  // SparseIdx
 
 // What differs between the curves: the kernels that do field arithmetic, and the host's window combine.  A context holds one.
 struct CurveOps {
@@ -23,9 +23,9 @@ struct CurveOps {
   void (*mul_table_scalars)(int, size_t, size_t, uint32_t*);
   void (*mul_fixed)(const uint32_t*, int, const uint32_t*, size_t, uint32_t*, uint32_t*, uint32_t*);
   int r_bits;
-  // k_count<C, 4, true> for C = 12 / 14 / 16: the first sort pass of endomorphism launches, which splits the scalars itself (csrc/glv.h)
+  // k_count<C, 4, glv_split_fn> (recode.h over the unit's split functor) for C = 12 / 14 / 16: the first sort pass of endomorphism launches, which splits the scalars itself (csrc/glv.h)
   void (*count_split[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t);
-  // ... and of sparse endomorphism launches (k_count<C, 4, true, 0, SparseIdx>: the split of scalar j, whose base is idx[j])
+  // ... and of sparse endomorphism launches (k_count<C, 4, glv_split_fn, 0, SparseIdx>: the split of scalar j, whose base is idx[j])
   void (*count_split_sparse[3])(const uint32_t*, size_t, uint32_t, uint32_t, int, int, int, size_t, uint32_t*, uint32_t*, uint16_t*, int, uint64_t*, uint32_t*, uint32_t*, size_t,
                                 SparseIdx);
   void (*scalars_from_mont256)(const uint32_t*, uint32_t*, size_t, uint32_t*);
@@ -66,25 +66,9 @@ struct CurveOps {
   void (*fft_scale[2])(const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, size_t);
   const uint32_t* fr_r;
 };
-#define MSM_CURVE_OPS(K, F)                                                                                                              \
-  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_mul_each<false>, K::k_mul_each<true>}, K::k_mul_normalize, F::SMUL_CHUNK, K::k_mul_table_scalars, K::k_mul_fixed, F::SMUL_R_BITS, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
-   {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
-   K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
-   K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \
-   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64, \
-   {K::k_fft_stage<0>, K::k_fft_stage<1>, K::k_fft_stage<2>}, K::k_fft_normalize, {K::k_fft_scale<1>, K::k_fft_scale<2>}, F::FR_R32}
-
-// A G2 unit (coordinates in Fq2, csrc/fq2.h): the same table (its point sampler draws multiples of the subgroup's generator)
-#define MSM_CURVE_OPS_FQ2(K, F)                                                                                                          \
-  {K::k_convert_points, K::k_convert_points_zero_id, K::k_precompute_tables, K::k_endo_points, {K::k_mul_each<false>, K::k_mul_each<true>}, K::k_mul_normalize, F::SMUL_CHUNK, K::k_mul_table_scalars, K::k_mul_fixed, F::SMUL_R_BITS, {K::k_count<12, 4, true>, K::k_count<14, 4, true>, K::k_count<16, 4, true>}, \
-   {K::k_count<12, 4, true, 0, SparseIdx>, K::k_count<14, 4, true, 0, SparseIdx>, K::k_count<16, 4, true, 0, SparseIdx>}, K::k_scalars_from_mont256, K::k_smvp_chunks, K::k_smvp_stitch, K::k_smvp_stitch_big,       \
-   K::k_bpr_rowcol<4, 8>, K::k_bpr_rowcol<2, 8>, K::k_bpr_rowcol<3, 8>, K::k_bpr_rowcol<4, 6>, K::k_bpr_rowcol<2, 6>, K::k_bpr_rowcol<2, 4>, \
-   K::k_bpr_w256, K::k_bpr_final, K::k_bpr_planes<false>, K::k_bpr_planes<true>, K::k_bpr_final_planes, K::BPR_USE_W256, K::CW, K::REC_WORDS, K::XYZZ_WORDS, F::GLV_SUPPORTED, K::k_sample_scalars, K::k_sample_points, K::k_export_buckets, K::k_test_fq, K::k_test_g1,                \
-   K::k_test_g1_mul_u32, F::host::combine_windows, F::host::window_from_planes, F::host::combine_wide, F::host::combine_wide_pairs, F::host::to_affine64, \
-   {nullptr, nullptr, nullptr}, nullptr, {nullptr, nullptr}, F::FR_R32}
-
 // accessors of the separately compiled units (hidden: not part of the C ABI)
 extern "C" {
+__attribute__((visibility("hidden"))) const CurveOps* msm_hip_curve_ops_bn254(void);
 __attribute__((visibility("hidden"))) const CurveOps* msm_hip_curve_ops_grumpkin(void);
 __attribute__((visibility("hidden"))) const CurveOps* msm_hip_curve_ops_pallas(void);
 __attribute__((visibility("hidden"))) const CurveOps* msm_hip_curve_ops_vesta(void);

@@ -315,7 +315,7 @@ inline bool window_from_planes(const uint8_t* planes, uint8_t* sum96) {
   return ok;
 }
 
-// The wide fixed-base tables' finish (msm_kernels.h: wide_key).  Magnitude m sits in virtual window vw = (m - 1) mod V at the slot of value
+// The wide fixed-base tables' finish (sort_kernels.h: wide_key).  Magnitude m sits in virtual window vw = (m - 1) mod V at the slot of value
 // (m - 1) / V + 1, so with the windows' weighted sums W_vw and plain totals TC_vw (V = nvirt, a power of two):
 //     sum_m m B_m = V * sum_vw W_vw - sum_vw (V - 1 - vw) TC_vw = V * sum_vw W_vw - sum_{j=0}^{V-2} (TC_0 + ... + TC_j)
 // -- log2 V doublings and 2 additions per virtual window.

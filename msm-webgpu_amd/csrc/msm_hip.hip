@@ -30,30 +30,24 @@
 #include "curve_ops.h"
 #include "host_fr.h"
 #include "host_pool.h"
+// the curve-neutral recode and sort, compiled here once for every curve; each curve's own kernels are a translation unit of their own (curve_ops.h)
+#include "sort_kernels.h"
 
-// the arithmetic and the kernels of BN254's unit (csrc/curve_select.h); the other curves' units are separate translation units (curve_ops.h)
-#define MSM_FIELD_NS bn254
-#define MSM_KERNEL_NS msmk
-#define MSM_CURVE_CONSTANTS "bn254_constants.h"
-#include "curve_unit.h"
-#undef MSM_FIELD_NS
-#undef MSM_KERNEL_NS
-#undef MSM_CURVE_CONSTANTS
-
-using namespace msmk;  // layout constants and the field-independent kernels (recode, sort) are taken from BN254's unit
+using namespace msm_layout;
+using namespace msm_sort;
 
 namespace {
-const CurveOps BN254_OPS = MSM_CURVE_OPS(msmk, bn254);
 // curve id (MSM_HIP_CURVE_*) -> its table
 inline const CurveOps* curve_ops(int curve) {
   switch (curve) {
+    case MSM_HIP_CURVE_BN254_G1: return msm_hip_curve_ops_bn254();
     case MSM_HIP_CURVE_GRUMPKIN: return msm_hip_curve_ops_grumpkin();
     case MSM_HIP_CURVE_PALLAS: return msm_hip_curve_ops_pallas();
     case MSM_HIP_CURVE_VESTA: return msm_hip_curve_ops_vesta();
     case MSM_HIP_CURVE_BLS12_381: return msm_hip_curve_ops_bls12_381();
     case MSM_HIP_CURVE_BN254_G2: return msm_hip_curve_ops_bn254_g2();
     case MSM_HIP_CURVE_BLS12_381_G2: return msm_hip_curve_ops_bls12_381_g2();
-    default: return &BN254_OPS;
+    default: return nullptr;  // (every entry point checks the curve id first)
   }
 }
 
@@ -63,10 +57,10 @@ enum LaunchMode {
   MODE_TABLES = 1,  // fixed-base tables: all windows of a vector feed one bucket set (MSM_HIP_BASES_PRECOMPUTE)
   MODE_HALVES = 2,  // endomorphism: 127-bit halves k1, k2 over the 2n points P_i, phi(P_i) (MSM_HIP_BASES_ENDOMORPHISM, csrc/glv.h)
   MODE_WIDE = 3,    // wide fixed-base tables: ceil(255 / C) digits of C = 16 .. 20 bits per scalar, one bucket set of 2^(C-1) slots run as 2^(C-16) virtual windows of 2^15
-                    // (MSM_HIP_BASES_PRECOMPUTE_WIDE; msm_kernels.h: k_count_wide)
+                    // (MSM_HIP_BASES_PRECOMPUTE_WIDE; sort_kernels.h: k_count_wide)
   MODE_NARROW = 4,  // narrow scalars (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128, and their MSM_HIP_SCALAR_SIGNED forms): the
                     // narrow_windows(C, bytes) windows of n x 1 .. 16 B integers over the plain records 0 .. n-1, which every base mode keeps
-                    // (msm_kernels.h: k_count<C, SW, false, NB>)
+                    // (recode.h: k_count<C, SW, void, NB>)
 };
 
 // bytes of a narrow scalar format (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128, each with or without MSM_HIP_SCALAR_SIGNED); 0 for the
@@ -82,7 +76,7 @@ inline int narrow_bytes(uint32_t format) {
   }
 }
 inline bool narrow_signed(uint32_t format) { return narrow_bytes(format) && (format & MSM_HIP_SCALAR_SIGNED); }  // two's-complement values
-// U8 / U16 (I8 / I16) run as byte windows (one per byte of the magnitude, digits 1 .. 255, a one-level counting sort: msm_kernels.h, k_byte_count
+// U8 / U16 (I8 / I16) run as byte windows (one per byte of the magnitude, digits 1 .. 255, a one-level counting sort: sort_kernels.h, k_byte_count
 // ...) on the 12-bit bucket grid -- the smallest the reduce kernels have, 2^11 slots of which 255 can fill; the wider formats as truncated signed
 // C-bit windows (C from n) through the two-level sort
 inline bool byte_windows(int nb) { return nb == 1 || nb == 2; }
@@ -136,7 +130,7 @@ struct LaunchRequest {
 struct LaunchPlan : LaunchRequest {   // (settled: wbits = the window bits of everything behind the recode, 16 for MODE_WIDE; v_count = the virtual windows run)
   int nb = 0;                         // MODE_NARROW: bytes per scalar ...
   bool nb_signed = false;             // ... and whether they are two's-complement (MSM_HIP_SCALAR_SIGNED)
-  int nb_kernel() const { return nb_signed ? -nb : nb; }  // the format as the scalar-loading kernels name it (msm_kernels.h: narrow_width)
+  int nb_kernel() const { return nb_signed ? -nb : nb; }  // the format as the scalar-loading kernels name it (msm_layout.h: narrow_width)
   int w_count_vec = 0;                // windows [w_begin, w_begin + w_count_vec) of every vector, in the request's window bits (MODE_WIDE: the T digits)
   int wide_bits = 0;                  // MODE_WIDE: the tables' digit width
   bool pairs = false;                 // MODE_WIDE, a share of the virtual windows: the launch leaves (window sum, plain total) record pairs
@@ -398,7 +392,7 @@ inline size_t piece_records_for(size_t n) {
 
 inline size_t stride_for(size_t n) { return (n + 3) & ~(size_t)3; }
 
-// The top digit of the wide tables' recode (msm_kernels.h: wide_digit), from the scalar field's modulus r (its top 64 bits, r >> 192):
+// The top digit of the wide tables' recode (sort_kernels.h: wide_digit), from the scalar field's modulus r (its top 64 bits, r >> 192):
 // its largest value over the scalars below r -- (r - 1 + the recode's bias below the digit) >> P, P = the digit's position -- decides the shift
 // (the largest that keeps the shifted digit within 2^(C-1)), and r / 2^P, the range of a uniform scalar's top digit, how many virtual windows
 // the shifted digit spreads over.  A top digit that does not fit after all is rejected by the kernel, never mis-added.
@@ -424,7 +418,7 @@ inline uint32_t wide_top_max(int curve, int bits) {
   for (int sh = 63; sh >= 0; sh -= bits) bias += 1ull << sh;
   return (uint32_t)(top >> fb) + (frac + bias < frac ? 1u : 0u);               // + the carry into the digit
 }
-// Round 5: with INTERLEAVED virtual windows (msm_kernels.h: wide_key) the narrow top digit spreads over the windows by itself and is used as it
+// Round 5: with INTERLEAVED virtual windows (sort_kernels.h: wide_key) the narrow top digit spreads over the windows by itself and is used as it
 // is -- no shift.  (Round 4 shifted it by the largest amount that kept it within 2^(C-1), to spread it over contiguous magnitude ranges;
 // MSM_HIP_WIDE_TOP_SHIFT still forces a shift for A/B runs: the kernels and the tables' last step honour it.)
 inline int env_wide_top_shift() {  // tuning aid
@@ -463,7 +457,7 @@ inline int pick_wide_bits(const msm_hip_ctx* ctx, size_t n) {
   const int bits = n <= ((size_t)1 << 16) ? 16 : n <= ((size_t)1 << 20) ? 17 : 20;
   return wide_bits_fit(ctx->curve, bits) ? bits : 19;
 }
-// SMVP lanes and lengths of a wide fixed-base launch over n points (msm_kernels.h: k_count_wide).  For uniform scalars every virtual window
+// SMVP lanes and lengths of a wide fixed-base launch over n points (sort_kernels.h: k_count_wide).  For uniform scalars every virtual window
 // receives (T - 1) n / VWIN entries from the T - 1 full digits, and the windows the shifted top digit reaches their share of its n more: the fullest
 // window's expected count F sets the device's chunk length (smvp_chunk_len), so the lanes are planned for F (+ 0.4 % + 64 entries: its
 // fluctuation is 0.07 % at 2^20) -- planned for the mean, the length the device settles on would be one entry more than the one the host
@@ -481,7 +475,7 @@ inline WideShape wide_shape(size_t n, int curve, int bits, int lwin) {  // (lwin
   const int WIDE_TABLES = wide_tables_of(bits), WIDE_VWIN = wide_vwin_of(bits);
   WideShape w;
   w.worst = n * (size_t)WIDE_TABLES;
-  // interleaved virtual windows (msm_kernels.h: wide_key): consecutive magnitudes go to consecutive windows, so every digit -- the narrow top one
+  // interleaved virtual windows (sort_kernels.h: wide_key): consecutive magnitudes go to consecutive windows, so every digit -- the narrow top one
   // included -- spreads evenly: each window expects T n / VWIN entries (a forced top shift of s puts the top digit's n entries into every 2^s-th
   // window only)
   const int shift = wide_top_shift(curve, bits);
@@ -719,7 +713,7 @@ int plan_launch(msm_hip_ctx* ctx, const LaunchRequest& r, LaunchPlan& p) {
   // fixed-base tables (`merge`): the w_count_vec windows of a vector feed one bucket set -- one local window of up to n * w_count_vec entries per
   // vector -- whose entries index the tables (window w of point i = record w * n_bases + i).  Wide tables: the same indexing; each vector's bucket
   // set of 2^(C-1) slots is run as 2^(C-16) local ("virtual") windows of 2^15, into which the entries fall by the top bits of their digit's
-  // magnitude (msm_kernels.h: k_count_wide).  Otherwise local window lw = v * w_count_vec + (w - w_begin).
+  // magnitude (sort_kernels.h: k_count_wide).  Otherwise local window lw = v * w_count_vec + (w - w_begin).
   const int w_count = merge ? nvec : wide ? nvec * v_count : nvec * w_count_vec;
   if (nvec < 1 || w_count > MAXLW) return MSM_HIP_ERR_INVALID_ARG;
 
@@ -806,7 +800,7 @@ void dispatch(decltype(V0) v, F&& f) {
 // for are recorded.
 int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_scalars) {
   const bool merge = p.mode == MODE_TABLES, halves = p.mode == MODE_HALVES, wide = p.mode == MODE_WIDE;
-  const bool bytes = byte_windows(p.nb);  // U8 / U16, I8 / I16: byte windows with their own one-level sort (msm_kernels.h: k_byte_count ...)
+  const bool bytes = byte_windows(p.nb);  // U8 / U16, I8 / I16: byte windows with their own one-level sort (sort_kernels.h: k_byte_count ...)
   const size_t merge_nb = merge || wide ? ctx->n_bases : 0;
   hipStream_t st = ctx->stream;
   const dim3 grid(p.tiles, p.nvec), block(256);
@@ -853,7 +847,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   uint16_t* digits = p.digits ? ctx->d_digits : nullptr;
   uint16_t* plane_out = p.planes ? ctx->d_digits : digits;
   const int plane_mode = p.planes ? 2 : (digits ? 1 : 0);
-  // sparse launches: the same passes instantiated with one more argument (msm_kernels.h: SparseIdx) -- the count passes guard the indices, the
+  // sparse launches: the same passes instantiated with one more argument (msm_layout.h: SparseIdx) -- the count passes guard the indices, the
   // scatter passes write them in place of the positions
   const SparseIdx sp{p.indices, (uint32_t)ctx->n_bases, d_err};
   // k_count leaves the prefix over tiles and the bin totals itself (bin_fill); the other first passes are followed by a scan kernel
@@ -896,10 +890,10 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
       if constexpr (NB != 0 || SW == 8) {  // (the halves were counted above, by the pass that splits them)
         const size_t vec_stride = p.n * (NB ? narrow_width(NB) : 8);
         if (p.sparse)
-          hipLaunchKernelGGL((k_count<C, SW, false, NB, SparseIdx>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec,
+          hipLaunchKernelGGL((k_count<C, SW, void, NB, SparseIdx>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec,
                              p.nvec, vec_stride, ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb, sp);
         else
-          hipLaunchKernelGGL((k_count<C, SW, false, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
+          hipLaunchKernelGGL((k_count<C, SW, void, NB>), grid, block, 0, st, d_scalars, p.n_sc, p.tile_len, p.tiles, p.w_begin, p.w_count_vec, p.nvec,
                              vec_stride, ctx->d_counts, ctx->d_bin_fill, plane_out, plane_mode, (uint64_t*)nullptr, (uint32_t*)nullptr, d_err, merge_nb);
       }
     });
@@ -960,7 +954,7 @@ int enqueue_sort(msm_hip_ctx* ctx, LaunchPlan& p, Slot& s, const uint32_t* d_sca
   // fine sort 2 - 2.5 x (profiles/r05_skew_hist.txt): k_sort_fine reports a huge bin in the slot's status word, and the 64 launches after such a
   // report run k_fine_hist (a prover's MSMs come in series of like inputs; the first of a series pays the fallback once).  The report means SKEW:
   // a bin of more than HUGE_BIN_MEANS mean bins -- the top window of endomorphism halves reaches two means, which at 2^20 is FINE_BIG, and used to
-  // keep the kernel in every launch of uniform scalars; such bins are shared without histograms at no measurable cost (msm_kernels.h: k_sort_fine)
+  // keep the kernel in every launch of uniform scalars; such bins are shared without histograms at no measurable cost (sort_kernels.h: k_sort_fine)
   // Narrow scalars always run it and leave the credit alone: their top window holds only the recode's carry (U8: all entries) -- one huge bin by
   // construction, which says nothing about the context's later 32-byte launches
   if (bytes) {  // byte windows: the scatter has grouped the entries by slot already; only the SMVP's chunk table is left
@@ -1735,7 +1729,7 @@ int msm_hip_run_windows_device(msm_hip_ctx* ctx, const void* scalars_dev, size_t
 
 int msm_hip_combine_windows_bn254(const uint8_t* window_sums_host, int num_windows, uint8_t out_xyz[96]) {
   if (!window_sums_host || !out_xyz || num_windows < 1 || num_windows > NWIN) return MSM_HIP_ERR_INVALID_ARG;
-  if (!bn254::host::combine_windows(window_sums_host, num_windows, WBITS, out_xyz)) return MSM_HIP_ERR_NONCANONICAL;
+  if (!curve_ops(MSM_HIP_CURVE_BN254_G1)->combine_windows(window_sums_host, num_windows, WBITS, out_xyz)) return MSM_HIP_ERR_NONCANONICAL;
   return MSM_HIP_OK;
 }
 
@@ -1766,7 +1760,7 @@ int msm_hip_combine_vwindows_batch_curve(int curve, const uint8_t* pairs_host, i
 
 int msm_hip_g1_to_affine_bn254(const uint8_t xyz[96], uint8_t out_xy[64]) {
   if (!xyz || !out_xy) return MSM_HIP_ERR_INVALID_ARG;
-  const int r = bn254::host::to_affine64(xyz, out_xy);
+  const int r = curve_ops(MSM_HIP_CURVE_BN254_G1)->to_affine64(xyz, out_xy);
   return r < 0 ? MSM_HIP_ERR_NONCANONICAL : r;
 }
 

@@ -156,7 +156,7 @@ FQ_HD g1_xyzz smul_endo(const fq& px, const fq& py, const uint32_t k[8]) {
 // ---- fixed base: k P from a table of multiples, no doublings
 // T_w[j] = j 2^(C w) P for j = 1 .. 2^(C-1) and w < W = (SMUL_R_BITS + 1 + C) / C windows, record (w << (C - 1)) + j - 1 of `table`: packed Montgomery
 // affine records like the resident bases, an all-zero record for a multiple that is the identity (a base of small order).  k < r is recoded into
-// W signed C-bit digits d_w in [-2^(C-1), 2^(C-1)) with the bias trick of the MSM's recode (msm_kernels.h, bias_scalar): digit w of k + bias,
+// W signed C-bit digits d_w in [-2^(C-1), 2^(C-1)) with the bias trick of the MSM's recode (recode.h, bias_scalar): digit w of k + bias,
 // bias = sum_w 2^(C w + C - 1), is d_w + 2^(C-1), and C W >= SMUL_R_BITS + 2 keeps k + bias below 2^(C W) for every C: no carry is lost.  k P = sum_w d_w 2^(C w) P: W gathered
 // mixed additions (10 products each).
 FQ_HD int smul_fixed_windows(int c) { return (SMUL_R_BITS + 1 + c) / c; }

@@ -1,7 +1,7 @@
 """Scalars that sit on the edges of C-bit signed window recoding (test infrastructure; no GPU, no oracle).
 
 The engine cuts a scalar of `bits` bits into nwin windows of C bits, lowest first, and makes each a signed digit: chunk + carry, minus 2^C with a
-carry into the next window when that reaches 2^(C-1) (msm_kernels.h, bias_scalar).  nwin is (254 + C) / C for 32-byte scalars and (8 w + C) / C for
+carry into the next window when that reaches 2^(C-1) (recode.h, bias_scalar).  nwin is (254 + C) / C for 32-byte scalars and (8 w + C) / C for
 narrow scalars of w bytes, so the top window holds a partial chunk (or nothing) plus the carry from below.  edge_values plants, for one value
 width and one C:
   - every chunk 2^(C-1): a digit of -2^(C-1) and a carry through every window, into the top one;

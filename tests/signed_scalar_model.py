@@ -4,7 +4,7 @@ A format is (width in bytes, signed).  A signed format holds two's-complement li
 the windows of the width and applies the sign to every digit (include/msm_hip.h, MSM_HIP_SCALAR_SIGNED):
   - widths 1 and 2 (byte windows): window j is byte j of |v|, an unsigned digit weighing 2^(8 j);
   - widths 4, 8 and 16: nwin = (8 w + C) / C signed C-bit digits of |v| -- chunk + carry, minus 2^C with a carry into the next window when
-    that reaches 2^(C-1) (msm_kernels.h, bias_scalar) -- weighing 2^(C k); the top window holds only what the carry leaves.
+    that reaches 2^(C-1) (recode.h, bias_scalar) -- weighing 2^(C k); the top window holds only what the carry leaves.
 tests/test_signed_scalar_abi.py checks that the digits reassemble every value; tests/test_gpu_signed_scalars.py compares the engine's digit
 planes with them."""
 

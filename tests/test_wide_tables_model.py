@@ -1,7 +1,7 @@
 """The wide fixed-base tables' arithmetic as a model over Z_r (CPU only; test infrastructure).
 
 The MSM is linear in the points, so the additive group Z_r stands in for the curve: "point" i is an integer g_i, "sum_i s_i P_i" is
-sum_i s_i g_i mod r.  The model follows csrc/msm_kernels.h (k_count_wide / wide_digit: signed C-bit digits by one biased addition, the top
+sum_i s_i g_i mod r.  The model follows csrc/sort_kernels.h (k_count_wide / wide_digit: signed C-bit digits by one biased addition, the top
 digit shifted against a top table that is `shift` doublings short -- 0 since round 5 --, magnitude m -> virtual window (m - 1) mod V and the slot of
 value (m - 1) / V + 1, slot 0 carrying 2^15) and csrc/host_g1.h (combine_wide: V sum_vw W_vw - sum_vw (V - 1 - vw) TC_vw), with the shape -- digit width, tables, virtual
 windows, top shift -- taken from the library's own host-only helper (msm_hip_wide_config), for every curve's scalar field and every width."""
@@ -33,7 +33,7 @@ def wide_msm_model(r, scalars, points, bits, tables, vwin, shift):
                 mag, neg = d << shift, False
             if mag == 0:
                 continue
-            hi, slot = (mag - 1) % vwin, ((mag - 1) // vwin + 1) & 0x7FFF               # msm_kernels.h: wide_key / wide_slot (interleaved)
+            hi, slot = (mag - 1) % vwin, ((mag - 1) // vwin + 1) & 0x7FFF               # sort_kernels.h: wide_key / wide_slot (interleaved)
             assert hi < vwin
             buckets[hi][slot] = (buckets[hi][slot] + (-table[w][i] if neg else table[w][i])) % r
     total, run, minus = 0, 0, 0

@@ -18,7 +18,7 @@ liveness analysis over the SGPRs (definitions and uses of every instruction, inl
 registers) reports every expanded branch whose pair is LIVE at the branch target, i.e. read there before it is written.  No build
 of this repository has shown one; the check is cheap insurance for the same family of expansions.
 
-usage: check_long_branch_hazard.py [file.s]        (no argument: compiles msm-webgpu_amd/csrc/msm_hip.hip to assembly first)
+usage: check_long_branch_hazard.py [file.s]        (no argument: every translation unit of msm-webgpu_amd/build.py, compiled to assembly first if the build left none)
 exit status 0 = clean, 1 = hazard found.
 """
 import os

@@ -10,7 +10,7 @@ d = sys.argv[1]
 ev = []
 for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
-        ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("msmk::", "").replace("void ", ""), "q" + r.get("Queue_Id", "?")))
+        ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("msmk::", "").replace("msm_sort::", "").replace("msm_recode::", "").replace("void ", ""), "q" + r.get("Queue_Id", "?")))
 for f in glob.glob(os.path.join(d, "**", "*memory_copy_trace.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "COPY " + r.get("Direction", "?").replace("MEMORY_COPY_", ""), "copy"))

@@ -6,7 +6,7 @@ launches = int(sys.argv[3]) if len(sys.argv) > 3 else 3
 ks = []
 for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
-        ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("msmk::", "").replace("void ", ""), "q" + r.get("Queue_Id", "?"), r["Grid_Size_X"] + "x" + r["Grid_Size_Y"]))
+        ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("msmk::", "").replace("msm_sort::", "").replace("msm_recode::", "").replace("void ", ""), "q" + r.get("Queue_Id", "?"), r["Grid_Size_X"] + "x" + r["Grid_Size_Y"]))
 ks.sort()
 sm = [i for i, k in enumerate(ks) if k[2] == "k_smvp_chunks" and k[4].endswith("x%d" % want)]
 # the count kernel in front of the first of the last `launches` grouped SMVPs

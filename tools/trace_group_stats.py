@@ -8,7 +8,7 @@ from collections import defaultdict
 rows = []
 with open(sys.argv[1]) as f:
     for r in csv.DictReader(f):
-        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("void ", "").replace("msmk::", ""), int(r["Grid_Size_Y"]), int(r["Grid_Size_X"])))
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("void ", "").replace("msmk::", "").replace("msm_sort::", "").replace("msm_recode::", ""), int(r["Grid_Size_Y"]), int(r["Grid_Size_X"])))
 rows.sort()
 want = int(sys.argv[2])
 # a kernel belongs to a launch of the wanted shape if its own grid y is the launch's local-window count (sort_fine, smvp, stitch, rowcol) or,
