@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "msm_fr.h"
 #include "msm_hip.h"
 
 namespace msm_webgpu {
@@ -209,6 +210,19 @@ class MsmContext {
   }
   void bases_fft_device(const uint8_t omega[32], int log_n, void* out_xy_dev, uint32_t flags = 0) {
     check(msm_hip_bases_fft_device(ctx_, omega, log_n, out_xy_dev, flags), "msm_hip_bases_fft_device");
+  }
+  /// Scalar-field NTT of `batch` vectors of 2^log_n scalars (libmsm_fr.so, msm_fr.h: msm_fr_ntt_device), in place in device memory on this
+  /// context's stream and in its curve's scalar field: out[i] = c t^i sum_j s^j omega^(i j) a[j].  `device`: the device this context was created
+  /// on.  pre_shift (s) / post_shift (t): 32 bytes or nullptr; flags: MSM_FR_SCALE_INV_N, MSM_FR_MONT256.  The result can go into run_device.
+  /// (A program that calls these links libmsm_fr.so beside libmsm_hip.so.)
+  void scalars_fft(int device, void* scalars_dev, int log_n, const uint8_t omega[32], size_t batch = 1, const uint8_t* pre_shift = nullptr,
+                   const uint8_t* post_shift = nullptr, uint32_t flags = 0) {
+    check(msm_fr_ntt_device(msm_hip_ctx_curve(ctx_), device, msm_hip_stream(ctx_), scalars_dev, log_n, batch, omega, pre_shift, post_shift, flags), "msm_fr_ntt_device");
+  }
+  /// ... and of host memory, staged through the device (msm_fr_ntt)
+  void scalars_fft_host(int device, uint8_t* scalars, int log_n, const uint8_t omega[32], size_t batch = 1, const uint8_t* pre_shift = nullptr,
+                        const uint8_t* post_shift = nullptr, uint32_t flags = 0) {
+    check(msm_fr_ntt(msm_hip_ctx_curve(ctx_), device, scalars, log_n, batch, omega, pre_shift, post_shift, flags), "msm_fr_ntt");
   }
   G1 finish(int slot) {
     G1 r;

@@ -9,6 +9,7 @@ Error behaviour: the reference panics (gpu.rs:22,51; lib.rs:58; msm.rs:399; util
 MsmHipError carrying the C-ABI error code.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -28,14 +29,22 @@ CURVES = {"bn254": (0, P), "grumpkin": (1, R_BN254), "pallas": (2, PALLAS_P), "v
 
 # group order r (the scalar field) of the G1 curves: what msm_hip_bases_fft's omega lives in
 BLS12_381_R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-SCALAR_FIELDS = {"bn254": R_BN254, "grumpkin": P, "pallas": VESTA_P, "vesta": PALLAS_P, "bls12_381": BLS12_381_R}
+SCALAR_FIELDS = {"bn254": R_BN254, "grumpkin": P, "pallas": VESTA_P, "vesta": PALLAS_P, "bls12_381": BLS12_381_R,
+                 "bn254_g2": R_BN254, "bls12_381_g2": BLS12_381_R}  # (a G2 group has its G1's order)
+# largest log_n of a scalar-field transform (include/msm_fr.h): min(2-adicity of r - 1, 26)
+FR_MAX_LOG_N = 26
 
 
 def root_of_unity(curve, log_n, inverse=False):
     """A primitive 2^log_n-th root of unity of a G1 curve's scalar field (its inverse with inverse=True), as an integer: the smallest quadratic
     non-residue raised to (r - 1) / 2^log_n.  Raises ValueError where 2^log_n does not divide r - 1 (Grumpkin: log_n > 1)."""
+    return _root_of_unity(curve, int(log_n), bool(inverse))
+
+
+@functools.lru_cache(maxsize=None)
+def _root_of_unity(curve, log_n, inverse):
+    # (two 254-bit modular exponentiations, a quarter of a millisecond: remembered, since scalars_fft asks on every call)
     r = SCALAR_FIELDS[curve]
-    log_n = int(log_n)
     if log_n < 0 or (r - 1) % (1 << log_n):
         raise ValueError("the scalar field of %s has no root of unity of order 2^%d" % (curve, log_n))
     g = 2
@@ -168,6 +177,46 @@ def lib():
         L.msm_hip_window_range.argtypes = [i, i, i, C.POINTER(i), C.POINTER(i)]
         _lib = L
     return _lib
+
+
+_fr_lib = None
+
+
+def fr_lib():
+    """Load libmsm_fr.so (in-tree; include/msm_fr.h): the scalar-field NTT.  Raises if it has not been built -- there is no fallback path."""
+    global _fr_lib
+    if _fr_lib is None:
+        so = _build.FR_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_fr.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, u8p, sz, i = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int
+        L.msm_fr_abi_version.restype = i
+        L.msm_fr_ntt_device.argtypes = [i, i, vp, vp, i, sz, u8p, u8p, u8p, C.c_uint32]
+        L.msm_fr_ntt.argtypes = [i, i, vp, i, sz, u8p, u8p, u8p, C.c_uint32]
+        L.msm_fr_release.argtypes = []
+        L.msm_fr_release.restype = None
+        L.msm_fr_test_pass_bits.argtypes = [i]
+        L.msm_fr_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
+        _fr_lib = L
+    return _fr_lib
+
+
+def fr_test_pass_bits(bits=0):
+    """test hook msm_fr_test_pass_bits: cap the radix-2 levels of a pass of the scalar-field NTT at `bits` (0: the design's 10)"""
+    _check(fr_lib().msm_fr_test_pass_bits(int(bits)), "msm_fr_test_pass_bits")
+
+
+def fr_last():
+    """(passes, widest pass's levels) of the last scalar-field NTT of this process (test hook msm_fr_test_last)"""
+    v = [C.c_int(), C.c_int()]
+    _check(fr_lib().msm_fr_test_last(*[C.byref(x) for x in v]), "msm_fr_test_last")
+    return tuple(x.value for x in v)
+
+
+def fr_release():
+    """msm_fr_release: free the scalar-field NTT's cached twiddles and scratch (they come back with the next call)"""
+    fr_lib().msm_fr_release()
 
 
 def _check(code, where):
@@ -368,6 +417,7 @@ class MsmContext:
         self.wide_bits_choice = 0
         self.scalar_width = 32  # bytes per scalar of the following runs (set_scalar_format) ...
         self.scalar_signed = False  # ... and whether they are two's-complement integers
+        self.scalar_mont256 = False  # ... or, at 32 bytes, s * 2^256 mod r
         self._keepalive = {}  # slot -> tensors the slot's launch still reads / writes; released when the slot is collected
 
     def _order_after_torch(self, *tensors):
@@ -548,6 +598,74 @@ class MsmContext:
         v = [C.c_int(), C.c_int()]
         _check(lib().msm_hip_test_fft_last(self._h, *[C.byref(x) for x in v]), "msm_hip_test_fft_last")
         return tuple(x.value for x in v)
+
+    # -- scalar-field NTT (libmsm_fr.so): coefficients <-> evaluations of the vectors this context commits to
+    FR_SCALE_INV_N, FR_MONT256 = 1, 2  # MSM_FR_SCALE_INV_N, MSM_FR_MONT256
+
+    def scalars_fft(self, scalars, log_n=None, omega=None, inverse=False, shift=None, batch=1):
+        """The transform of `batch` vectors of n = 2^log_n scalars (msm_fr_ntt_device, include/msm_fr.h), in natural order:
+        out[i] = sum_j omega^(i j) (shift^j a[j]) -- the evaluations of the polynomial with coefficients a on the n-th roots of unity (on the coset
+        shift * H with `shift`); inverse=True undoes it: omega^-1, 1 / n, and shift^-i afterwards.  scalars: a CUDA uint8 tensor of batch * n * 32
+        bytes, transformed IN PLACE on this context's stream and returned -- it can go straight into msm() --, or host bytes (bytes come back).
+        log_n: None takes it from the size.  omega: None takes root_of_unity(curve, log_n); an integer or 32 bytes otherwise, a primitive n-th root.
+        The scalars are in this context's 32-byte scalar format (set_scalar_format: canonical, or mont256) and must be below r."""
+        if self.curve not in SCALAR_FIELDS or self.curve == "grumpkin":
+            raise ValueError("the scalar field of %s has no transform (2-adicity 1)" % self.curve)
+        if getattr(self, "scalar_width", 32) != 32:
+            raise ValueError("scalars_fft takes 32-byte scalars; the context's scalar format is %d bytes wide" % self.scalar_width)
+        r = SCALAR_FIELDS[self.curve]
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError("batch must be at least 1")
+        on_device = isinstance(scalars, torch.Tensor) and scalars.is_cuda
+        if on_device:
+            t, total = _as_device_u8(scalars, 32, "scalars")
+        else:
+            buf = bytes(scalars)
+            if len(buf) % 32:
+                raise ValueError("scalars must be n x 32 bytes")
+            total = len(buf) // 32
+        if log_n is None:
+            n = total // batch
+            if total % batch or n == 0 or n & (n - 1):
+                raise ValueError("%d scalars are not %d vectors of a power-of-two length" % (total, batch))
+            log_n = n.bit_length() - 1
+        log_n = int(log_n)
+        two_adicity = ((r - 1) & -(r - 1)).bit_length() - 1
+        if not 0 <= log_n <= min(two_adicity, FR_MAX_LOG_N):
+            raise ValueError("log_n must lie in [0, %d] on %s, not %d" % (min(two_adicity, FR_MAX_LOG_N), self.curve, log_n))
+        if total != batch << log_n:
+            raise ValueError("%d scalars are not %d vectors of 2^%d" % (total, batch, log_n))
+        if omega is None:
+            w = root_of_unity(self.curve, log_n)
+        else:
+            w = int.from_bytes(omega, "little") if isinstance(omega, (bytes, bytearray)) else int(omega)
+            if isinstance(omega, (bytes, bytearray)) and len(omega) != 32:
+                raise ValueError("omega must be an integer or 32 bytes")
+            if not 0 < w < r or (w != 1 if log_n == 0 else pow(w, 1 << (log_n - 1), r) != r - 1):
+                raise ValueError("omega is not a primitive 2^%d-th root of unity of the scalar field" % log_n)
+        g = None
+        if shift is not None:
+            g = (int.from_bytes(shift, "little") if isinstance(shift, (bytes, bytearray)) else int(shift)) % r
+            if g == 0:
+                raise ValueError("shift must be invertible")
+        flags = self.FR_MONT256 if getattr(self, "scalar_mont256", False) else 0
+        pre = post = None
+        if inverse:
+            w = root_of_unity(self.curve, log_n, inverse=True) if omega is None else pow(w, r - 2, r)
+            flags |= self.FR_SCALE_INV_N
+            post = pow(g, r - 2, r).to_bytes(32, "little") if g is not None else None
+        else:
+            pre = g.to_bytes(32, "little") if g is not None else None
+        wb = w.to_bytes(32, "little")
+        if on_device:
+            self._order_after_torch(t)
+            stream = lib().msm_hip_stream(self._h)
+            _check(fr_lib().msm_fr_ntt_device(self.curve_id, self.device, stream, t.data_ptr(), log_n, batch, wb, pre, post, flags), "msm_fr_ntt_device")
+            return scalars
+        out = C.create_string_buffer(buf, max(len(buf), 1))
+        _check(fr_lib().msm_fr_ntt(self.curve_id, self.device, C.cast(out, C.c_void_p), log_n, batch, wb, pre, post, flags), "msm_fr_ntt")
+        return out.raw[:len(buf)]
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under
@@ -837,6 +955,7 @@ class MsmContext:
         fmt = SCALAR_FORMATS[(width, bool(signed))] if width != 32 else (1 if mont256 else 0)
         _check(lib().msm_hip_set_scalar_format(self._h, fmt), "msm_hip_set_scalar_format")
         self.scalar_width, self.scalar_signed = width, bool(signed)
+        self.scalar_mont256 = bool(mont256)
 
     def skew_credit(self):
         """launches left that run k_fine_hist because an earlier 32-byte launch met a huge coarse bin (test hook)"""

@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so and libmsm_fr.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -8,6 +8,13 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.environ.get("MSM_HIP_SO") or os.path.join(HERE, "libmsm_hip.so")
 SOURCES = ["msm_hip.hip", "curve_bn254.hip", "curve_grumpkin.hip", "curve_pallas.hip", "curve_vesta.hip", "curve_bls12_381.hip", "curve_bn254_g2.hip", "curve_bls12_381_g2.hip", "fq2.h", "bn254_g2_constants.h", "bls12_381_g2_constants.h", "fq28x14_asm.h", "bls12_381_constants.h", "curve_ops.h", "msm_layout.h", "recode.h", "sort_kernels.h", "msm_kernels.h", "g1.h", "fq29.h", "fq29_asm.h", "host_g1.h", "host_fr.h", "host_pool.h", "host_worker.h", "glv.h", "scalar_mul.h", "msm_mgpu.h", "curve_select.h", "curve_unit.h", "grumpkin_constants.h", "bn254_constants.h", "pallas_constants.h", "vesta_constants.h"]
 HEADER = os.path.join(HERE, "..", "include", "msm_hip.h")
+# libmsm_fr.so (include/msm_fr.h): the scalar-field NTT, a library of its own -- one translation unit per field, its own sources and stamp.  None
+# of it is part of libmsm_hip.so (TRANSLATION_UNITS, SOURCES and device_asm_files() below are that library's alone).
+FR_SO = os.path.join(HERE, "libmsm_fr.so")
+FR_UNITS = ["fr_bn254.hip", "fr_pallas.hip", "fr_vesta.hip", "fr_bls12_381.hip"]
+FR_SOURCES = FR_UNITS + ["fr_unit.h", "ntt_kernels.h", "ntt_host.h", "ntt_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h", "fr_pallas_constants.h",
+                         "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FR_HEADERS = [os.path.join(HERE, "..", "include", "msm_fr.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -22,6 +29,44 @@ def device_asm_is_current():
         return False
     newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in SOURCES if os.path.exists(os.path.join(CSRC, f)))
     return all(os.path.getmtime(f) >= newest for f in device_asm_files())
+
+
+def fr_device_asm_files():
+    """The device assembly of libmsm_fr.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FR_UNITS]
+
+
+def fr_build_stamp():
+    """build_stamp() for libmsm_fr.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FR_SOURCES)] + FR_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def fr_needs_build():
+    """libmsm_fr.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FR_SO + ".stamp") as f:
+            return not os.path.exists(FR_SO) or f.read().strip() != fr_build_stamp()
+    except OSError:
+        return True
+
+
+def fr_device_asm_is_current():
+    """device_asm_is_current() for libmsm_fr.so's units"""
+    if fr_needs_build() or not all(os.path.exists(f) for f in fr_device_asm_files()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FR_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in fr_device_asm_files())
 
 
 def build_stamp():
@@ -97,8 +142,10 @@ def compile_flags():
 
 
 def build(force=False, verbose=False):
-    """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so"""
-    if not force and not needs_build():
+    """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
+    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
+    if not do_hip and not do_fr:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -119,15 +166,25 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(TRANSLATION_UNITS), os.cpu_count() or 1)) as pool:
-        objs = list(pool.map(compile_unit, TRANSLATION_UNITS))
-    cmd = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "--hip-link"] + objs + ["-o", SO + ".tmp"]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd, cwd=TEMPS)
-    os.replace(SO + ".tmp", SO)
-    with open(stamp_path(), "w") as f:
-        f.write(build_stamp() + "\n")
+    def link(objs, so):
+        cmd = [hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "--hip-link"] + objs + ["-o", so + ".tmp"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd, cwd=TEMPS)
+        os.replace(so + ".tmp", so)
+
+    # one pool for the units of both libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else [])
+    with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
+        objs = dict(zip(units, pool.map(compile_unit, units)))
+    if do_hip:
+        link([objs[u] for u in TRANSLATION_UNITS], SO)
+        with open(stamp_path(), "w") as f:
+            f.write(build_stamp() + "\n")
+    if do_fr:
+        link([objs[u] for u in FR_UNITS], FR_SO)
+        with open(FR_SO + ".stamp", "w") as f:
+            f.write(fr_build_stamp() + "\n")
     return SO
 
 

@@ -18,7 +18,8 @@ liveness analysis over the SGPRs (definitions and uses of every instruction, inl
 registers) reports every expanded branch whose pair is LIVE at the branch target, i.e. read there before it is written.  No build
 of this repository has shown one; the check is cheap insurance for the same family of expansions.
 
-usage: check_long_branch_hazard.py [file.s]        (no argument: every translation unit of msm-webgpu_amd/build.py, compiled to assembly first if the build left none)
+usage: check_long_branch_hazard.py [file.s | unit.hip ...]   (no argument: every translation unit of libmsm_hip.so in msm-webgpu_amd/build.py, compiled to
+       assembly first if the build left none; unit names -- e.g. the scalar-field units fr_bn254.hip ... of libmsm_fr.so -- check those instead)
 exit status 0 = clean, 1 = hazard found.
 """
 import os
@@ -220,17 +221,20 @@ def analyse_liveness(name, lines):
     return [(name, instrs[gi][2], lab, sorted(pair & live_in[ti])) for gi, pair, ti, lab in jumps if pair & live_in[ti]]
 
 
-def compile_to_asm(extra):
+def compile_to_asm(extra, units=None):
     """Device assembly of the product, one file per translation unit: the files the library's own build left behind when they are
-    current (msm-webgpu_amd/build.py keeps the compiler's intermediate files), else fresh -S compiles (minutes)."""
+    current (msm-webgpu_amd/build.py keeps the compiler's intermediate files), else fresh -S compiles (minutes).  units: None -- the
+    units of libmsm_hip.so; a list of unit names otherwise (libmsm_fr.so's: build.FR_UNITS)."""
     sys.path.insert(0, os.path.join(ROOT, "msm-webgpu_amd"))
     import build as _b
 
-    if not extra and _b.device_asm_is_current():
+    if not extra and units is None and _b.device_asm_is_current():
         return _b.device_asm_files()
+    if not extra and units is not None and set(units) <= set(_b.FR_UNITS) and _b.fr_device_asm_is_current():
+        return [f for u, f in zip(_b.FR_UNITS, _b.fr_device_asm_files()) if u in units]
     outdir = tempfile.mkdtemp(prefix="msm_hip_asm_")
     outs = []
-    for unit in _b.TRANSLATION_UNITS:
+    for unit in (_b.TRANSLATION_UNITS if units is None else units):
         out = os.path.join(outdir, os.path.splitext(unit)[0] + ".s")
         cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
                os.path.join(ROOT, "msm-webgpu_amd", "csrc", unit), "-o", out] + extra
@@ -252,7 +256,8 @@ def check_file(path):
 
 def main():
     args = sys.argv[1:]
-    paths = [a for a in args if a.endswith(".s")] or compile_to_asm(args)
+    units = [a for a in args if a.endswith(".hip")]
+    paths = [a for a in args if a.endswith(".s")] or compile_to_asm([a for a in args if not a.endswith(".hip")], units or None)
     bad = 0
     for path in paths:
         long_branches, found, live = check_file(path)

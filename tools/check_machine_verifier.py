@@ -13,7 +13,7 @@ The check: every translation unit is compiled once more, device side only, with 
 -verify-machineinstrs`; a clean unit compiles, a miscompiled one aborts naming function and instruction.  Results are cached under
 build/ (key: the sources' and flags' hash) -- the verifier makes a unit's compile 2 - 3 x slower.
 
-usage: check_machine_verifier.py            every unit with the flags of the current environment (MSM_HIP_SLP=1: the miscompiled variant; MSM_HIP_ASM_SMVP_ONLY, MSM_HIP_EXTRA_FLAGS ...)
+usage: check_machine_verifier.py [unit.hip ...]   the named units (e.g. libmsm_fr.so's fr_bn254.hip ...), or every unit of libmsm_hip.so, with the flags of the current environment (MSM_HIP_SLP=1: the miscompiled variant; MSM_HIP_ASM_SMVP_ONLY, MSM_HIP_EXTRA_FLAGS ...)
 exit status 0 = clean, 1 = the verifier fired.
 """
 import hashlib
@@ -32,9 +32,10 @@ import build as _b  # noqa: E402
 CACHE = os.path.join(ROOT, "build", "machine_verifier_cache.json")
 
 
-def sources_hash(flags):
+def sources_hash(flags, units=()):
+    """hash of the flags and of the sources the units are built from (libmsm_fr.so's units have a source list of their own)"""
     h = hashlib.sha256(" ".join(flags).encode())
-    for name in sorted(_b.SOURCES):
+    for name in sorted(_b.FR_SOURCES if units and set(units) <= set(_b.FR_UNITS) else _b.SOURCES):
         path = os.path.join(_b.CSRC, name)
         if os.path.exists(path):
             h.update(name.encode())
@@ -66,7 +67,7 @@ def check(units=None, use_cache=True):
     """-> {unit: [(function, message), ...]} for every translation unit of the build, with the current environment's flags"""
     units = units or _b.TRANSLATION_UNITS
     flags = _b.compile_flags()
-    key = sources_hash(flags)
+    key = sources_hash(flags, units)
     cache = {}
     if use_cache and os.path.exists(CACHE):
         try:
@@ -85,7 +86,7 @@ def check(units=None, use_cache=True):
 
 def main():
     bad = 0
-    for unit, found in check(use_cache="--no-cache" not in sys.argv).items():
+    for unit, found in check(units=[a for a in sys.argv[1:] if a.endswith(".hip")] or None, use_cache="--no-cache" not in sys.argv).items():
         print("%s: %s" % (unit, "clean" if not found else "%d machine-verifier reports" % len(found)))
         for fn, msg in found:
             print("  MISCOMPILE in %s: %s" % (fn, msg))

@@ -7,6 +7,8 @@ Run: python tools/gen_constants.py > msm-webgpu_amd/csrc/bn254_constants.h
      python tools/gen_constants.py grumpkin > msm-webgpu_amd/csrc/grumpkin_constants.h
      python tools/gen_constants.py pallas   > msm-webgpu_amd/csrc/pallas_constants.h      (likewise vesta, bls12_381)
      python tools/gen_constants.py bn254_g2 > msm-webgpu_amd/csrc/bn254_g2_constants.h   (a G2 unit's Fq2-level constants; likewise bls12_381_g2)
+     python tools/gen_constants.py fr bn254 > msm-webgpu_amd/csrc/fr_bn254_constants.h   (field-only: a curve's SCALAR field for the NTT units of
+                                                                                          libmsm_fr.so; likewise pallas, vesta, bls12_381)
 (Grumpkin, BN254's cycle partner: base field = BN254's scalar field, scalar field = BN254's base field, y^2 = x^3 - 17; the two
 moduli agree in their top 128 bits, so 2^261 / modulus = 169 and every lazy bound of fq29.h / g1.h holds for both.
 Pallas / Vesta, the Pasta cycle: 255-bit moduli, 2^261 / modulus = 127 -- the largest operand product of the group formulas,
@@ -213,6 +215,62 @@ def emit_g2(which):
     print("}  // namespace MSM_FIELD_NS")
 
 
+def emit_field(name):
+    """msm-webgpu_amd/csrc/fr_<name>_constants.h: a SCALAR field alone, as csrc/fq29.h reads a modulus (9 x 29-bit limbs, R = 2^261) -- what the
+    scalar-field NTT (csrc/ntt_kernels.h, libmsm_fr.so) is instantiated with.  No curve constants.  Grumpkin's r (2-adicity 1) is not offered."""
+    r = {"bn254": RMOD, "pallas": 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
+         "vesta": 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
+         "bls12_381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001}[name]
+    w, l, nw = 29, 9, 8
+    m = (1 << w) - 1
+    rr = 1 << (w * l)
+    lim = lambda x: [(x >> (w * i)) & m for i in range(l)]
+    words = lambda x, bits, n: [(x >> (bits * i)) & ((1 << bits) - 1) for i in range(n)]
+    a = lambda nm, vals, ty="uint32_t", fmt="0x%08xu": "static constexpr %s %s[%d] = {%s};" % (ty, nm, len(vals), ", ".join(fmt % v for v in vals))
+    assert r.bit_length() <= 255 and sum(v << (w * i) for i, v in enumerate(lim(r))) == r
+    headroom = rr // r
+    assert l * ((1 << (w + 1)) + 64) ** 2 + l * (1 << w) ** 2 < 1 << 64, "column overflow"
+    two_adicity = ((r - 1) & -(r - 1)).bit_length() - 1
+    # the NTT's lazy bound (csrc/ntt_kernels.h): a tile enters a pass below 2r and gains at most 3r per radix-2 level; its values meet
+    # twiddles below r in the multiplier, whose operand product may reach headroom * r^2
+    assert 2 + 3 * 10 <= headroom, "ten butterfly levels per pass do not fit the multiplier's value bound"
+
+    def borrow(k):  # k*r with limbs 0..7 >= 2^31 - 4: a + KP[k] - b never borrows (see borrow_proof below)
+        q = lim(k * r)
+        up = (1 << 31) >> w
+        c = [q[0] + (1 << 31)] + [q[i] + (1 << 31) - up for i in range(1, l - 1)] + [q[l - 1] - up]
+        assert sum(v << (w * i) for i, v in enumerate(c)) == k * r and all(0 <= v < (1 << 32) for v in c) and c[l - 1] > 0
+        return c
+
+    print("// GENERATED by tools/gen_constants.py fr %s -- do not edit." % name)
+    print("// The scalar field of %s as a field of its own: r = %d" % (name, r))
+    print("// (what csrc/fq29.h reads, and nothing of a curve: the scalar-field NTT's units, csrc/fr_%s.hip)" % name)
+    print("#pragma once\n#include <cstdint>\nnamespace MSM_FIELD_NS {")
+    print("constexpr int FQ_HEADROOM = %d;  // floor(2^%d / r): a Montgomery product of operands with value(a) value(b) <= FQ_HEADROOM r^2 is < 2r" % (headroom, w * l))
+    print("constexpr int FQ_EXT = 1;")
+    print("constexpr int FQ_LIMBS = %d;\nconstexpr int FQ_LIMB_BITS = %d;\nconstexpr int FQ_WORDS = %d;  // packed 32-bit words per element (wire / storage form)\nconstexpr uint32_t FQ_MASK = 0x%xu;" % (l, w, nw, m))
+    print("constexpr int FR_TWO_ADICITY = %d;  // 2^%d divides r - 1" % (two_adicity, two_adicity))
+    print(a("FQ_P29", lim(r)))
+    print("constexpr uint32_t FQ_N0_29 = 0x%xu;  // -r^-1 mod 2^%d" % ((-pow(r, -1, 1 << w)) % (1 << w), w))
+    print(a("FQ_ONE29", lim(rr % r)) + "  // R mod r, R = 2^%d" % (w * l))
+    print(a("FQ_R2_29", lim(rr * rr % r)) + "  // R^2 mod r")
+    print(a("FQ_2P266_29", lim(pow(2, 2 * w * l - 256, r))) + "  // 2^%d mod r" % (2 * w * l - 256))
+    print("// k*r in borrow-proof form (limbs 0..7 >= 2^31 - 4): a + KP[k] - b is limb-wise non-negative for b < (k-1)*r")
+    print("static constexpr uint32_t FQ_KP29[17][%d] = {" % l)
+    for k in range(17):
+        print("  {%s}," % ", ".join("0x%08xu" % v for v in (borrow(k) if k >= 2 else [0] * l)))
+    print("};")
+    q2 = lim(2 * r)
+    lazy2p = [q2[0] + (1 << w)] + [q2[i] + (1 << w) - 1 for i in range(1, l - 1)] + [q2[l - 1] - 1]
+    assert sum(v << (w * i) for i, v in enumerate(lazy2p)) == 2 * r and all((1 << w) - 1 <= v < (1 << (w + 1)) for v in lazy2p[:l - 1])
+    print(a("FQ_2P_LAZY29", lazy2p) + "  // 2r, borrow-free against exact limbs: fq_neg_lazy")
+    print(a("FQ_P32", words(r, 32, nw)) + "  // r as %d x 32-bit words (packed / canonical form)" % nw)
+    print("}  // namespace MSM_FIELD_NS")
+
+
+if len(sys.argv) > 2 and sys.argv[1] == "fr":
+    emit_field(sys.argv[2])
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] in ("bn254_g2", "bls12_381_g2"):
     emit_g2(sys.argv[1][:-3])
     sys.exit(0)
