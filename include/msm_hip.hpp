@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "msm_fr.h"
+#include "msm_frvec.h"
 #include "msm_hip.h"
 
 namespace msm_webgpu {
@@ -223,6 +224,40 @@ class MsmContext {
   void scalars_fft_host(int device, uint8_t* scalars, int log_n, const uint8_t omega[32], size_t batch = 1, const uint8_t* pre_shift = nullptr,
                         const uint8_t* post_shift = nullptr, uint32_t flags = 0) {
     check(msm_fr_ntt(msm_hip_ctx_curve(ctx_), device, scalars, log_n, batch, omega, pre_shift, post_shift, flags), "msm_fr_ntt");
+  }
+  /// Vector arithmetic over this context's scalar field (libmsm_frvec.so, msm_frvec.h), on device memory, on this context's stream: what lies
+  /// between a transform and the next commitment.  `device`: the device this context was created on.  out may be a (in place) or any operand.
+  /// b / c: a device vector, or nullptr with the 32-byte canonical constant b_const / c_const that is broadcast.  flags: MSM_FRVEC_MONT256.
+  /// (A program that calls these links libmsm_frvec.so beside libmsm_hip.so.)
+  void scalars_map(int device, int op, void* out, const void* a, const void* b, const void* c, size_t n, const uint8_t* b_const = nullptr, const uint8_t* c_const = nullptr,
+                   uint32_t flags = 0) {
+    check(msm_frvec_map_device(msm_hip_ctx_curve(ctx_), device, msm_hip_stream(ctx_), out, a, b, c, n, op, b_const, c_const, flags), "msm_frvec_map_device");
+  }
+  void scalars_add(int device, void* out, const void* a, const void* b, size_t n, const uint8_t* b_const = nullptr, uint32_t flags = 0) {
+    scalars_map(device, MSM_FRVEC_ADD, out, a, b, nullptr, n, b_const, nullptr, flags);
+  }
+  void scalars_sub(int device, void* out, const void* a, const void* b, size_t n, const uint8_t* b_const = nullptr, uint32_t flags = 0) {
+    scalars_map(device, MSM_FRVEC_SUB, out, a, b, nullptr, n, b_const, nullptr, flags);
+  }
+  void scalars_mul(int device, void* out, const void* a, const void* b, size_t n, const uint8_t* b_const = nullptr, uint32_t flags = 0) {
+    scalars_map(device, MSM_FRVEC_MUL, out, a, b, nullptr, n, b_const, nullptr, flags);
+  }
+  void scalars_mul_add(int device, void* out, const void* a, const void* b, const void* c, size_t n, const uint8_t* b_const = nullptr, const uint8_t* c_const = nullptr,
+                       uint32_t flags = 0) {
+    scalars_map(device, MSM_FRVEC_MUL_ADD, out, a, b, c, n, b_const, c_const, flags);
+  }
+  void scalars_mul_sub(int device, void* out, const void* a, const void* b, const void* c, size_t n, const uint8_t* b_const = nullptr, const uint8_t* c_const = nullptr,
+                       uint32_t flags = 0) {
+    scalars_map(device, MSM_FRVEC_MUL_SUB, out, a, b, c, n, b_const, c_const, flags);
+  }
+  /// out[i] = 1 / a[i], 1 / 0 = 0 (msm_frvec_inverse_device)
+  void scalars_inverse(int device, void* out, const void* a, size_t n, uint32_t flags = 0) {
+    check(msm_frvec_inverse_device(msm_hip_ctx_curve(ctx_), device, msm_hip_stream(ctx_), out, a, n, flags), "msm_frvec_inverse_device");
+  }
+  /// running sums / products (op: MSM_FRVEC_SUM, MSM_FRVEC_PRODUCT) along `batch` rows of n; flags: MSM_FRVEC_EXCLUSIVE, MSM_FRVEC_MONT256;
+  /// totals_host: nullptr, or batch * 32 bytes of host memory for the rows' totals (msm_frvec_scan_device)
+  void scalars_scan(int device, void* out, const void* a, size_t n, int op, size_t batch = 1, uint32_t flags = 0, uint8_t* totals_host = nullptr) {
+    check(msm_frvec_scan_device(msm_hip_ctx_curve(ctx_), device, msm_hip_stream(ctx_), out, a, n, batch, op, flags, totals_host), "msm_frvec_scan_device");
   }
   G1 finish(int slot) {
     G1 r;

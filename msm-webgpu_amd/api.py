@@ -219,6 +219,51 @@ def fr_release():
     fr_lib().msm_fr_release()
 
 
+_frvec_lib = None
+
+
+def frvec_lib():
+    """Load libmsm_frvec.so (in-tree; include/msm_frvec.h): vector arithmetic over the scalar field.  Raises if it has not been built -- there is no
+    fallback path."""
+    global _frvec_lib
+    if _frvec_lib is None:
+        so = _build.FRVEC_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frvec.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
+        L.msm_frvec_abi_version.restype = i
+        L.msm_frvec_map_device.argtypes = [i, i, vp, vp, vp, vp, vp, sz, i, u8p, u8p, u32]
+        L.msm_frvec_inverse_device.argtypes = [i, i, vp, vp, vp, sz, u32]
+        L.msm_frvec_scan_device.argtypes = [i, i, vp, vp, vp, sz, sz, i, u32, vp]
+        L.msm_frvec_map.argtypes = [i, i, vp, vp, vp, vp, sz, i, u8p, u8p, u32]
+        L.msm_frvec_inverse.argtypes = [i, i, vp, vp, sz, u32]
+        L.msm_frvec_scan.argtypes = [i, i, vp, vp, sz, sz, i, u32, vp]
+        L.msm_frvec_release.argtypes = []
+        L.msm_frvec_release.restype = None
+        L.msm_frvec_test_tile.argtypes = [i]
+        L.msm_frvec_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
+        _frvec_lib = L
+    return _frvec_lib
+
+
+def frvec_test_tile(elements=0):
+    """test hook msm_frvec_test_tile: shrink the tile of scalars_inverse and scalars_scan to `elements` (0: the design's 1024)"""
+    _check(frvec_lib().msm_frvec_test_tile(int(elements)), "msm_frvec_test_tile")
+
+
+def frvec_last():
+    """(kernel launches, levels) of the last vector call of this process (test hook msm_frvec_test_last)"""
+    v = [C.c_int(), C.c_int()]
+    _check(frvec_lib().msm_frvec_test_last(*[C.byref(x) for x in v]), "msm_frvec_test_last")
+    return tuple(x.value for x in v)
+
+
+def frvec_release():
+    """msm_frvec_release: free the vector library's scratch and staging buffers (they come back with the next call)"""
+    frvec_lib().msm_frvec_release()
+
+
 def _check(code, where):
     if code != 0:
         raise MsmHipError(code, where)
@@ -666,6 +711,158 @@ class MsmContext:
         out = C.create_string_buffer(buf, max(len(buf), 1))
         _check(fr_lib().msm_fr_ntt(self.curve_id, self.device, C.cast(out, C.c_void_p), log_n, batch, wb, pre, post, flags), "msm_fr_ntt")
         return out.raw[:len(buf)]
+
+    # -- vector arithmetic over the scalar field (libmsm_frvec.so): what lies between a transform and the next commitment
+    FRVEC_EXCLUSIVE, FRVEC_MONT256 = 1, 2  # MSM_FRVEC_EXCLUSIVE, MSM_FRVEC_MONT256
+    FRVEC_MAX_ELEMENTS = 1 << 26
+    _FRVEC_MAPS = {"add": 0, "sub": 1, "mul": 2, "mul_add": 3, "mul_sub": 4}  # MSM_FRVEC_ADD ..
+    _FRVEC_SCANS = {"sum": 0, "product": 1}  # MSM_FRVEC_SUM, MSM_FRVEC_PRODUCT
+
+    def _frvec_field(self, what):
+        if self.curve not in SCALAR_FIELDS or self.curve == "grumpkin":
+            raise ValueError("%s is not offered on the scalar field of %s" % (what, self.curve))
+        if getattr(self, "scalar_width", 32) != 32:
+            raise ValueError("%s takes 32-byte scalars; the context's scalar format is %d bytes wide" % (what, self.scalar_width))
+        return SCALAR_FIELDS[self.curve]
+
+    def _frvec_vector(self, v, name):
+        """-> (tensor or None, bytes or None, number of scalars)"""
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            t, n = _as_device_u8(v, 32, name)
+            return t, None, n
+        b = bytes(v)
+        if len(b) % 32:
+            raise ValueError("%s must be n x 32 bytes" % name)
+        return None, b, len(b) // 32
+
+    def _frvec_out(self, out, t, n, on_device):
+        if out is None:
+            return None
+        if not on_device:
+            raise TypeError("out is for device vectors; host bytes return bytes")
+        if not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * n or not out.is_contiguous() or out.device != t.device:
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes on %s" % (n, t.device))
+        return out
+
+    def _frvec_map(self, op, a, b, c, out):
+        r = self._frvec_field("scalars_" + op)
+        if op not in self._FRVEC_MAPS:
+            raise ValueError("unknown op %r" % (op,))
+        ta, ba, n = self._frvec_vector(a, "a")
+        on_device = ta is not None
+        if n < 1 or n > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("a vector holds 1 .. 2^26 scalars, not %d" % n)
+        vecs, consts = [], []
+        for name, v in (("b", b), ("c", c)):
+            if v is None:  # (an op of two operands has no c)
+                vecs.append(None), consts.append(None)
+            elif isinstance(v, int) or (isinstance(v, (bytes, bytearray)) and len(v) == 32 and (on_device or n != 1)):
+                k = int.from_bytes(v, "little") if isinstance(v, (bytes, bytearray)) else int(v)
+                if not 0 <= k < r:
+                    raise ValueError("the constant %s must lie in [0, r)" % name)
+                vecs.append(None), consts.append(k.to_bytes(32, "little"))
+            else:
+                tv, bv, m = self._frvec_vector(v, name)
+                if (tv is not None) != on_device:
+                    raise TypeError("%s must be on the device exactly when a is" % name)
+                if m != n:
+                    raise ValueError("%s holds %d scalars, a holds %d" % (name, m, n))
+                vecs.append(tv if on_device else bv), consts.append(None)
+        out = self._frvec_out(out, ta, n, on_device)
+        flags = self.FRVEC_MONT256 if getattr(self, "scalar_mont256", False) else 0
+        code = self._FRVEC_MAPS[op]
+        if on_device:
+            self._order_after_torch(ta)
+            stream = lib().msm_hip_stream(self._h)
+            dst = a if out is None else out
+            ptr = [v.data_ptr() if v is not None else None for v in vecs]
+            _check(frvec_lib().msm_frvec_map_device(self.curve_id, self.device, stream, (ta if out is None else out).data_ptr(), ta.data_ptr(), ptr[0], ptr[1], n, code,
+                                                    consts[0], consts[1], flags), "msm_frvec_map_device")
+            return dst
+        buf = C.create_string_buffer(32 * n)
+        host = [C.cast(C.c_char_p(v), C.c_void_p) if v is not None else None for v in vecs]
+        _check(frvec_lib().msm_frvec_map(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), host[0], host[1], n, code, consts[0],
+                                         consts[1], flags), "msm_frvec_map")
+        return buf.raw
+
+    def scalars_add(self, a, b, out=None):
+        """a + b, element by element, over this context's scalar field (msm_frvec_map_device, include/msm_frvec.h).  a: a CUDA uint8 tensor of n x 32
+        bytes -- the result is written over it (out=None) or into `out`, on this context's stream, and that tensor is returned -- or host bytes
+        (bytes come back).  b: a vector like a, or an integer / its 32 little-endian bytes in [0, r), which is broadcast.  The vectors are in this
+        context's 32-byte scalar format (canonical, or mont256) and must be below r; a constant is always a plain integer.  (Beside a host vector of ONE scalar, 32 bytes
+        are a vector too.)"""
+        return self._frvec_map("add", a, b, None, out)
+
+    def scalars_sub(self, a, b, out=None):
+        """a - b (as scalars_add)"""
+        return self._frvec_map("sub", a, b, None, out)
+
+    def scalars_mul(self, a, b, out=None):
+        """a * b (as scalars_add)"""
+        return self._frvec_map("mul", a, b, None, out)
+
+    def scalars_mul_add(self, a, b, c, out=None):
+        """a * b + c (as scalars_add; c: a vector or a constant, like b)"""
+        if c is None:
+            raise ValueError("scalars_mul_add needs c")
+        return self._frvec_map("mul_add", a, b, c, out)
+
+    def scalars_mul_sub(self, a, b, c, out=None):
+        """a * b - c (as scalars_mul_add)"""
+        if c is None:
+            raise ValueError("scalars_mul_sub needs c")
+        return self._frvec_map("mul_sub", a, b, c, out)
+
+    def scalars_inverse(self, a, out=None):
+        """1 / a element by element, 1 / 0 = 0 (msm_frvec_inverse_device): Montgomery's trick on the device, with one Fermat inversion per call.
+        a, out: as scalars_add."""
+        self._frvec_field("scalars_inverse")
+        ta, ba, n = self._frvec_vector(a, "a")
+        on_device = ta is not None
+        if n < 1 or n > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("a vector holds 1 .. 2^26 scalars, not %d" % n)
+        out = self._frvec_out(out, ta, n, on_device)
+        flags = self.FRVEC_MONT256 if getattr(self, "scalar_mont256", False) else 0
+        if on_device:
+            self._order_after_torch(ta)
+            stream = lib().msm_hip_stream(self._h)
+            _check(frvec_lib().msm_frvec_inverse_device(self.curve_id, self.device, stream, (ta if out is None else out).data_ptr(), ta.data_ptr(), n, flags),
+                   "msm_frvec_inverse_device")
+            return a if out is None else out
+        buf = C.create_string_buffer(32 * n)
+        _check(frvec_lib().msm_frvec_inverse(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, flags), "msm_frvec_inverse")
+        return buf.raw
+
+    def scalars_scan(self, a, op="product", exclusive=False, batch=1, out=None, totals=False):
+        """Running products (op="product") or sums (op="sum") along each of `batch` rows of a (msm_frvec_scan_device): out[i] = a[0] o .. o a[i];
+        exclusive=True: a[0] o .. o a[i - 1], and out[0] is 1 (0 for sums).  a, out: as scalars_add.  totals=True: returns (result, totals) with
+        every row's total -- what an exclusive scan does not store, e.g. the closing value of a grand product -- as batch x 32 host bytes."""
+        self._frvec_field("scalars_scan")
+        if op not in self._FRVEC_SCANS:
+            raise ValueError("op must be \"sum\" or \"product\", not %r" % (op,))
+        batch = int(batch)
+        ta, ba, total = self._frvec_vector(a, "a")
+        on_device = ta is not None
+        if batch < 1 or total < 1 or total % batch or total > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not %d rows of 1 .. 2^26 / batch scalars" % (total, batch))
+        n = total // batch
+        out = self._frvec_out(out, ta, total, on_device)
+        flags = (self.FRVEC_MONT256 if getattr(self, "scalar_mont256", False) else 0) | (self.FRVEC_EXCLUSIVE if exclusive else 0)
+        tot = C.create_string_buffer(32 * batch) if totals else None
+        tot_ptr = C.cast(tot, C.c_void_p) if totals else None
+        code = self._FRVEC_SCANS[op]
+        if on_device:
+            self._order_after_torch(ta)
+            stream = lib().msm_hip_stream(self._h)
+            _check(frvec_lib().msm_frvec_scan_device(self.curve_id, self.device, stream, (ta if out is None else out).data_ptr(), ta.data_ptr(), n, batch, code, flags,
+                                                     tot_ptr), "msm_frvec_scan_device")
+            res = a if out is None else out
+        else:
+            buf = C.create_string_buffer(32 * total)
+            _check(frvec_lib().msm_frvec_scan(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, batch, code, flags, tot_ptr),
+                   "msm_frvec_scan")
+            res = buf.raw
+        return (res, tot.raw) if totals else res
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so and libmsm_fr.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, libmsm_fr.so and libmsm_frvec.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -15,6 +15,12 @@ FR_UNITS = ["fr_bn254.hip", "fr_pallas.hip", "fr_vesta.hip", "fr_bls12_381.hip"]
 FR_SOURCES = FR_UNITS + ["fr_unit.h", "ntt_kernels.h", "ntt_host.h", "ntt_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h", "fr_pallas_constants.h",
                          "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
 FR_HEADERS = [os.path.join(HERE, "..", "include", "msm_fr.h"), HEADER]
+# libmsm_frvec.so (include/msm_frvec.h): vector arithmetic over the scalar field -- map, batch inverse, scan --, the third library, built the same way
+FRVEC_SO = os.path.join(HERE, "libmsm_frvec.so")
+FRVEC_UNITS = ["frvec_bn254.hip", "frvec_pallas.hip", "frvec_vesta.hip", "frvec_bls12_381.hip"]
+FRVEC_SOURCES = FRVEC_UNITS + ["frvec_unit.h", "frvec_kernels.h", "frvec_host.h", "frvec_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
+                               "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FRVEC_HEADERS = [os.path.join(HERE, "..", "include", "msm_frvec.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -67,6 +73,44 @@ def fr_device_asm_is_current():
         return False
     newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FR_SOURCES if os.path.exists(os.path.join(CSRC, f)))
     return all(os.path.getmtime(f) >= newest for f in fr_device_asm_files())
+
+
+def frvec_device_asm_files():
+    """The device assembly of libmsm_frvec.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRVEC_UNITS]
+
+
+def frvec_build_stamp():
+    """build_stamp() for libmsm_frvec.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FRVEC_SOURCES)] + FRVEC_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def frvec_needs_build():
+    """libmsm_frvec.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FRVEC_SO + ".stamp") as f:
+            return not os.path.exists(FRVEC_SO) or f.read().strip() != frvec_build_stamp()
+    except OSError:
+        return True
+
+
+def frvec_device_asm_is_current():
+    """device_asm_is_current() for libmsm_frvec.so's units"""
+    if frvec_needs_build() or not all(os.path.exists(f) for f in frvec_device_asm_files()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRVEC_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in frvec_device_asm_files())
 
 
 def build_stamp():
@@ -143,9 +187,10 @@ def compile_flags():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
-    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so and msm-webgpu_amd/libmsm_frvec.so.  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
-    if not do_hip and not do_fr:
+    do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
+    if not do_hip and not do_fr and not do_frvec:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -173,8 +218,8 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of both libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else [])
+    # one pool for the units of all three libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else [])
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
@@ -185,6 +230,10 @@ def build(force=False, verbose=False):
         link([objs[u] for u in FR_UNITS], FR_SO)
         with open(FR_SO + ".stamp", "w") as f:
             f.write(fr_build_stamp() + "\n")
+    if do_frvec:
+        link([objs[u] for u in FRVEC_UNITS], FRVEC_SO)
+        with open(FRVEC_SO + ".stamp", "w") as f:
+            f.write(frvec_build_stamp() + "\n")
     return SO
 
 
