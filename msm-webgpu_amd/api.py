@@ -264,6 +264,55 @@ def frvec_release():
     frvec_lib().msm_frvec_release()
 
 
+_frpoly_lib = None
+
+
+def frpoly_lib():
+    """Load libmsm_frpoly.so (in-tree; include/msm_frpoly.h): polynomial opening over the scalar field.  Raises if it has not been built -- there is
+    no fallback path."""
+    global _frpoly_lib
+    if _frpoly_lib is None:
+        so = _build.FRPOLY_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frpoly.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
+        L.msm_frpoly_abi_version.restype = i
+        L.msm_frpoly_eval_device.argtypes = [i, i, vp, vp, sz, sz, u8p, u32, vp]
+        L.msm_frpoly_divide_device.argtypes = [i, i, vp, vp, vp, sz, sz, u8p, u32, vp]
+        L.msm_frpoly_dot_device.argtypes = [i, i, vp, vp, vp, sz, sz, u32, vp]
+        L.msm_frpoly_combine_device.argtypes = [i, i, vp, vp, vp, sz, sz, u8p, u32]
+        L.msm_frpoly_powers_device.argtypes = [i, i, vp, vp, sz, u8p, u8p, u32]
+        L.msm_frpoly_eval.argtypes = [i, i, vp, sz, sz, u8p, u32, vp]
+        L.msm_frpoly_divide.argtypes = [i, i, vp, vp, sz, sz, u8p, u32, vp]
+        L.msm_frpoly_dot.argtypes = [i, i, vp, vp, sz, sz, u32, vp]
+        L.msm_frpoly_combine.argtypes = [i, i, vp, vp, sz, sz, u8p, u32]
+        L.msm_frpoly_powers.argtypes = [i, i, vp, sz, u8p, u8p, u32]
+        L.msm_frpoly_release.argtypes = []
+        L.msm_frpoly_release.restype = None
+        L.msm_frpoly_test_tile.argtypes = [i]
+        L.msm_frpoly_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
+        _frpoly_lib = L
+    return _frpoly_lib
+
+
+def frpoly_test_tile(elements=0):
+    """test hook msm_frpoly_test_tile: shrink the tile of scalars_eval, scalars_divide and scalars_dot to `elements` (0: the design's 1024)"""
+    _check(frpoly_lib().msm_frpoly_test_tile(int(elements)), "msm_frpoly_test_tile")
+
+
+def frpoly_last():
+    """(kernel launches, levels) of the last opening call of this process (test hook msm_frpoly_test_last)"""
+    v = [C.c_int(), C.c_int()]
+    _check(frpoly_lib().msm_frpoly_test_last(*[C.byref(x) for x in v]), "msm_frpoly_test_last")
+    return tuple(x.value for x in v)
+
+
+def frpoly_release():
+    """msm_frpoly_release: free the opening library's scratch, constants and staging buffers (they come back with the next call)"""
+    frpoly_lib().msm_frpoly_release()
+
+
 def _check(code, where):
     if code != 0:
         raise MsmHipError(code, where)
@@ -863,6 +912,143 @@ class MsmContext:
                    "msm_frvec_scan")
             res = buf.raw
         return (res, tot.raw) if totals else res
+
+    # -- polynomial opening over the scalar field (libmsm_frpoly.so): what follows the last commitment
+    FRPOLY_SHARED_B, FRPOLY_MONT256, FRPOLY_MAX_ROWS = 1, 2, 256  # MSM_FRPOLY_SHARED_B, MSM_FRPOLY_MONT256, MSM_FRPOLY_MAX_ROWS
+
+    def _frpoly_const(self, v, r, name):
+        k = int.from_bytes(v, "little") if isinstance(v, (bytes, bytearray)) else int(v)
+        if isinstance(v, (bytes, bytearray)) and len(v) != 32:
+            raise ValueError("%s must be an integer or its 32 little-endian bytes" % name)
+        if not 0 <= k < r:
+            raise ValueError("%s must lie in [0, r)" % name)
+        return k.to_bytes(32, "little")
+
+    def _frpoly_rows(self, a, batch, name="a"):
+        """-> (tensor or None, bytes or None, scalars per row)"""
+        batch = int(batch)
+        ta, ba, total = self._frvec_vector(a, name)
+        if batch < 1 or total < 1 or total % batch or total > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not %d rows of 1 .. 2^26 / batch scalars" % (total, batch))
+        return ta, ba, total // batch
+
+    def _frpoly_flags(self):
+        return self.FRPOLY_MONT256 if getattr(self, "scalar_mont256", False) else 0
+
+    def scalars_eval(self, a, z, batch=1):
+        """The values a(z) = sum_j a[j] z^j of `batch` polynomials given by their coefficients, one row of a each (msm_frpoly_eval_device,
+        include/msm_frpoly.h) -> batch x 32 host bytes in the data's form.  a: a CUDA uint8 tensor of batch x n x 32 bytes, or host bytes, in this
+        context's 32-byte scalar format; z: an integer in [0, r) or its 32 little-endian bytes, always a plain integer."""
+        r = self._frvec_field("scalars_eval")
+        ta, ba, n = self._frpoly_rows(a, batch)
+        zb = self._frpoly_const(z, r, "z")
+        values = C.create_string_buffer(32 * int(batch))
+        if ta is not None:
+            self._order_after_torch(ta)
+            _check(frpoly_lib().msm_frpoly_eval_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), ta.data_ptr(), n, int(batch), zb, self._frpoly_flags(),
+                                                       C.cast(values, C.c_void_p)), "msm_frpoly_eval_device")
+        else:
+            _check(frpoly_lib().msm_frpoly_eval(self.curve_id, self.device, C.cast(C.c_char_p(ba), C.c_void_p), n, int(batch), zb, self._frpoly_flags(),
+                                                C.cast(values, C.c_void_p)), "msm_frpoly_eval")
+        return values.raw
+
+    def scalars_divide(self, a, z, batch=1, out=None, values=False):
+        """(a(X) - a(z)) / (X - z) for every row of a, by synthetic division (msm_frpoly_divide_device): out[i] = sum_{j > i} a[j] z^(j - i - 1), kept
+        at the length of a (the last coefficient is 0).  a, out: as scalars_add -- in place on a device tensor unless `out` is given; z, batch: as
+        scalars_eval.  values=True: returns (quotients, values) with every a(z) as batch x 32 host bytes."""
+        r = self._frvec_field("scalars_divide")
+        ta, ba, n = self._frpoly_rows(a, batch)
+        batch = int(batch)
+        zb = self._frpoly_const(z, r, "z")
+        on_device = ta is not None
+        out = self._frvec_out(out, ta, n * batch, on_device)
+        vals = C.create_string_buffer(32 * batch) if values else None
+        vals_ptr = C.cast(vals, C.c_void_p) if values else None
+        if on_device:
+            self._order_after_torch(ta)
+            _check(frpoly_lib().msm_frpoly_divide_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), (ta if out is None else out).data_ptr(), ta.data_ptr(), n,
+                                                         batch, zb, self._frpoly_flags(), vals_ptr), "msm_frpoly_divide_device")
+            res = a if out is None else out
+        else:
+            buf = C.create_string_buffer(32 * n * batch)
+            _check(frpoly_lib().msm_frpoly_divide(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, batch, zb, self._frpoly_flags(),
+                                                  vals_ptr), "msm_frpoly_divide")
+            res = buf.raw
+        return (res, vals.raw) if values else res
+
+    def scalars_dot(self, a, b, batch=1):
+        """sum_j a[row][j] b[row][j] for every row of a (msm_frpoly_dot_device) -> batch x 32 host bytes in the data's form.  b: as many scalars as
+        a, or -- beside batch > 1 -- one row of n scalars that is used for every row of a.  a and b are both device tensors or both host bytes."""
+        self._frvec_field("scalars_dot")
+        ta, ba, n = self._frpoly_rows(a, batch)
+        batch = int(batch)
+        tb, bb, m = self._frvec_vector(b, "b")
+        if (tb is not None) != (ta is not None):
+            raise TypeError("b must be on the device exactly when a is")
+        if m != n * batch and m != n:
+            raise ValueError("b holds %d scalars; a holds %d rows of %d" % (m, batch, n))
+        flags = self._frpoly_flags() | (self.FRPOLY_SHARED_B if m == n and batch > 1 else 0)
+        values = C.create_string_buffer(32 * batch)
+        if ta is not None:
+            self._order_after_torch(ta)
+            _check(frpoly_lib().msm_frpoly_dot_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), ta.data_ptr(), tb.data_ptr(), n, batch, flags,
+                                                      C.cast(values, C.c_void_p)), "msm_frpoly_dot_device")
+        else:
+            _check(frpoly_lib().msm_frpoly_dot(self.curve_id, self.device, C.cast(C.c_char_p(ba), C.c_void_p), C.cast(C.c_char_p(bb), C.c_void_p), n, batch, flags,
+                                               C.cast(values, C.c_void_p)), "msm_frpoly_dot")
+        return values.raw
+
+    def scalars_combine(self, a, coeffs, out=None):
+        """out[i] = sum_k coeffs[k] a[k][i]: the linear combination of the len(coeffs) rows of a (msm_frpoly_combine_device), e.g. the fold of the
+        polynomials of a batched opening with powers of a challenge.  coeffs: 1 .. 256 integers in [0, r) (or their 32-byte encodings).  a: a CUDA
+        uint8 tensor of len(coeffs) x n x 32 bytes -- the n scalars of the result go into `out` (a CUDA uint8 tensor, which may be row 0 of a) or
+        a new tensor -- or host bytes (bytes come back)."""
+        r = self._frvec_field("scalars_combine")
+        coeffs = list(coeffs)
+        if not 1 <= len(coeffs) <= self.FRPOLY_MAX_ROWS:
+            raise ValueError("a combination takes 1 .. %d rows, not %d" % (self.FRPOLY_MAX_ROWS, len(coeffs)))
+        ta, ba, n = self._frpoly_rows(a, len(coeffs))
+        cb = b"".join(self._frpoly_const(c, r, "a coefficient") for c in coeffs)
+        on_device = ta is not None
+        out = self._frvec_out(out, ta, n, on_device)
+        if on_device:
+            if out is None:
+                out = torch.empty((n, 32), dtype=torch.uint8, device=ta.device)
+            self._order_after_torch(ta)
+            _check(frpoly_lib().msm_frpoly_combine_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), out.data_ptr(), ta.data_ptr(), n, len(coeffs), cb,
+                                                          self._frpoly_flags()), "msm_frpoly_combine_device")
+            return out
+        buf = C.create_string_buffer(32 * n)
+        _check(frpoly_lib().msm_frpoly_combine(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, len(coeffs), cb,
+                                               self._frpoly_flags()), "msm_frpoly_combine")
+        return buf.raw
+
+    def scalars_powers(self, g, n, scale=1, out=None):
+        """scale * g^i for i < n as a CUDA uint8 tensor of n x 32 bytes in this context's scalar format (msm_frpoly_powers_device): the powers of a
+        challenge, or the evaluation domain from a root of unity.  g, scale: integers in [0, r) or their 32 little-endian bytes."""
+        r = self._frvec_field("scalars_powers")
+        n = int(n)
+        if n < 1 or n > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("a vector holds 1 .. 2^26 scalars, not %d" % n)
+        gb, cb = self._frpoly_const(g, r, "g"), self._frpoly_const(scale, r, "scale")
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes" % n)
+        self._order_after_torch(out)
+        _check(frpoly_lib().msm_frpoly_powers_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), out.data_ptr(), n, gb, cb, self._frpoly_flags()),
+               "msm_frpoly_powers_device")
+        return out
+
+    def kzg_open(self, coeffs, z):
+        """A KZG opening of the polynomial with the coefficients `coeffs` (a CUDA uint8 tensor of n x 32 bytes, n <= the resident bases, or host
+        bytes) at z over the resident monomial bases tau^j G: -> (y, W) with y = f(z) as 32 bytes in the data's form and W the commitment (G1) to
+        (f - y) / (X - z).  scalars_divide into a fresh tensor, then msm."""
+        if isinstance(coeffs, torch.Tensor) and coeffs.is_cuda:
+            q, y = self.scalars_divide(coeffs, z, out=torch.empty_like(coeffs), values=True)
+        else:
+            q, y = self.scalars_divide(coeffs, z, values=True)
+        return y, self.msm(q)
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so, libmsm_fr.so and libmsm_frvec.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so and libmsm_frpoly.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -21,6 +21,12 @@ FRVEC_UNITS = ["frvec_bn254.hip", "frvec_pallas.hip", "frvec_vesta.hip", "frvec_
 FRVEC_SOURCES = FRVEC_UNITS + ["frvec_unit.h", "frvec_kernels.h", "frvec_host.h", "frvec_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
                                "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
 FRVEC_HEADERS = [os.path.join(HERE, "..", "include", "msm_frvec.h"), HEADER]
+# libmsm_frpoly.so (include/msm_frpoly.h): polynomial opening over the scalar field -- eval, divide, dot, combine, powers --, the fourth library
+FRPOLY_SO = os.path.join(HERE, "libmsm_frpoly.so")
+FRPOLY_UNITS = ["frpoly_bn254.hip", "frpoly_pallas.hip", "frpoly_vesta.hip", "frpoly_bls12_381.hip"]
+FRPOLY_SOURCES = FRPOLY_UNITS + ["frpoly_unit.h", "frpoly_kernels.h", "frpoly_host.h", "frpoly_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
+                                 "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FRPOLY_HEADERS = [os.path.join(HERE, "..", "include", "msm_frpoly.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -113,6 +119,44 @@ def frvec_device_asm_is_current():
     return all(os.path.getmtime(f) >= newest for f in frvec_device_asm_files())
 
 
+def frpoly_device_asm_paths():
+    """The device assembly of libmsm_frpoly.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRPOLY_UNITS]
+
+
+def frpoly_build_stamp():
+    """build_stamp() for libmsm_frpoly.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FRPOLY_SOURCES)] + FRPOLY_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def frpoly_needs_build():
+    """libmsm_frpoly.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FRPOLY_SO + ".stamp") as f:
+            return not os.path.exists(FRPOLY_SO) or f.read().strip() != frpoly_build_stamp()
+    except OSError:
+        return True
+
+
+def frpoly_device_asm_is_current():
+    """device_asm_is_current() for libmsm_frpoly.so's units"""
+    if frpoly_needs_build() or not all(os.path.exists(f) for f in frpoly_device_asm_paths()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRPOLY_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in frpoly_device_asm_paths())
+
+
 def build_stamp():
     """what the library on disk must have been built FROM to be the product: a hash over the compile flags (the environment switches of the
     diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source.  Written next to the
@@ -187,10 +231,11 @@ def compile_flags():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
-    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so and msm-webgpu_amd/libmsm_frvec.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so and msm-webgpu_amd/libmsm_frpoly.so.  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
     do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
-    if not do_hip and not do_fr and not do_frvec:
+    do_frpoly = (force and not os.environ.get("MSM_HIP_SO")) or frpoly_needs_build()
+    if not do_hip and not do_fr and not do_frvec and not do_frpoly:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -218,8 +263,8 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of all three libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else [])
+    # one pool for the units of all four libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else [])
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
@@ -234,6 +279,10 @@ def build(force=False, verbose=False):
         link([objs[u] for u in FRVEC_UNITS], FRVEC_SO)
         with open(FRVEC_SO + ".stamp", "w") as f:
             f.write(frvec_build_stamp() + "\n")
+    if do_frpoly:
+        link([objs[u] for u in FRPOLY_UNITS], FRPOLY_SO)
+        with open(FRPOLY_SO + ".stamp", "w") as f:
+            f.write(frpoly_build_stamp() + "\n")
     return SO
 
 

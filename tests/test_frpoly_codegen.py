@@ -1,0 +1,74 @@
+"""The code-generation gates (tools/check_long_branch_hazard.py, tools/check_machine_verifier.py) over the four units of libmsm_frpoly.so, which
+are not among the other three libraries' units; every unit's kernels sit in the unit's own namespace, none of them uses scratch memory, and the
+library on disk is the current sources'."""
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import check_long_branch_hazard as chk  # noqa: E402
+
+KERNELS = ("k_frpoly_fold", "k_frpoly_suffix", "k_frpoly_combine", "k_frpoly_powers")
+
+
+def _units():
+    import importlib
+
+    return list(importlib.import_module("msm_webgpu_amd.build").FRPOLY_UNITS)
+
+
+def test_frpoly_units_have_no_long_branch_hazard(built):
+    paths = chk.compile_to_asm([], units=_units())
+    assert len(paths) == 4 and all("frpoly_" in os.path.basename(p) for p in paths)
+    for path in paths:
+        long_branches, found, live = chk.check_file(path)
+        assert found == [] and live == [], (path, found, live)
+
+
+def test_frpoly_units_pass_the_machine_verifier():
+    import check_machine_verifier as mv
+
+    reports = mv.check(units=_units())
+    assert sorted(reports) == sorted(_units())
+    for unit, found in reports.items():
+        assert found == [], (unit, found)
+
+
+def test_each_unit_holds_its_four_kernels_in_its_own_namespace_without_scratch(built):
+    for path in chk.compile_to_asm([], units=_units()):
+        with open(path) as f:
+            text = f.read()
+        names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
+        field = "frp_" + os.path.basename(path).split("-hip-")[0][len("frpoly_"):]
+        assert len(names) == len(KERNELS), (path, names)
+        for k in KERNELS:
+            assert any(("%d%s" % (len(field), field)) in n and ("%d%s" % (len(k), k)) in n for n in names), (path, k, names)
+        # the kernel descriptors and the metadata: no private segment, nothing spilled, no dynamic stack
+        assert re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.vgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS) and re.findall(r"\.sgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert not re.search(r"\.uses_dynamic_stack:\s+true", text), path
+        # LDS: the two buffers of the suffix scan, as libmsm_frvec.so's scan (18 KiB), are the most
+        assert max(int(v) for v in re.findall(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", text)) <= 18 * 1024, path
+
+
+def test_library_on_disk_was_built_from_the_current_sources(built):
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert os.path.exists(b.FRPOLY_SO) and not b.frpoly_needs_build()
+    assert b.frpoly_device_asm_is_current()
+
+
+def test_the_other_libraries_do_not_depend_on_this_one():
+    """libmsm_frpoly.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert sorted(b.FRPOLY_UNITS) == ["frpoly_bls12_381.hip", "frpoly_bn254.hip", "frpoly_pallas.hip", "frpoly_vesta.hip"]
+    assert not any(f.startswith("frpoly_") for f in b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES)
+    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_")) for f in b.FRPOLY_SOURCES)  # (no kernel of the other three)
+    for u in b.FRPOLY_SOURCES:
+        assert os.path.exists(os.path.join(b.CSRC, u)), u
