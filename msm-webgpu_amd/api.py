@@ -313,6 +313,58 @@ def frpoly_release():
     frpoly_lib().msm_frpoly_release()
 
 
+_frmle_lib = None
+
+
+class FrmleTerm(C.Structure):
+    """msm_frmle_term (include/msm_frmle.h): coeff * prod_{f < degree} row[rows[f]]"""
+    _fields_ = [("coeff", C.c_uint8 * 32), ("degree", C.c_uint32), ("rows", C.c_uint32 * 4)]
+
+
+def frmle_lib():
+    """Load libmsm_frmle.so (in-tree; include/msm_frmle.h): the sumcheck over multilinear tables of the scalar field.  Raises if it has not been built
+    -- there is no fallback path."""
+    global _frmle_lib
+    if _frmle_lib is None:
+        so = _build.FRMLE_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frmle.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, u8p, sz, i, u32, tp = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrmleTerm)
+        L.msm_frmle_abi_version.restype = i
+        L.msm_frmle_fold_device.argtypes = [i, i, vp, vp, vp, sz, sz, sz, u8p, u32]
+        L.msm_frmle_eval_device.argtypes = [i, i, vp, vp, sz, sz, sz, u8p, u32, vp]
+        L.msm_frmle_eq_device.argtypes = [i, i, vp, vp, sz, u8p, u8p, u32]
+        L.msm_frmle_round_device.argtypes = [i, i, vp, vp, sz, sz, sz, tp, sz, u8p, u32, vp]
+        L.msm_frmle_fold.argtypes = [i, i, vp, vp, sz, sz, sz, u8p, u32]
+        L.msm_frmle_eval.argtypes = [i, i, vp, sz, sz, sz, u8p, u32, vp]
+        L.msm_frmle_eq.argtypes = [i, i, vp, sz, u8p, u8p, u32]
+        L.msm_frmle_round.argtypes = [i, i, vp, sz, sz, sz, tp, sz, u8p, u32, vp]
+        L.msm_frmle_release.argtypes = []
+        L.msm_frmle_release.restype = None
+        L.msm_frmle_test_tile.argtypes = [i]
+        L.msm_frmle_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
+        _frmle_lib = L
+    return _frmle_lib
+
+
+def frmle_test_tile(elements=0):
+    """test hook msm_frmle_test_tile: shrink the tile of scalars_mle_eval and scalars_sumcheck_round to `elements` (0: the design's 1024)"""
+    _check(frmle_lib().msm_frmle_test_tile(int(elements)), "msm_frmle_test_tile")
+
+
+def frmle_last():
+    """(kernel launches, levels) of the last sumcheck call of this process (test hook msm_frmle_test_last)"""
+    v = [C.c_int(), C.c_int()]
+    _check(frmle_lib().msm_frmle_test_last(*[C.byref(x) for x in v]), "msm_frmle_test_last")
+    return tuple(x.value for x in v)
+
+
+def frmle_release():
+    """msm_frmle_release: free the sumcheck library's scratch, constants and staging buffers (they come back with the next call)"""
+    frmle_lib().msm_frmle_release()
+
+
 def _check(code, where):
     if code != 0:
         raise MsmHipError(code, where)
@@ -1049,6 +1101,162 @@ class MsmContext:
         else:
             q, y = self.scalars_divide(coeffs, z, values=True)
         return y, self.msm(q)
+
+    # -- the sumcheck over multilinear tables of the scalar field (libmsm_frmle.so): the loop between the commitments of a Nova / Spartan /
+    # HyperPlonk-style prover.  The FIRST variable of a table is the TOP bit of its index (include/msm_frmle.h).
+    FRMLE_MONT256, FRMLE_MAX_DEGREE, FRMLE_MAX_TERMS, FRMLE_MAX_ROWS = 2, 4, 8, 16  # MSM_FRMLE_MONT256, MSM_FRMLE_MAX_DEGREE, ..
+
+    def _frmle_field(self, what):
+        """every curve's scalar field, Grumpkin's included (a G2 context takes its G1's)"""
+        if self.curve not in SCALAR_FIELDS:
+            raise ValueError("%s is not offered on the scalar field of %s" % (what, self.curve))
+        if getattr(self, "scalar_width", 32) != 32:
+            raise ValueError("%s takes 32-byte scalars; the context's scalar format is %d bytes wide" % (what, self.scalar_width))
+        return SCALAR_FIELDS[self.curve]
+
+    def _frmle_flags(self):
+        return self.FRMLE_MONT256 if getattr(self, "scalar_mont256", False) else 0
+
+    def _frmle_rows(self, a, batch, n, least):
+        """-> (tensor or None, bytes or None, n, stride): `batch` rows, stride = scalars / batch apart, of which the first n (default: all) are the table"""
+        batch = int(batch)
+        ta, ba, total = self._frvec_vector(a, "a")
+        if batch < 1 or total < 1 or total % batch or total > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not %d rows of 1 .. 2^26 / batch scalars" % (total, batch))
+        stride = total // batch
+        n = stride if n is None else int(n)
+        if n < least or n > stride or n & (n - 1):
+            raise ValueError("a table holds a power of two of scalars, at least %d and at most the %d of a row, not %d" % (least, stride, n))
+        return ta, ba, n, stride
+
+    def scalars_mle_fold(self, a, c, batch=1, n=None, out=None):
+        """Bind the top variable of `batch` multilinear tables to c (msm_frmle_fold_device, include/msm_frmle.h): row[i] = row[i] + c (row[i + n/2] -
+        row[i]) for i < n / 2.  a: a CUDA uint8 tensor of batch x N x 32 bytes -- folded in place, or into `out` (same size; only the first n / 2
+        scalars of every row are written) -- or host bytes (bytes of the same layout come back).  n: the table's length, a power of two <= N
+        (default N): a sumcheck keeps halving n in one buffer.  c: an integer in [0, r) or its 32 little-endian bytes, always a plain integer."""
+        r = self._frmle_field("scalars_mle_fold")
+        ta, ba, n, stride = self._frmle_rows(a, batch, n, 2)
+        batch = int(batch)
+        cb = self._frpoly_const(c, r, "c")
+        on_device = ta is not None
+        out = self._frvec_out(out, ta, stride * batch, on_device)
+        if on_device:
+            self._order_after_torch(ta)
+            _check(frmle_lib().msm_frmle_fold_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), (ta if out is None else out).data_ptr(), ta.data_ptr(), n,
+                                                     batch, stride, cb, self._frmle_flags()), "msm_frmle_fold_device")
+            return a if out is None else out
+        buf = C.create_string_buffer(ba, len(ba))
+        _check(frmle_lib().msm_frmle_fold(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, batch, stride, cb,
+                                          self._frmle_flags()), "msm_frmle_fold")
+        return buf.raw
+
+    def scalars_mle_eval(self, a, point, batch=1, n=None):
+        """The multilinear extensions of `batch` tables at `point` (msm_frmle_eval_device) -> batch x 32 host bytes in the data's form.  point:
+        log2(n) integers in [0, r) (or their 32-byte encodings); point[0] is the variable at the TOP bit of the index -- a table indexed with x_0 at
+        the lowest bit passes its point reversed.  a, batch, n: as scalars_mle_fold; nothing is written."""
+        r = self._frmle_field("scalars_mle_eval")
+        ta, ba, n, stride = self._frmle_rows(a, batch, n, 1)
+        batch = int(batch)
+        point = list(point)
+        if len(point) != n.bit_length() - 1:
+            raise ValueError("a table of %d scalars has %d variables, the point %d" % (n, n.bit_length() - 1, len(point)))
+        pb = b"".join(self._frpoly_const(z, r, "a coordinate of the point") for z in point)
+        values = C.create_string_buffer(32 * batch)
+        if ta is not None:
+            self._order_after_torch(ta)
+            _check(frmle_lib().msm_frmle_eval_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), ta.data_ptr(), n, batch, stride, pb, self._frmle_flags(),
+                                                     C.cast(values, C.c_void_p)), "msm_frmle_eval_device")
+        else:
+            _check(frmle_lib().msm_frmle_eval(self.curve_id, self.device, C.cast(C.c_char_p(ba), C.c_void_p), n, batch, stride, pb, self._frmle_flags(),
+                                              C.cast(values, C.c_void_p)), "msm_frmle_eval")
+        return values.raw
+
+    def scalars_eq(self, point, scale=1, out=None):
+        """The table of scale * eq(point, .) over {0, 1}^k, k = len(point), as a CUDA uint8 tensor of 2^k x 32 bytes in this context's scalar format
+        (msm_frmle_eq_device): out[i] = scale prod_j (bit_(k-1-j)(i) ? point[j] : 1 - point[j]).  point, scale: integers in [0, r) or their 32
+        little-endian bytes."""
+        r = self._frmle_field("scalars_eq")
+        point = list(point)
+        if len(point) > 26:
+            raise ValueError("a table holds at most 2^26 scalars, not 2^%d" % len(point))
+        n = 1 << len(point)
+        pb = b"".join(self._frpoly_const(z, r, "a coordinate of the point") for z in point)
+        cb = self._frpoly_const(scale, r, "scale")
+        if out is None:
+            out = torch.empty((n, 32), dtype=torch.uint8, device="cuda:%d" % self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * n or not out.is_contiguous():
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes" % n)
+        self._order_after_torch(out)
+        _check(frmle_lib().msm_frmle_eq_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), out.data_ptr(), n, pb, cb, self._frmle_flags()),
+               "msm_frmle_eq_device")
+        return out
+
+    def _frmle_terms(self, terms, batch, r):
+        """[(coeff, (row, ..)), ..] -> (array of msm_frmle_term, the largest degree)"""
+        terms = list(terms)
+        if not 1 <= len(terms) <= self.FRMLE_MAX_TERMS:
+            raise ValueError("a round takes 1 .. %d terms, not %d" % (self.FRMLE_MAX_TERMS, len(terms)))
+        arr = (FrmleTerm * len(terms))()
+        top = 0
+        for t, (coeff, rows) in zip(arr, terms):
+            rows = [int(x) for x in rows]
+            if not 1 <= len(rows) <= self.FRMLE_MAX_DEGREE:
+                raise ValueError("a term has 1 .. %d factors, not %d" % (self.FRMLE_MAX_DEGREE, len(rows)))
+            if any(not 0 <= x < batch for x in rows):
+                raise ValueError("a term names a row outside the %d rows" % batch)
+            t.coeff[:] = self._frpoly_const(coeff, r, "a coefficient")
+            t.degree = len(rows)
+            t.rows[:len(rows)] = rows
+            top = max(top, len(rows))
+        return arr, top
+
+    def scalars_sumcheck_round(self, a, terms, batch=1, n=None, fold=None):
+        """The values g(0) .. g(D) of a sumcheck round polynomial over `batch` multilinear tables (msm_frmle_round_device) -> (D + 1) x 32 host bytes
+        in the data's form: g(t) = sum_{i < n/2} sum_terms coeff prod_f (row_f[i] + t (row_f[i + n/2] - row_f[i])), D the largest degree.  terms:
+        1 .. 8 pairs (coeff, (row, ..)) of a plain integer coefficient and 1 .. 4 row numbers (a row may repeat); batch <= 16.  fold: None, or the
+        previous round's challenge -- the call then first binds the top variable of ALL rows to it, in place (as scalars_mle_fold, n >= 4), and
+        returns the round values of the folded tables, of n / 2 scalars: one pass over the data per round.  a, n: as scalars_mle_fold; host bytes
+        with fold return (values, the folded bytes)."""
+        r = self._frmle_field("scalars_sumcheck_round")
+        ta, ba, n, stride = self._frmle_rows(a, batch, n, 2 if fold is None else 4)
+        batch = int(batch)
+        if batch > self.FRMLE_MAX_ROWS:
+            raise ValueError("a round takes at most %d rows, not %d" % (self.FRMLE_MAX_ROWS, batch))
+        arr, top = self._frmle_terms(terms, batch, r)
+        fb = None if fold is None else self._frpoly_const(fold, r, "fold")
+        values = C.create_string_buffer(32 * (self.FRMLE_MAX_DEGREE + 1))
+        if ta is not None:
+            self._order_after_torch(ta)
+            _check(frmle_lib().msm_frmle_round_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), ta.data_ptr(), n, batch, stride, arr, len(arr), fb,
+                                                      self._frmle_flags(), C.cast(values, C.c_void_p)), "msm_frmle_round_device")
+            return values.raw[:32 * (top + 1)]
+        buf = C.create_string_buffer(ba, len(ba))
+        _check(frmle_lib().msm_frmle_round(self.curve_id, self.device, C.cast(buf, C.c_void_p), n, batch, stride, arr, len(arr), fb, self._frmle_flags(),
+                                           C.cast(values, C.c_void_p)), "msm_frmle_round")
+        return values.raw[:32 * (top + 1)] if fold is None else (values.raw[:32 * (top + 1)], buf.raw)
+
+    def sumcheck_prove(self, a, terms, batch, challenge):
+        """The prover's side of a sumcheck of sum_x sum_terms coeff prod_f row_f[x] over `batch` tables of N = 2^k scalars (a: a CUDA uint8 tensor of
+        batch x N x 32 bytes, DESTROYED: the rounds run in place), the counterpart of kzg_open: round j's values go to challenge(j, values) -- values:
+        (D + 1) x 32 bytes in the data's form --, which returns the verifier's challenge, an integer in [0, r); every round after the first binds
+        the previous challenge in the same pass (scalars_sumcheck_round with fold).  -> (the k rounds' values, the k challenges, every row's value
+        at that point as batch x 32 bytes)."""
+        r = self._frmle_field("sumcheck_prove")
+        if not (isinstance(a, torch.Tensor) and a.is_cuda):
+            raise TypeError("sumcheck_prove runs in place on a CUDA(HIP) uint8 tensor")
+        _, _, n, _ = self._frmle_rows(a, batch, None, 1)
+        rounds, point = [], []
+        while n >> len(point) > 1:
+            j = len(point)
+            values = self.scalars_sumcheck_round(a, terms, batch, n >> max(j - 1, 0), fold=point[-1] if j else None)
+            c = int(challenge(j, values))
+            if not 0 <= c < r:
+                raise ValueError("challenge %d is not in [0, r)" % j)
+            rounds.append(values)
+            point.append(c)
+        # the last challenge binds what is left of every row: two scalars, or -- N = 1 -- the row itself
+        finals = self.scalars_mle_eval(a, point[-1:], batch, 2 if point else 1)
+        return rounds, point, finals
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

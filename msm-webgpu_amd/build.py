@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so and libmsm_frpoly.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so and libmsm_frmle.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -27,6 +27,13 @@ FRPOLY_UNITS = ["frpoly_bn254.hip", "frpoly_pallas.hip", "frpoly_vesta.hip", "fr
 FRPOLY_SOURCES = FRPOLY_UNITS + ["frpoly_unit.h", "frpoly_kernels.h", "frpoly_host.h", "frpoly_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
                                  "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
 FRPOLY_HEADERS = [os.path.join(HERE, "..", "include", "msm_frpoly.h"), HEADER]
+# libmsm_frmle.so (include/msm_frmle.h): the sumcheck over multilinear tables -- fold, eval, eq, round --, the fifth library; the only one with a
+# unit for Grumpkin's scalar field (no transform needs it here)
+FRMLE_SO = os.path.join(HERE, "libmsm_frmle.so")
+FRMLE_UNITS = ["frmle_bn254.hip", "frmle_grumpkin.hip", "frmle_pallas.hip", "frmle_vesta.hip", "frmle_bls12_381.hip"]
+FRMLE_SOURCES = FRMLE_UNITS + ["frmle_unit.h", "frmle_kernels.h", "frmle_host.h", "frmle_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
+                               "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FRMLE_HEADERS = [os.path.join(HERE, "..", "include", "msm_frmle.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -157,6 +164,44 @@ def frpoly_device_asm_is_current():
     return all(os.path.getmtime(f) >= newest for f in frpoly_device_asm_paths())
 
 
+def frmle_device_asm_paths():
+    """The device assembly of libmsm_frmle.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRMLE_UNITS]
+
+
+def frmle_build_stamp():
+    """build_stamp() for libmsm_frmle.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FRMLE_SOURCES)] + FRMLE_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def frmle_needs_build():
+    """libmsm_frmle.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FRMLE_SO + ".stamp") as f:
+            return not os.path.exists(FRMLE_SO) or f.read().strip() != frmle_build_stamp()
+    except OSError:
+        return True
+
+
+def frmle_device_asm_is_current():
+    """device_asm_is_current() for libmsm_frmle.so's units"""
+    if frmle_needs_build() or not all(os.path.exists(f) for f in frmle_device_asm_paths()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRMLE_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in frmle_device_asm_paths())
+
+
 def build_stamp():
     """what the library on disk must have been built FROM to be the product: a hash over the compile flags (the environment switches of the
     diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source.  Written next to the
@@ -231,11 +276,13 @@ def compile_flags():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
-    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so and msm-webgpu_amd/libmsm_frpoly.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so, msm-webgpu_amd/libmsm_frpoly.so and
+    msm-webgpu_amd/libmsm_frmle.so.  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
     do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
     do_frpoly = (force and not os.environ.get("MSM_HIP_SO")) or frpoly_needs_build()
-    if not do_hip and not do_fr and not do_frvec and not do_frpoly:
+    do_frmle = (force and not os.environ.get("MSM_HIP_SO")) or frmle_needs_build()
+    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -263,8 +310,8 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of all four libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else [])
+    # one pool for the units of all five libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else [])
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
@@ -283,6 +330,10 @@ def build(force=False, verbose=False):
         link([objs[u] for u in FRPOLY_UNITS], FRPOLY_SO)
         with open(FRPOLY_SO + ".stamp", "w") as f:
             f.write(frpoly_build_stamp() + "\n")
+    if do_frmle:
+        link([objs[u] for u in FRMLE_UNITS], FRMLE_SO)
+        with open(FRMLE_SO + ".stamp", "w") as f:
+            f.write(frmle_build_stamp() + "\n")
     return SO
 
 

@@ -8,7 +8,8 @@ Run: python tools/gen_constants.py > msm-webgpu_amd/csrc/bn254_constants.h
      python tools/gen_constants.py pallas   > msm-webgpu_amd/csrc/pallas_constants.h      (likewise vesta, bls12_381)
      python tools/gen_constants.py bn254_g2 > msm-webgpu_amd/csrc/bn254_g2_constants.h   (a G2 unit's Fq2-level constants; likewise bls12_381_g2)
      python tools/gen_constants.py fr bn254 > msm-webgpu_amd/csrc/fr_bn254_constants.h   (field-only: a curve's SCALAR field for the NTT units of
-                                                                                          libmsm_fr.so; likewise pallas, vesta, bls12_381)
+                                                                                          libmsm_fr.so; likewise pallas, vesta, bls12_381 -- and
+                                                                                          grumpkin, for the sumcheck units of libmsm_frmle.so alone)
 (Grumpkin, BN254's cycle partner: base field = BN254's scalar field, scalar field = BN254's base field, y^2 = x^3 - 17; the two
 moduli agree in their top 128 bits, so 2^261 / modulus = 169 and every lazy bound of fq29.h / g1.h holds for both.
 Pallas / Vesta, the Pasta cycle: 255-bit moduli, 2^261 / modulus = 127 -- the largest operand product of the group formulas,
@@ -217,8 +218,9 @@ def emit_g2(which):
 
 def emit_field(name):
     """msm-webgpu_amd/csrc/fr_<name>_constants.h: a SCALAR field alone, as csrc/fq29.h reads a modulus (9 x 29-bit limbs, R = 2^261) -- what the
-    scalar-field NTT (csrc/ntt_kernels.h, libmsm_fr.so) is instantiated with.  No curve constants.  Grumpkin's r (2-adicity 1) is not offered."""
-    r = {"bn254": RMOD, "pallas": 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
+    scalar-field NTT (csrc/ntt_kernels.h, libmsm_fr.so) is instantiated with.  No curve constants.  Grumpkin's r (BN254's base-field prime,
+    2-adicity 1) has no transform: it is here for libmsm_frmle.so, whose sumcheck needs no root of unity."""
+    r = {"bn254": RMOD, "grumpkin": P, "pallas": 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
          "vesta": 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
          "bls12_381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001}[name]
     w, l, nw = 29, 9, 8
