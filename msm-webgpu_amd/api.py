@@ -365,6 +365,71 @@ def frmle_release():
     frmle_lib().msm_frmle_release()
 
 
+_frmat_lib = None
+
+
+def frmat_lib():
+    """Load libmsm_frmat.so (in-tree; include/msm_frmat.h): sparse matrix-vector products over the scalar field.  Raises if it has not been built
+    (msm-webgpu_amd/build.py builds it beside the other five)."""
+    global _frmat_lib
+    if _frmat_lib is None:
+        so = _build.FRMAT_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frmat.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        i, sz, vp, u32 = C.c_int, C.c_size_t, C.c_void_p, C.c_uint32
+        L.msm_frmat_abi_version.restype = i
+        L.msm_frmat_create.argtypes = [i, i, sz, sz, sz, vp, vp, vp, u32, C.POINTER(vp)]
+        L.msm_frmat_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
+        L.msm_frmat_destroy.argtypes = [vp]
+        L.msm_frmat_destroy.restype = None
+        L.msm_frmat_mul_device.argtypes = [vp, vp, vp, sz, vp, sz, u32]
+        L.msm_frmat_mul.argtypes = [vp, vp, sz, vp, sz, u32]
+        L.msm_frmat_release.argtypes = []
+        L.msm_frmat_release.restype = None
+        L.msm_frmat_test_tile.argtypes = [i]
+        L.msm_frmat_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
+        _frmat_lib = L
+    return _frmat_lib
+
+
+def frmat_test_tile(entries=0):
+    """test hook msm_frmat_test_tile: the matrices created from now on use tiles of `entries` entries (0: the design's 1024)"""
+    _check(frmat_lib().msm_frmat_test_tile(int(entries)), "msm_frmat_test_tile")
+
+
+def frmat_last():
+    """(kernel launches, levels) of the last sparse product of this process (test hook msm_frmat_test_last)"""
+    v = [C.c_int(), C.c_int()]
+    _check(frmat_lib().msm_frmat_test_last(*[C.byref(x) for x in v]), "msm_frmat_test_last")
+    return tuple(x.value for x in v)
+
+
+def frmat_release():
+    """msm_frmat_release: free the sparse-product library's staging buffers (they come back with the next call); the matrices stay"""
+    frmat_lib().msm_frmat_release()
+
+
+class FrMatrix:
+    """A sparse matrix over a scalar field, resident on one device (msm_frmat_create, include/msm_frmat.h): MsmContext.scalars_matrix makes it,
+    MsmContext.scalars_matvec multiplies by it.  close() frees it; so does collecting it."""
+
+    def __init__(self, handle, curve, device, rows, cols, nnz, has_transpose):
+        self._h, self.curve, self.device = handle, curve, device
+        self.rows, self.cols, self.nnz, self.has_transpose = rows, cols, nnz, has_transpose
+
+    def close(self):
+        if self._h:
+            frmat_lib().msm_frmat_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _check(code, where):
     if code != 0:
         raise MsmHipError(code, where)
@@ -1257,6 +1322,122 @@ class MsmContext:
         # the last challenge binds what is left of every row: two scalars, or -- N = 1 -- the row itself
         finals = self.scalars_mle_eval(a, point[-1:], batch, 2 if point else 1)
         return rounds, point, finals
+
+    # -- sparse matrix-vector products over the scalar field (libmsm_frmat.so): the rows Az, Bz, Cz of an R1CS, between the commitment to the
+    # witness (msm) and the sumcheck (sumcheck_prove)
+    FRMAT_MONT256, FRMAT_WITH_TRANSPOSE, FRMAT_TRANSPOSE = 2, 4, 8  # MSM_FRMAT_MONT256, ..
+    FRMAT_MAX_DIM, FRMAT_MAX_NNZ = 1 << 26, 1 << 28
+
+    @staticmethod
+    def _frmat_indices(v, name, bound):
+        """any integer sequence, numpy array or CPU tensor -> a contiguous uint32 array; a negative or too large index raises"""
+        if isinstance(v, torch.Tensor):
+            if v.is_cuda:
+                raise TypeError("%s comes from host memory" % name)
+            v = v.numpy()
+        a = np.asarray(v)
+        if a.size == 0:
+            return np.zeros(0, dtype=np.uint32)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError("%s must be a flat sequence of integers" % name)
+        if int(a.min()) < 0 or int(a.max()) > bound:
+            raise ValueError("%s holds an index outside [0, %d]" % (name, bound))
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
+    def scalars_matrix(self, rows, cols, row_ptr, col_idx, values, transpose=False):
+        """A rows x cols sparse matrix over this context's scalar field in CSR form -> FrMatrix (msm_frmat_create, include/msm_frmat.h), checked
+        here on the host and resident on this context's device from its first product on.  row_ptr: rows + 1 integers from 0 to nnz, never
+        decreasing; col_idx: nnz columns below cols, in any order within a row, repeats adding up; values: nnz integers in [0, r) or nnz x 32
+        canonical little-endian bytes -- always plain integers, whatever the context's scalar format.  Indices: any integer sequence, a numpy array
+        or a CPU tensor.  transpose=True also keeps the transposed structure, for scalars_matvec(..., transpose=True).  Every curve's scalar
+        field, Grumpkin's included; a G2 context takes its G1's."""
+        r = self._frmle_field("scalars_matrix")
+        rows, cols = int(rows), int(cols)
+        if not (1 <= rows <= self.FRMAT_MAX_DIM and 1 <= cols <= self.FRMAT_MAX_DIM):
+            raise ValueError("a matrix has 1 .. 2^26 rows and columns, not %d x %d" % (rows, cols))
+        ptr = self._frmat_indices(row_ptr, "row_ptr", self.FRMAT_MAX_NNZ)
+        idx = self._frmat_indices(col_idx, "col_idx", cols - 1)
+        nnz = int(idx.size)
+        if ptr.size != rows + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != nnz or (rows and bool((ptr[1:] < ptr[:-1]).any())):
+            raise ValueError("row_ptr must hold rows + 1 integers from 0 to nnz = %d that never decrease" % nnz)
+        if isinstance(values, (bytes, bytearray)):
+            vb = bytes(values)
+        elif isinstance(values, np.ndarray) and values.dtype == np.uint8:
+            vb = values.tobytes()
+        else:
+            values = [int(v) for v in values]
+            if any(not 0 <= v < r for v in values):
+                raise ValueError("the values must lie in [0, r)")
+            vb = b"".join(v.to_bytes(32, "little") for v in values)
+        if len(vb) != 32 * nnz:
+            raise ValueError("%d values for %d columns" % (len(vb) // 32, nnz))
+        h = C.c_void_p()
+        _check(frmat_lib().msm_frmat_create(self.curve_id, self.device, rows, cols, nnz, ptr.ctypes.data, idx.ctypes.data if nnz else None,
+                                            C.cast(C.c_char_p(vb), C.c_void_p) if nnz else None, self.FRMAT_WITH_TRANSPOSE if transpose else 0, C.byref(h)), "msm_frmat_create")
+        return FrMatrix(h, self.curve, self.device, rows, cols, nnz, bool(transpose))
+
+    def scalars_matvec(self, mat, x, out=None, transpose=False, pad_to=None):
+        """y = M x -- transpose=True: M^T x, for a matrix made with transpose=True -- over the scalar field (msm_frmat_mul_device): y[i] = sum_j
+        M[i][j] x[j].  x: a CUDA uint8 tensor of cols x 32 bytes (rows x 32 with transpose) in this context's 32-byte scalar format, or host bytes
+        (bytes come back).  -> a CUDA uint8 tensor of pad_to x 32 bytes, or `out` (contiguous, that size; a row of a larger buffer will do):
+        pad_to defaults to the exact length, and y[length .. pad_to) is zero whatever out held.  An element of x that is not below r raises
+        MsmHipError (code -4) where an entry of the matrix references it; a column nobody references is not read."""
+        self._frmle_field("scalars_matvec")
+        if not isinstance(mat, FrMatrix) or not mat._h:
+            raise TypeError("mat must be an open FrMatrix (scalars_matrix)")
+        if mat.curve != self.curve or mat.device != self.device:
+            raise ValueError("the matrix belongs to %s on device %d" % (mat.curve, mat.device))
+        if transpose and not mat.has_transpose:
+            raise ValueError("the matrix was made without transpose=True")
+        in_len, out_len = (mat.rows, mat.cols) if transpose else (mat.cols, mat.rows)
+        tx, bx, n = self._frvec_vector(x, "x")
+        if n != in_len:
+            raise ValueError("x holds %d scalars, the matrix takes %d" % (n, in_len))
+        y_len = out_len if pad_to is None else int(pad_to)
+        if not out_len <= y_len <= self.FRMAT_MAX_DIM:
+            raise ValueError("pad_to must lie in [%d, 2^26], not %d" % (out_len, y_len))
+        flags = (self.FRMAT_MONT256 if getattr(self, "scalar_mont256", False) else 0) | (self.FRMAT_TRANSPOSE if transpose else 0)
+        if tx is None:
+            if out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            buf = C.create_string_buffer(32 * y_len)
+            _check(frmat_lib().msm_frmat_mul(mat._h, C.cast(buf, C.c_void_p), y_len, C.cast(C.c_char_p(bx), C.c_void_p), n, flags), "msm_frmat_mul")
+            return buf.raw
+        if out is None:
+            out = torch.empty((y_len, 32), dtype=torch.uint8, device=tx.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * y_len or not out.is_contiguous() or out.device != tx.device:
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes on %s" % (y_len, tx.device))
+        self._order_after_torch(tx)
+        _check(frmat_lib().msm_frmat_mul_device(mat._h, lib().msm_hip_stream(self._h), out.data_ptr(), y_len, tx.data_ptr(), n, flags), "msm_frmat_mul_device")
+        return out
+
+    def r1cs_tables(self, a, b, c, z, n=None, out=None, first_row=0):
+        """The tables Az, Bz, Cz of an R1CS as the rows first_row .. first_row + 2 of a batch x N x 32 byte CUDA buffer: three scalars_matvec calls
+        over one z (a CUDA uint8 tensor of cols x 32 bytes).  N = n, or the next power of two >= the matrices' rows; the tail of every row is zero.
+        out: None -- a new buffer of (first_row + 3) x N, whose other rows are NOT initialised -- or a contiguous buffer of batch x N x 32 bytes,
+        whose other rows are left as they are: with scalars_eq(point, out=out[0]) and first_row=1 it is one sumcheck_prove input for eq A B - eq C."""
+        mats = (a, b, c)
+        if any(not isinstance(m, FrMatrix) for m in mats) or len({(m.rows, m.cols) for m in mats}) != 1:
+            raise ValueError("a, b, c must be three FrMatrix of one shape")
+        first_row = int(first_row)
+        if n is None:
+            n = 1
+            while n < a.rows:
+                n *= 2
+        n = int(n)
+        if n < a.rows or n & (n - 1) or first_row < 0:
+            raise ValueError("n must be a power of two >= %d rows, first_row >= 0" % a.rows)
+        if out is None:
+            if not (isinstance(z, torch.Tensor) and z.is_cuda):
+                raise TypeError("z must be a CUDA(HIP) uint8 tensor")
+            out = torch.empty((first_row + 3, n, 32), dtype=torch.uint8, device=z.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() % (32 * n) or \
+                out.numel() < 32 * n * (first_row + 3):
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of batch x %d x 32 bytes with batch >= %d" % (n, first_row + 3))
+        table = out.view(-1, n, 32)
+        for k, m in enumerate(mats):
+            self.scalars_matvec(m, z, out=table[first_row + k], pad_to=n)
+        return out
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under
