@@ -410,6 +410,38 @@ def frmat_release():
     frmat_lib().msm_frmat_release()
 
 
+_frgate_lib = None
+
+
+class FrgateTerm(C.Structure):
+    """msm_frgate_term (include/msm_frgate.h): coeff * prod_{f < degree} row[rows[f]] at the rotation rots[f]"""
+    _fields_ = [("coeff", C.c_uint8 * 32), ("degree", C.c_uint32), ("rows", C.c_uint32 * 8), ("rots", C.c_int32 * 8)]
+
+
+def frgate_lib():
+    """Load libmsm_frgate.so (in-tree; include/msm_frgate.h): constraint evaluation over rotated rows of the scalar field.  Raises if it has not been
+    built (msm-webgpu_amd/build.py builds it beside the other six)."""
+    global _frgate_lib
+    if _frgate_lib is None:
+        so = _build.FRGATE_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frgate.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, sz, i, u32, tp = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrgateTerm)
+        L.msm_frgate_abi_version.restype = i
+        L.msm_frgate_apply_device.argtypes = [i, i, vp, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32]
+        L.msm_frgate_apply.argtypes = [i, i, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32]
+        L.msm_frgate_release.argtypes = []
+        L.msm_frgate_release.restype = None
+        _frgate_lib = L
+    return _frgate_lib
+
+
+def frgate_release():
+    """msm_frgate_release: free the constraint-evaluation library's constants and staging buffers (they come back with the next call)"""
+    frgate_lib().msm_frgate_release()
+
+
 class FrMatrix:
     """A sparse matrix over a scalar field, resident on one device (msm_frmat_create, include/msm_frmat.h): MsmContext.scalars_matrix makes it,
     MsmContext.scalars_matvec multiplies by it.  close() frees it; so does collecting it."""
@@ -1438,6 +1470,139 @@ class MsmContext:
         for k, m in enumerate(mats):
             self.scalars_matvec(m, z, out=table[first_row + k], pad_to=n)
         return out
+
+    # -- constraint evaluation over the scalar field (libmsm_frgate.so): sums of products of rotated rows, the numerator of a PLONK / halo2-style
+    # quotient over the extended coset domain, between two scalars_fft
+    FRGATE_MONT256, FRGATE_ACCUMULATE = 2, 4  # MSM_FRGATE_MONT256, MSM_FRGATE_ACCUMULATE
+    FRGATE_MAX_DEGREE, FRGATE_MAX_TERMS, FRGATE_MAX_ROWS = 8, 64, 32  # MSM_FRGATE_MAX_DEGREE, ..
+
+    def _frgate_terms(self, terms, batch, r):
+        """[(coeff, (factor, ..)), ..], a factor a row number or (row, rotation) -> (array of msm_frgate_term, the largest degree)"""
+        terms = list(terms)
+        if not 1 <= len(terms) <= self.FRGATE_MAX_TERMS:
+            raise ValueError("a gate takes 1 .. %d terms, not %d" % (self.FRGATE_MAX_TERMS, len(terms)))
+        arr = (FrgateTerm * len(terms))()
+        top = 0
+        for t, (coeff, factors) in zip(arr, terms):
+            factors = [(int(f), 0) if isinstance(f, (int, np.integer)) else (int(f[0]), int(f[1])) for f in factors]
+            if not 1 <= len(factors) <= self.FRGATE_MAX_DEGREE:
+                raise ValueError("a term has 1 .. %d factors, not %d" % (self.FRGATE_MAX_DEGREE, len(factors)))
+            if any(not 0 <= row < batch for row, _ in factors):
+                raise ValueError("a term names a row outside the %d rows" % batch)
+            if any(not -2 ** 31 <= rot < 2 ** 31 for _, rot in factors):
+                raise ValueError("a rotation is a signed 32-bit integer")
+            t.coeff[:] = self._frpoly_const(coeff, r, "a coefficient")
+            t.degree = len(factors)
+            t.rows[:len(factors)] = [row for row, _ in factors]
+            t.rots[:len(factors)] = [rot for _, rot in factors]
+            top = max(top, len(factors))
+        return arr, top
+
+    def scalars_gate(self, a, terms, batch=1, n=None, step=1, scale=None, out=None, accumulate=False):
+        """out[i] = (out[i] if accumulate else 0) + scale[i mod len(scale)] * sum_terms coeff prod_f row_f[(i + rotation_f * step) mod n], i < n
+        (msm_frgate_apply_device, include/msm_frgate.h): a constraint system evaluated element by element in one pass.  terms: 1 .. 64 pairs
+        (coeff, factors) of a plain integer coefficient and 1 .. 8 factors, each a row number or (row, rotation) -- a rotation of any sign and
+        size, in units of `step` elements, wrapping round the n elements.  a, batch, n: as scalars_mle_fold (batch <= 32 rows, n a power of two);
+        a CUDA tensor runs on this context's stream, behind torch's; host bytes return bytes.  scale: None, or a vector like a of a power of two
+        <= n of scalars.  out: a contiguous CUDA uint8 tensor of n x 32 bytes that overlaps neither a nor scale (a new one by default; with host
+        bytes and accumulate, the n x 32 bytes to add onto).  The vectors are in this context's 32-byte scalar format and must be below r
+        where they are read: the rows a term names, scale, and out with accumulate."""
+        r = self._frmle_field("scalars_gate")
+        ta, ba, n, stride = self._frmle_rows(a, batch, n, 1)
+        batch, step = int(batch), int(step)
+        if batch > self.FRGATE_MAX_ROWS:
+            raise ValueError("a gate takes at most %d rows, not %d" % (self.FRGATE_MAX_ROWS, batch))
+        if not 1 <= step <= n:
+            raise ValueError("step must lie in [1, n = %d], not %d" % (n, step))
+        arr, _ = self._frgate_terms(terms, batch, r)
+        on_device = ta is not None
+        ts = bs = None
+        scale_len = 0
+        if scale is not None:
+            ts, bs, scale_len = self._frvec_vector(scale, "scale")
+            if (ts is not None) != on_device:
+                raise TypeError("scale must be on the device exactly when a is")
+            if scale_len < 1 or scale_len > n or scale_len & (scale_len - 1):
+                raise ValueError("scale holds a power of two of scalars, at most n = %d, not %d" % (n, scale_len))
+        flags = (self.FRGATE_MONT256 if getattr(self, "scalar_mont256", False) else 0) | (self.FRGATE_ACCUMULATE if accumulate else 0)
+        if not on_device:
+            if accumulate:
+                ob = bytes(out) if out is not None else b""
+                if len(ob) != 32 * n:
+                    raise ValueError("with host bytes, accumulate adds onto out: %d x 32 bytes" % n)
+                buf = C.create_string_buffer(ob, len(ob))
+            elif out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            else:
+                buf = C.create_string_buffer(32 * n)
+            _check(frgate_lib().msm_frgate_apply(self.curve_id, self.device, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), n, batch, stride, arr, len(arr),
+                                                 step, C.cast(C.c_char_p(bs), C.c_void_p) if bs is not None else None, scale_len, flags), "msm_frgate_apply")
+            return buf.raw
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate adds onto out")
+            out = torch.empty((n, 32), dtype=torch.uint8, device=ta.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * n or not out.is_contiguous() or out.device != ta.device:
+            raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes on %s" % (n, ta.device))
+        if ts is not None and ts.device != ta.device:
+            raise ValueError("scale must be on %s" % (ta.device,))
+        lo, hi = out.data_ptr(), out.data_ptr() + 32 * n
+        for t, size in ((ta, 32 * batch * stride), (ts, 32 * scale_len)):
+            if t is not None and lo < t.data_ptr() + size and t.data_ptr() < hi:
+                raise ValueError("out overlaps an input: a lane reads what its neighbours write to, the call is never in place")
+        self._order_after_torch(ta)
+        _check(frgate_lib().msm_frgate_apply_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), out.data_ptr(), ta.data_ptr(), n, batch, stride, arr, len(arr),
+                                                    step, ts.data_ptr() if ts is not None else None, scale_len, flags), "msm_frgate_apply_device")
+        return out
+
+    def vanishing_inverse(self, log_n, log_ext, shift):
+        """The 2^log_ext values 1 / (shift^n w^(n i) - 1), i < 2^log_ext, w = root_of_unity(curve, log_n + log_ext), n = 2^log_n, as a CUDA uint8 tensor
+        of 2^log_ext x 32 bytes in this context's scalar format: 1 / Z_H on the coset shift <w>, which has period 2^log_ext -- the `scale` of
+        scalars_gate on the extended domain.  Computed with Python integers on the host.  Raises ValueError where shift^n = 1 (the coset meets H)."""
+        r = self._frvec_field("vanishing_inverse")
+        log_n, log_ext = int(log_n), int(log_ext)
+        if log_n < 0 or log_ext < 0:
+            raise ValueError("log_n and log_ext are not negative")
+        w = root_of_unity(self.curve, log_n + log_ext)
+        g = pow((int.from_bytes(shift, "little") if isinstance(shift, (bytes, bytearray)) else int(shift)) % r, 1 << log_n, r)
+        wn = pow(w, 1 << log_n, r)  # a primitive 2^log_ext-th root
+        vals, x = [], g
+        for _ in range(1 << log_ext):
+            if x in (0, 1):
+                raise ValueError("Z_H vanishes on the coset: shift^n = %d" % x)
+            vals.append(pow(x - 1, r - 2, r))
+            x = x * wn % r
+        if getattr(self, "scalar_mont256", False):
+            vals = [v * pow(2, 256, r) % r for v in vals]
+        host = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(-1, 32).copy()
+        return torch.from_numpy(host).to("cuda:%d" % self.device)
+
+    def quotient(self, coeffs, terms, batch, log_n, log_ext, shift):
+        """The N = n 2^log_ext coefficients of t(X) = E(X) / Z_H(X), n = 2^log_n, as a CUDA uint8 tensor of N x 32 bytes:
+        E(X) = sum_terms coeff prod_f column_f(omega^rotation_f X), omega = root_of_unity(curve, log_n) -- a rotation by +1 is the next row of H.
+        coeffs: a CUDA uint8 tensor of batch x n x 32 bytes, the columns in coefficient form, left untouched.  Nothing leaves the device: a
+        zero-padded copy of batch x N, scalars_fft onto the coset shift <root_of_unity(curve, log_n + log_ext)>, scalars_gate with step = 2^log_ext
+        and scale = vanishing_inverse, scalars_fft back.  Needs 2^log_ext >= D - 1, D the largest degree among the terms: E / Z_H then has fewer
+        than N coefficients, and where the constraints hold on H those from (D - 1) n upward are zero."""
+        r = self._frvec_field("quotient")
+        if not (isinstance(coeffs, torch.Tensor) and coeffs.is_cuda):
+            raise TypeError("quotient takes a CUDA(HIP) uint8 tensor")
+        batch, log_n, log_ext = int(batch), int(log_n), int(log_ext)
+        t, total = _as_device_u8(coeffs, 32, "coeffs")
+        if log_n < 0 or log_ext < 0 or batch < 1 or total != batch << log_n:
+            raise ValueError("%d scalars are not %d columns of 2^%d" % (total, batch, log_n))
+        if batch > self.FRGATE_MAX_ROWS or (batch << (log_n + log_ext)) > self.FRVEC_MAX_ELEMENTS:
+            raise ValueError("the extended columns are at most %d rows and 2^26 scalars" % self.FRGATE_MAX_ROWS)
+        _, top = self._frgate_terms(terms, batch, r)
+        if (1 << log_ext) < top - 1:
+            raise ValueError("terms of degree %d need log_ext with 2^log_ext >= %d" % (top, top - 1))
+        n, big = 1 << log_n, 1 << (log_n + log_ext)
+        scale = self.vanishing_inverse(log_n, log_ext, shift)
+        ext = torch.zeros((batch, big, 32), dtype=torch.uint8, device=t.device)
+        ext[:, :n] = t.view(batch, n, 32)
+        self.scalars_fft(ext, log_n + log_ext, shift=shift, batch=batch)
+        out = self.scalars_gate(ext, terms, batch=batch, step=1 << log_ext, scale=scale)
+        return self.scalars_fft(out, log_n + log_ext, inverse=True, shift=shift)
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

@@ -1,0 +1,86 @@
+"""The code-generation gates (tools/check_long_branch_hazard.py, tools/check_machine_verifier.py) over the five units of libmsm_frgate.so, which
+are not among the other six libraries' units; every unit's kernel sits in the unit's own namespace, it uses no scratch memory and spills nothing,
+its LDS is what DESIGN.md section 4.22 states (none), and the library on disk is the current sources'.  Resource metadata only."""
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import check_long_branch_hazard as chk  # noqa: E402
+
+KERNELS = ("k_frgate_apply",)
+
+
+def _units():
+    import importlib
+
+    return list(importlib.import_module("msm_webgpu_amd.build").FRGATE_UNITS)
+
+
+def test_frgate_units_have_no_long_branch_hazard(built):
+    paths = chk.compile_to_asm([], units=_units())
+    assert len(paths) == 5 and all("frgate_" in os.path.basename(p) for p in paths)
+    for path in paths:
+        long_branches, found, live = chk.check_file(path)
+        assert found == [] and live == [], (path, found, live)
+
+
+def test_frgate_units_pass_the_machine_verifier():
+    import check_machine_verifier as mv
+
+    reports = mv.check(units=_units())
+    assert sorted(reports) == sorted(_units())
+    for unit, found in reports.items():
+        assert found == [], (unit, found)
+
+
+def test_each_unit_holds_its_kernel_in_its_own_namespace_without_scratch(built):
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    section = design[design.index("### 4.22"):]
+    section = section[:section.index("\n## ")]
+    assert "LDS 0 B" in section  # (the LDS size asserted below is the one the document states)
+    for path in chk.compile_to_asm([], units=_units()):
+        with open(path) as f:
+            text = f.read()
+        names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
+        field = "frg_" + os.path.basename(path).split("-hip-")[0][len("frgate_"):]
+        assert len(names) == len(KERNELS), (path, names)
+        for k in KERNELS:
+            mine = [n for n in names if ("%d%s" % (len(field), field)) in n and ("%d%s" % (len(k), k)) in n]
+            assert len(mine) == 1, (path, k, names)
+        # the kernel descriptor and the metadata: no private segment, nothing spilled, no dynamic stack
+        assert re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.vgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS) and re.findall(r"\.sgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert not re.search(r"\.uses_dynamic_stack:\s+true", text), path
+        assert [int(v) for v in re.findall(r"\.amdhsa_group_segment_fixed_size\s+(\d+)", text)] == [0], path
+        # the registers DESIGN.md section 4.22 states: no more vector registers than the sibling libraries' kernels
+        assert all(int(v) <= 168 for v in re.findall(r"\.vgpr_count:\s+(\d+)", text)), path
+
+
+def test_library_on_disk_was_built_from_the_current_sources(built):
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert os.path.exists(b.FRGATE_SO) and not b.frgate_needs_build()
+    assert b.frgate_device_asm_is_current()
+    for needs in (b.fr_needs_build, b.frvec_needs_build, b.frpoly_needs_build, b.frmle_needs_build, b.frmat_needs_build):  # the other stamps stay current
+        assert not needs()
+
+
+def test_the_other_libraries_do_not_depend_on_this_one():
+    """libmsm_frgate.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert sorted(b.FRGATE_UNITS) == ["frgate_bls12_381.hip", "frgate_bn254.hip", "frgate_grumpkin.hip", "frgate_pallas.hip", "frgate_vesta.hip"]
+    for other in (b.TRANSLATION_UNITS, b.FR_UNITS, b.FRVEC_UNITS, b.FRPOLY_UNITS, b.FRMLE_UNITS, b.FRMAT_UNITS):
+        assert not set(other) & set(b.FRGATE_UNITS)
+    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES + b.FRMAT_SOURCES
+    assert not any(f.startswith("frgate_") for f in others)
+    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_", "frmat_")) for f in b.FRGATE_SOURCES)  # (no kernel of the other six)
+    for u in b.FRGATE_SOURCES:
+        assert os.path.exists(os.path.join(b.CSRC, u)), u
