@@ -442,6 +442,75 @@ def frgate_release():
     frgate_lib().msm_frgate_release()
 
 
+_frlook_lib = None
+
+
+def frlook_lib():
+    """Load libmsm_frlook.so (in-tree; include/msm_frlook.h): lookup arguments over the scalar field -- multiplicities and table indices.  Raises
+    if it has not been built (msm-webgpu_amd/build.py builds it beside the other seven)."""
+    global _frlook_lib
+    if _frlook_lib is None:
+        so = _build.FRLOOK_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frlook.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, sz, i, u32, u64p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)
+        L.msm_frlook_abi_version.restype = i
+        L.msm_frlook_create_device.argtypes = [i, i, vp, vp, sz, u32, C.POINTER(vp)]
+        L.msm_frlook_create.argtypes = [i, i, vp, sz, u32, C.POINTER(vp)]
+        L.msm_frlook_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
+        L.msm_frlook_destroy.argtypes = [vp]
+        L.msm_frlook_destroy.restype = None
+        L.msm_frlook_count_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p]
+        L.msm_frlook_count.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p]
+        L.msm_frlook_release.argtypes = []
+        L.msm_frlook_release.restype = None
+        L.msm_frlook_test_hash_bits.argtypes = [i]
+        _frlook_lib = L
+    return _frlook_lib
+
+
+lib_frlook = frlook_lib
+
+
+def frlook_test_hash_bits(bits=0):
+    """test hook msm_frlook_test_hash_bits: the tables created from now on keep only the low `bits` of the hash (0: the design's 32)"""
+    _check(frlook_lib().msm_frlook_test_hash_bits(int(bits)), "msm_frlook_test_hash_bits")
+
+
+def frlook_release():
+    """msm_frlook_release: free the lookup library's staging buffers (they come back with the next call); the tables stay"""
+    frlook_lib().msm_frlook_release()
+
+
+class FrLookup:
+    """A lookup table over a scalar field, resident on one device (msm_frlook_create_device, include/msm_frlook.h): MsmContext.lookup_table makes
+    it, MsmContext.scalars_multiplicities and MsmContext.logup count into it.  n: its entries; distinct: how many different values they hold;
+    mont256: the form its keys were stored in.  close() frees it; so does collecting it or leaving a `with` block."""
+
+    def __init__(self, handle, curve, device, n, distinct, mont256):
+        self._h, self.curve, self.device = handle, curve, device
+        self.n, self.distinct, self.mont256 = n, distinct, mont256
+
+    def close(self):
+        if self._h:
+            frlook_lib().msm_frlook_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FrMatrix:
     """A sparse matrix over a scalar field, resident on one device (msm_frmat_create, include/msm_frmat.h): MsmContext.scalars_matrix makes it,
     MsmContext.scalars_matvec multiplies by it.  close() frees it; so does collecting it."""
@@ -1603,6 +1672,203 @@ class MsmContext:
         self.scalars_fft(ext, log_n + log_ext, shift=shift, batch=batch)
         out = self.scalars_gate(ext, terms, batch=batch, step=1 << log_ext, scale=scale)
         return self.scalars_fft(out, log_n + log_ext, inverse=True, shift=shift)
+
+    # -- lookup arguments over the scalar field (libmsm_frlook.so): the multiplicity column of a logUp / plookup-style lookup and the table index
+    # of every looked-up value, between the quotient and the commitments
+    FRLOOK_MONT256, FRLOOK_MISSING = 2, 0xFFFFFFFF  # MSM_FRLOOK_MONT256, MSM_FRLOOK_MISSING
+    FRLOOK_MAX_TABLE, FRLOOK_MAX_ELEMENTS = 1 << 24, 1 << 26  # MSM_FRLOOK_MAX_TABLE, MSM_FRLOOK_MAX_ELEMENTS
+
+    def lookup_table(self, t, n=None):
+        """A lookup table over this context's scalar field -> FrLookup (msm_frlook_create_device, include/msm_frlook.h).  t: a CUDA uint8 tensor of
+        32-byte scalars in this context's scalar format (canonical, or mont256) -- e.g. the columns of a table folded with a challenge by
+        scalars_combine --, of which the first n (default: all, at most 2^24) are the table; host bytes are taken too and go to the device with the
+        first count.  The handle keeps a copy of its own: t is free afterwards.  A value may repeat: every match is credited to its lowest
+        index.  A value that is not below r raises MsmHipError (code -4).  Every curve's scalar field, Grumpkin's included."""
+        self._frmle_field("lookup_table")
+        tt, bt, total = self._frvec_vector(t, "t")
+        n = total if n is None else int(n)
+        if not 1 <= n <= min(total, self.FRLOOK_MAX_TABLE):
+            raise ValueError("a table holds 1 .. 2^24 scalars, at most the %d given, not %d" % (total, n))
+        mont = bool(getattr(self, "scalar_mont256", False))
+        flags = self.FRLOOK_MONT256 if mont else 0
+        h = C.c_void_p()
+        if tt is not None:
+            self._order_after_torch(tt)
+            _check(frlook_lib().msm_frlook_create_device(self.curve_id, self.device, lib().msm_hip_stream(self._h), tt.data_ptr(), n, flags, C.byref(h)),
+                   "msm_frlook_create_device")
+        else:
+            _check(frlook_lib().msm_frlook_create(self.curve_id, self.device, C.cast(C.c_char_p(bt), C.c_void_p), n, flags, C.byref(h)), "msm_frlook_create")
+        distinct = C.c_size_t()
+        _check(frlook_lib().msm_frlook_info(h, None, C.byref(distinct), None), "msm_frlook_info")
+        return FrLookup(h, self.curve, self.device, n, distinct.value, mont)
+
+    def scalars_multiplicities(self, table, f, batch=1, n=None, out=None, indices=False, counts=False, strict=True):
+        """m[j] = the number of elements of f equal to the table's value j (msm_frlook_count_device): the multiplicity column of a logUp, as
+        table.n scalars in this context's scalar format (under mont256 the count k is k * 2^256 mod r).  table: an FrLookup of this context's
+        curve, device and scalar format.  f: a CUDA uint8 tensor of batch rows, of which the first n scalars (default: the whole row; any n >= 1)
+        are looked up, or host bytes of the same layout.  A table value that repeats gets all its matches at its lowest index and 0 at the others.
+        -> m (a CUDA uint8 tensor of table.n x 32 bytes, or `out`; bytes for host bytes), or a tuple of m and what was asked for, in this
+        order: indices=True, the table index of every element as a CUDA int32 tensor of batch x n, -1 where the value is not in the table (numpy
+        uint32 with 0xFFFFFFFF for host bytes); counts=True, the counts as a CUDA tensor of table.n 32-bit words (torch.uint32; numpy uint32 for
+        host bytes); strict=False, the pair (missing, first_missing): how many elements are not in the table and the lowest flat index
+        row * n + i among them (None: none).  strict=True raises ValueError naming both instead.  m counts the elements that were found.  An
+        element that is not below r raises MsmHipError (code -4)."""
+        self._frmle_field("scalars_multiplicities")
+        if not isinstance(table, FrLookup) or not table._h:
+            raise TypeError("table must be an open FrLookup (lookup_table)")
+        mont = bool(getattr(self, "scalar_mont256", False))
+        if table.curve != self.curve or table.device != self.device or table.mont256 != mont:
+            raise ValueError("the table belongs to %s on device %d with mont256=%s" % (table.curve, table.device, table.mont256))
+        batch = int(batch)
+        tf, bf, total = self._frvec_vector(f, "f")
+        if batch < 1 or total < 1 or total % batch or total > self.FRLOOK_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not %d rows of 1 .. 2^26 / batch scalars" % (total, batch))
+        stride = total // batch
+        n = stride if n is None else int(n)
+        if not 1 <= n <= stride:
+            raise ValueError("n must lie in [1, %d], the length of a row, not %d" % (stride, n))
+        flags = self.FRLOOK_MONT256 if mont else 0
+        miss, first = C.c_uint64(), C.c_uint64()
+        if tf is None:
+            if out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            buf = C.create_string_buffer(32 * table.n)
+            idx = np.empty(batch * n, dtype=np.uint32) if indices else None
+            cnt = np.empty(table.n, dtype=np.uint32) if counts else None
+            _check(frlook_lib().msm_frlook_count(table._h, C.cast(buf, C.c_void_p), cnt.ctypes.data if counts else None, idx.ctypes.data if indices else None,
+                                                 C.cast(C.c_char_p(bf), C.c_void_p), n, batch, stride, flags, C.byref(miss), C.byref(first)), "msm_frlook_count")
+            m = buf.raw
+            if indices:
+                idx = idx.reshape(batch, n)
+        else:
+            if out is None:
+                m = torch.empty((table.n, 32), dtype=torch.uint8, device=tf.device)
+            elif not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or out.numel() != 32 * table.n or not out.is_contiguous() or out.device != tf.device:
+                raise ValueError("out must be a contiguous CUDA(HIP) uint8 tensor of %d x 32 bytes on %s" % (table.n, tf.device))
+            else:
+                m = out
+            idx = torch.empty((batch, n), dtype=torch.int32, device=tf.device) if indices else None
+            cnt = torch.empty(table.n, dtype=torch.uint32, device=tf.device) if counts else None
+            self._order_after_torch(tf)
+            _check(frlook_lib().msm_frlook_count_device(table._h, lib().msm_hip_stream(self._h), m.data_ptr(), cnt.data_ptr() if counts else None,
+                                                        idx.data_ptr() if indices else None, tf.data_ptr(), n, batch, stride, flags, C.byref(miss), C.byref(first)),
+                   "msm_frlook_count_device")
+        if strict and miss.value:
+            raise ValueError("%d looked-up values are not in the table; the first is element %d (row %d, position %d)" % (miss.value, first.value, first.value // n,
+                                                                                                                        first.value % n))
+        res = (m,) + ((idx,) if indices else ()) + ((cnt,) if counts else ())
+        if not strict:
+            res += ((miss.value, first.value if miss.value else None),)
+        return res[0] if len(res) == 1 else res
+
+    def logup(self, table_values, f, beta, batch=1, n=None, lookup=None):
+        """The columns of a logUp argument, prepared on the device: with m = scalars_multiplicities(lookup_table(table_values), f),
+        h_f[i] = sum_rows 1 / (beta + f[row][i]), i < n, and h_t[j] = m[j] / (beta + t[j]) -> (m, h_f, h_t, sum h_f, sum h_t).  The lookup holds
+        exactly when every value is in the table -- ValueError otherwise, as scalars_multiplicities(strict=True) -- and the two sums agree.
+        table_values: a CUDA uint8 tensor of 32-byte scalars in this context's scalar format; f, batch, n: as scalars_multiplicities, on the
+        device; beta: an integer in [0, r) or its 32 bytes, always a plain integer; lookup: an FrLookup already made of table_values (else one is
+        made and closed here).  m, h_f, h_t: new CUDA uint8 tensors of table.n, n and table.n scalars; the sums: 32 host bytes each, in the
+        data's form.  Chains scalars_add (beta broadcast), scalars_inverse, scalars_mul and scalars_scan(op="sum", totals=True) behind the
+        lookup; the inputs are left untouched.  beta = -value is NOT detected: the vector library's 1 / 0 = 0 applies, and the term of that
+        value is then missing from its sum -- draw beta after the columns are committed.  On Grumpkin, whose scalar field the vector library
+        has no unit for, the same columns come from the libraries that have one (_logup_without_frvec): scalars_gate for beta + x, the
+        products and the row sums, 1 / x as x^(r - 2) in 127 scalars_gate passes (again 1 / 0 = 0), scalars_mle_eval for the two sums --
+        the same bytes, some hundred launches more; there batch * n and the table are at most 2^25 scalars."""
+        r = self._frmle_field("logup")
+        if not (isinstance(table_values, torch.Tensor) and table_values.is_cuda and isinstance(f, torch.Tensor) and f.is_cuda):
+            raise TypeError("logup takes CUDA(HIP) uint8 tensors")
+        tt, n_t = _as_device_u8(table_values, 32, "table_values")
+        tf, total = _as_device_u8(f, 32, "f")
+        batch = int(batch)
+        if batch < 1 or total < 1 or total % batch:
+            raise ValueError("%d scalars are not %d rows" % (total, batch))
+        stride = total // batch
+        n = stride if n is None else int(n)
+        if not 1 <= n <= stride:
+            raise ValueError("n must lie in [1, %d], the length of a row, not %d" % (stride, n))
+        beta = int.from_bytes(self._frpoly_const(beta, r, "beta"), "little")
+        own = lookup is None
+        if own:
+            lookup = self.lookup_table(tt)
+        elif not isinstance(lookup, FrLookup) or lookup.n != n_t:
+            raise ValueError("lookup must be the FrLookup of the %d table values" % n_t)
+        try:
+            m = self.scalars_multiplicities(lookup, tf, batch=batch, n=n)
+        finally:
+            if own:
+                lookup.close()
+        den = torch.empty((batch * n, 32), dtype=torch.uint8, device=tf.device)  # a copy: 1 / (beta + f), row after row
+        den.view(batch, n, 32).copy_(tf.view(batch, stride, 32)[:, :n])
+        if self.curve == "grumpkin":
+            return (m,) + self._logup_without_frvec(r, den, tt.view(-1, 32)[:n_t], m, beta, batch, n)
+        self.scalars_inverse(self.scalars_add(den, beta))
+        h_f = den if batch == 1 else den[:n].clone()
+        for row in range(1, batch):
+            self.scalars_add(h_f, den[row * n:(row + 1) * n])
+        h_t = tt.view(-1, 32)[:n_t].clone()
+        self.scalars_mul(self.scalars_inverse(self.scalars_add(h_t, beta)), m)
+        _, sum_f = self.scalars_scan(h_f, op="sum", out=torch.empty_like(h_f), totals=True)
+        _, sum_t = self.scalars_scan(h_t, op="sum", out=torch.empty_like(h_t), totals=True)
+        return m, h_f, h_t, sum_f, sum_t
+
+    def _gate_inverse(self, x, r):
+        """1 / x element by element, 1 / 0 = 0, for a CUDA tensor of N = 2^k scalars, where the vector library has no unit: x^(r - 2), two bits
+        of the exponent per scalars_gate pass (acc^4 x^d, d <= 3: degree <= 7), between two buffers of two rows (acc, x) because a gate is
+        never in place -> a contiguous N x 32 tensor"""
+        big = x.shape[0]
+        bufs = [torch.empty((2, big, 32), dtype=torch.uint8, device=x.device) for _ in range(2)]
+        for b in bufs:
+            b[1].copy_(x)
+        digits, e = [], r - 2
+        while e:
+            digits.append(e & 3)
+            e >>= 2
+        digits.reverse()
+        self.scalars_gate(bufs[1], [(1, (1,) * digits[0])], batch=2, out=bufs[0][0])  # (the top digit is not 0)
+        cur = 0
+        for d in digits[1:]:
+            self.scalars_gate(bufs[cur], [(1, (0,) * 4 + (1,) * d)], batch=2, out=bufs[1 - cur][0])
+            cur = 1 - cur
+        return bufs[cur][0]
+
+    def _logup_without_frvec(self, r, den, table, m, beta, batch, n):
+        """logup's columns behind the lookup from scalars_gate and scalars_mle_eval alone.  den: the batch * n looked-up scalars, row after row
+        (overwritten); table, m: the table's values and multiplicities -> (h_f, h_t, sum h_f, sum h_t)"""
+        def pow2(k):
+            return max(2, 1 << (k - 1).bit_length())
+
+        if max(pow2(batch * n), pow2(table.shape[0])) > 1 << 25:
+            raise ValueError("on %s logup takes at most 2^25 looked-up scalars and table values" % self.curve)
+        one = (pow(2, 256, r) if getattr(self, "scalar_mont256", False) else 1).to_bytes(32, "little")
+        dev = den.device
+
+        def inverse_of_beta_plus(v):  # v: count x 32 -> 2^k x 32, the tail 1 / beta
+            count, big = v.shape[0], pow2(v.shape[0])
+            rows = torch.zeros((2, big, 32), dtype=torch.uint8, device=dev)
+            rows[0, :count].copy_(v)
+            rows[1].copy_(torch.frombuffer(bytearray(one), dtype=torch.uint8).to(dev))
+            return self._gate_inverse(self.scalars_gate(rows, [(1, (0,)), (beta, (1,))], batch=2), r)
+
+        def total(v):  # sum of 2^k scalars = 2^k times their multilinear extension at (1/2, .., 1/2)
+            k = v.shape[0].bit_length() - 1
+            at_half = int.from_bytes(self.scalars_mle_eval(v, [(r + 1) // 2] * k), "little")
+            return (at_half << k) % r
+
+        inv_f = inverse_of_beta_plus(den)
+        wide = pow2(n)
+        sum_rows = torch.zeros((wide, 32), dtype=torch.uint8, device=dev)
+        for first in range(0, batch, self.FRGATE_MAX_ROWS):  # at most 32 rows to a gate, each padded with zeros to 2^k
+            count = min(self.FRGATE_MAX_ROWS, batch - first)
+            rows = torch.zeros((count, wide, 32), dtype=torch.uint8, device=dev)
+            rows[:, :n].copy_(inv_f[first * n:(first + count) * n].view(count, n, 32))
+            self.scalars_gate(rows, [(1, (c,)) for c in range(count)], batch=count, out=sum_rows, accumulate=True)
+        n_t, big_t = table.shape[0], pow2(table.shape[0])
+        pair = torch.zeros((2, big_t, 32), dtype=torch.uint8, device=dev)
+        pair[0, :n_t].copy_(m)
+        pair[1].copy_(inverse_of_beta_plus(table))
+        prod = self.scalars_gate(pair, [(1, (0, 1))], batch=2)  # (zero behind the table: m is padded with zeros)
+        sums = [total(v).to_bytes(32, "little") for v in (sum_rows, prod)]
+        return sum_rows[:n].clone(), prod[:n_t].clone(), sums[0], sums[1]
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so, libmsm_frmle.so, libmsm_frmat.so and libmsm_frgate.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so, libmsm_frmle.so, libmsm_frmat.so, libmsm_frgate.so and libmsm_frlook.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -48,6 +48,13 @@ FRGATE_UNITS = ["frgate_bn254.hip", "frgate_grumpkin.hip", "frgate_pallas.hip", 
 FRGATE_SOURCES = FRGATE_UNITS + ["frgate_unit.h", "frgate_kernels.h", "frgate_host.h", "frgate_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
                                  "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
 FRGATE_HEADERS = [os.path.join(HERE, "..", "include", "msm_frgate.h"), HEADER]
+# libmsm_frlook.so (include/msm_frlook.h): lookup arguments over the scalar field -- the multiplicity column and the table indices of a logUp --,
+# the eighth library; it matches keys and computes nothing, so of the field's files it needs the constants alone (no fq29.h)
+FRLOOK_SO = os.path.join(HERE, "libmsm_frlook.so")
+FRLOOK_UNITS = ["frlook_bn254.hip", "frlook_grumpkin.hip", "frlook_pallas.hip", "frlook_vesta.hip", "frlook_bls12_381.hip"]
+FRLOOK_SOURCES = FRLOOK_UNITS + ["frlook_unit.h", "frlook_kernels.h", "frlook_host.h", "frlook_plan.h", "host_fr.h", "fr_bn254_constants.h",
+                                 "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FRLOOK_HEADERS = [os.path.join(HERE, "..", "include", "msm_frlook.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -292,6 +299,44 @@ def frgate_device_asm_is_current():
     return all(os.path.getmtime(f) >= newest for f in frgate_device_asm_paths())
 
 
+def frlook_device_asm_paths():
+    """The device assembly of libmsm_frlook.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRLOOK_UNITS]
+
+
+def frlook_build_stamp():
+    """build_stamp() for libmsm_frlook.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FRLOOK_SOURCES)] + FRLOOK_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def frlook_needs_build():
+    """libmsm_frlook.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FRLOOK_SO + ".stamp") as f:
+            return not os.path.exists(FRLOOK_SO) or f.read().strip() != frlook_build_stamp()
+    except OSError:
+        return True
+
+
+def frlook_device_asm_is_current():
+    """device_asm_is_current() for libmsm_frlook.so's units"""
+    if frlook_needs_build() or not all(os.path.exists(f) for f in frlook_device_asm_paths()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRLOOK_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in frlook_device_asm_paths())
+
+
 def build_stamp():
     """what the library on disk must have been built FROM to be the product: a hash over the compile flags (the environment switches of the
     diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source.  Written next to the
@@ -367,14 +412,15 @@ def compile_flags():
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
     from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so, msm-webgpu_amd/libmsm_frpoly.so,
-    msm-webgpu_amd/libmsm_frmle.so, msm-webgpu_amd/libmsm_frmat.so and msm-webgpu_amd/libmsm_frgate.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    msm-webgpu_amd/libmsm_frmle.so, msm-webgpu_amd/libmsm_frmat.so, msm-webgpu_amd/libmsm_frgate.so and msm-webgpu_amd/libmsm_frlook.so.  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
     do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
     do_frpoly = (force and not os.environ.get("MSM_HIP_SO")) or frpoly_needs_build()
     do_frmle = (force and not os.environ.get("MSM_HIP_SO")) or frmle_needs_build()
     do_frmat = (force and not os.environ.get("MSM_HIP_SO")) or frmat_needs_build()
     do_frgate = (force and not os.environ.get("MSM_HIP_SO")) or frgate_needs_build()
-    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle and not do_frmat and not do_frgate:
+    do_frlook = (force and not os.environ.get("MSM_HIP_SO")) or frlook_needs_build()
+    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle and not do_frmat and not do_frgate and not do_frlook:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -402,8 +448,8 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of all seven libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else []) + (FRMAT_UNITS if do_frmat else []) + (FRGATE_UNITS if do_frgate else [])
+    # one pool for the units of all eight libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else []) + (FRMAT_UNITS if do_frmat else []) + (FRGATE_UNITS if do_frgate else []) + (FRLOOK_UNITS if do_frlook else [])
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
@@ -434,6 +480,10 @@ def build(force=False, verbose=False):
         link([objs[u] for u in FRGATE_UNITS], FRGATE_SO)
         with open(FRGATE_SO + ".stamp", "w") as f:
             f.write(frgate_build_stamp() + "\n")
+    if do_frlook:
+        link([objs[u] for u in FRLOOK_UNITS], FRLOOK_SO)
+        with open(FRLOOK_SO + ".stamp", "w") as f:
+            f.write(frlook_build_stamp() + "\n")
     return SO
 
 

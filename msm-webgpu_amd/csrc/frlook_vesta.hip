@@ -1,0 +1,10 @@
+// The scalar field of Vesta as a translation unit of libmsm_frlook.so: the field's r and the lookup kernels (csrc/frlook_unit.h,
+// csrc/frlook_kernels.h), reached by the host code through the table below.
+#define MSM_FIELD_NS frl_vesta
+#define MSM_CURVE_CONSTANTS "fr_vesta_constants.h"
+#include "frlook_unit.h"
+
+extern "C" const FrlookOps* msm_frlook_ops_vesta(void) {
+  static const FrlookOps ops = {frl_vesta::FQ_P32, frl_vesta::frlook_launch_build, frl_vesta::frlook_launch_count, frl_vesta::frlook_launch_finish};
+  return &ops;
+}
