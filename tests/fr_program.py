@@ -1,0 +1,850 @@
+"""Programs over the seven scalar-field libraries (libmsm_fr, frvec, frpoly, frmle, frmat, frgate, frlook): a generator, and a model interpreter
+that predicts every byte a program leaves on the device.  Needs no GPU, no HIP and no torch: tools/fuzz_fr.py runs the programs on the device and
+compares, tests/test_fr_program.py checks the tester itself.
+
+A program is a list of steps (kind, field index, arguments): tuples of ints, strings, lists and dicts, replayable from their repr alone.  Every
+field of a program has an ARENA of 32-byte scalars on the device; an operand is a range [off16, n] of it: n scalars from byte 16 * off16 on.  The
+arena has two halves: in the first a scalar starts at 0 mod 32, in the second at 16 mod 32 (the arena's base is aligned far more strictly), so every
+byte is always read at the same alignment and stays part of one canonical scalar.  Each half is four banks; an output is exactly one of the inputs
+or lies in a bank that no input of the call touches -- or, in an "overlap" step, overlaps an input in part, which the headers say is refused.
+
+The model mirrors an arena as its STORED bytes: a step decodes its operands under the field's current form (canonical, or a * 2^256 mod r),
+computes with the per-library models of this directory, and encodes again -- so set_scalar_format changes no byte, only how later steps read."""
+import functools
+import hashlib
+import random
+
+from tests import frgate_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
+
+FIELD_R = {
+    "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+    "grumpkin": 21888242871839275222246405745257275088696311157297823662689037894645226208583,
+    "pallas": 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
+    "vesta": 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
+    "bls12_381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001,
+}
+BANK, BANKS = 4608, 4  # scalars to a bank, banks to a half of the arena
+HALF = BANK * BANKS
+ARENA16 = 4 * HALF + 2  # the arena in units of 16 bytes: half A, 16 bytes that nobody writes, half B, 16 more
+LENGTHS = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2051, 4097)
+LARGE, SMALL = 1023, 65  # a "large" step has an operand of at least LARGE scalars to a row, a "small" one at most SMALL
+ERR_INVALID_ARG, ERR_NONCANONICAL, REFUSED = -2, -4, "refused"  # MSM_HIP_ERR_*; REFUSED: the Python layer raises ValueError before the C call
+HOOKS = {"fr_test_pass_bits": (0, 1, 2, 3, 5), "frvec_test_tile": (0, 2, 3, 8, 64), "frpoly_test_tile": (0, 2, 3, 8, 64), "frmle_test_tile": (0, 2, 8, 64),
+         "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8)}
+LIBRARY = {"map": "frvec", "inverse": "frvec", "scan": "frvec", "fft": "fr", "eval": "frpoly", "divide": "frpoly", "dot": "frpoly", "combine": "frpoly",
+           "powers": "frpoly", "mle_fold": "frmle", "mle_eval": "frmle", "eq": "frmle", "round": "frmle", "matrix": "frmat", "matvec": "frmat", "gate": "frgate",
+           "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook"}
+LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook")
+GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult")  # the libraries that serve its scalar field
+KINDS = tuple(LIBRARY) + ("format", "hook", "close", "stream", "plant", "overlap")
+
+
+def label(step):
+    """what a step counts as: its kind, "overlap" where its output overlaps an input in part"""
+    return "overlap" if step[2].get("overlap") else step[0]
+
+
+@functools.lru_cache(maxsize=None)
+def root_of_unity(r, log_n):
+    """the smallest quadratic non-residue raised to (r - 1) / 2^log_n: what api.root_of_unity gives (the driver compares the two)"""
+    g = 2
+    while pow(g, (r - 1) // 2, r) != r - 1:
+        g += 1
+    return pow(g, (r - 1) >> log_n, r)
+
+
+def expand(seed, count, r):
+    """`count` integers below r from an integer seed, by SHAKE-256: no random generator is needed to replay a step"""
+    raw = hashlib.shake_256(b"fr_program/%d" % seed).digest(40 * count)
+    return [int.from_bytes(raw[40 * i:40 * i + 40], "little") % r for i in range(count)]
+
+
+def initial_arena(seed):
+    """16 * ARENA16 bytes whose every aligned 16-byte half ends in a byte below 16: a scalar read at either alignment is below 2^252 < r"""
+    b = bytearray(hashlib.shake_256(b"fr_program/arena/%d" % seed).digest(16 * ARENA16))
+    b[15::16] = bytes(x & 15 for x in b[15::16])
+    return b
+
+
+def _cuts(a, b):
+    """do the ranges [off16, n] a and b share a byte"""
+    return a[0] < b[0] + 2 * b[1] and b[0] < a[0] + 2 * a[1]
+
+
+class Model:
+    """the interpreter: step() applies a step to the mirrored arenas and returns what the device must have done --
+    {"error": None / ERR_* / REFUSED, "writes": [(off16, n), ..] ranges the step wrote (compared), "rewrite": ranges that are unspecified after a
+    predicted ERR_NONCANONICAL (the driver rewrites them from the model), "host": the host values the call returns (None where there are none)}"""
+
+    def __init__(self, fields):
+        self.fields = list(fields)
+        self.r = [FIELD_R[f] for f in self.fields]
+        self.arena = [bytearray(16 * ARENA16) for _ in self.fields]
+        self.mont = [False] * len(self.fields)
+        self.mats = [{} for _ in self.fields]
+        self.tabs = [{} for _ in self.fields]
+        self.planted = [{} for _ in self.fields]  # off16 -> the 32 bytes a planted value replaced
+        self.hooks = {h: 0 for h in HOOKS}
+        self.side_stream = False
+
+    # ---- the arena -------------------------------------------------------------------------------------------------------------------------
+    def raw(self, f, rng):
+        return bytes(self.arena[f][16 * rng[0]:16 * rng[0] + 32 * rng[1]])
+
+    def stored(self, f, rng):
+        return frvec_model.from_bytes(self.raw(f, rng))
+
+    def plain(self, f, rng):
+        v = self.stored(f, rng)
+        return frvec_model.mont(v, self.r[f], back=True) if self.mont[f] else v
+
+    def enc(self, f, vals):
+        """plain values -> bytes in the field's current form"""
+        vals = [v % self.r[f] for v in vals]
+        return frvec_model.to_bytes(frvec_model.mont(vals, self.r[f]) if self.mont[f] else vals)
+
+    def put(self, f, off16, data):
+        self.arena[f][16 * off16:16 * off16 + len(data)] = data
+
+    def _heal(self, f):
+        spots = []
+        for off16, old in self.planted[f].items():
+            self.put(f, off16, old)
+            spots.append((off16, 1))
+        self.planted[f].clear()
+        return spots
+
+    def _run(self, f, reads, writes, compute):
+        """reads: the ranges whose every scalar the call compares with r; writes: what it writes; compute() -> ([(off16, bytes), ..], host)"""
+        if self.planted[f]:
+            hit = any(_cuts((p, 1), rd) and (p - rd[0]) % 2 == 0 for p in self.planted[f] for rd in reads)
+            assert hit, "a planted value must be read by the step that follows it"
+            return {"error": ERR_NONCANONICAL, "writes": [], "rewrite": [tuple(w) for w in writes] + self._heal(f), "host": None}
+        puts, host = compute()
+        for off16, data in puts:
+            self.put(f, off16, data)
+        return {"error": None, "writes": [(off16, len(data) // 32) for off16, data in puts], "rewrite": [], "host": host}
+
+    @staticmethod
+    def _fail(code):
+        return {"error": code, "writes": [], "rewrite": [], "host": None}
+
+    @staticmethod
+    def _partial(out, ins):
+        """an output that shares bytes with an input without starting where it starts"""
+        return any(_cuts(out, i) and out[0] != i[0] for i in ins)
+
+    def step(self, step):
+        kind, f, a = step
+        out = getattr(self, "op_" + kind)(f, **{k: v for k, v in a.items() if k != "overlap"})
+        assert bool(a.get("overlap")) == (out["error"] == ERR_INVALID_ARG), "an overlap step, and only that, is refused with ERR_INVALID_ARG"
+        return out
+
+    # ---- steps that call no library ------------------------------------------------------------------------------------------------------------
+    def op_init(self, f, seed):
+        self.arena[f] = initial_arena(seed)
+        self.planted[f].clear()
+        return {"error": None, "writes": [], "rewrite": [(0, ARENA16 // 2)], "host": None}
+
+    def op_format(self, f, mont):
+        self.mont[f] = bool(mont)
+        return self._fail(None)
+
+    def op_hook(self, f, name, value):
+        assert value in HOOKS[name]
+        self.hooks[name] = value
+        return self._fail(None)
+
+    def op_stream(self, f, side):
+        self.side_stream = bool(side)
+        return self._fail(None)
+
+    def op_close(self, f, what, slot):
+        del (self.mats if what == "mat" else self.tabs)[f][slot]
+        return self._fail(None)
+
+    def op_plant(self, f, at, value):
+        assert self.r[f] <= value < 1 << 256 and at not in self.planted[f]
+        self.planted[f][at] = self.raw(f, (at, 1))
+        self.put(f, at, value.to_bytes(32, "little"))
+        return {"error": None, "writes": [(at, 1)], "rewrite": [], "host": None}
+
+    # ---- libmsm_frvec --------------------------------------------------------------------------------------------------------------------------
+    def op_map(self, f, op, a, b, c, out):
+        dst = a if out is None else out
+        vecs = [v for v in (a, b, c) if isinstance(v, (list, tuple))]
+        if self._partial(dst, vecs):
+            return self._fail(ERR_INVALID_ARG)
+
+        def compute():
+            val = lambda v: v if v is None or isinstance(v, int) else self.plain(f, v)
+            return [(dst[0], self.enc(f, frvec_model.map_op(op, self.plain(f, a), val(b), val(c), self.r[f])))], None
+        return self._run(f, vecs, [dst], compute)
+
+    def op_inverse(self, f, a, out):
+        dst = a if out is None else out
+        if self._partial(dst, [a]):
+            return self._fail(ERR_INVALID_ARG)
+        return self._run(f, [a], [dst], lambda: ([(dst[0], self.enc(f, frvec_model.inverse(self.plain(f, a), self.r[f])))], None))
+
+    def op_scan(self, f, a, op, exclusive, batch, out, totals):
+        dst = a if out is None else out
+        if self._partial(dst, [a]):
+            return self._fail(ERR_INVALID_ARG)
+
+        def compute():
+            res, tot = frvec_model.scan(self.plain(f, a), op, exclusive, self.r[f], batch)
+            return [(dst[0], self.enc(f, res))], (self.enc(f, tot) if totals else None)
+        return self._run(f, [a], [dst], compute)
+
+    # ---- libmsm_fr -----------------------------------------------------------------------------------------------------------------------------
+    def op_fft(self, f, a, log_n, batch, inverse, shift, omega):
+        r, n = self.r[f], 1 << log_n
+        assert a[1] == batch * n
+
+        def compute():
+            w = root_of_unity(r, log_n) if omega is None else omega
+            v, res = self.plain(f, a), []
+            for k in range(batch):
+                row = v[k * n:(k + 1) * n]
+                res += ntt_model.intt(row, w, r, shift or 1) if inverse else ntt_model.ntt(row, w, r, pre=shift or 1)
+            return [(a[0], self.enc(f, res))], None
+        return self._run(f, [a], [a], compute)
+
+    # ---- libmsm_frpoly -------------------------------------------------------------------------------------------------------------------------
+    def op_eval(self, f, a, z, batch):
+        return self._run(f, [a], [], lambda: ([], self.enc(f, [frpoly_model.evaluate(row, z, self.r[f]) for row in frpoly_model.rows_of(self.plain(f, a), batch)])))
+
+    def op_divide(self, f, a, z, batch, out, values):
+        dst = a if out is None else out
+        if self._partial(dst, [a]):
+            return self._fail(ERR_INVALID_ARG)
+
+        def compute():
+            q, vals = [], []
+            for row in frpoly_model.rows_of(self.plain(f, a), batch):
+                qq, y = frpoly_model.divide(row, z, self.r[f])
+                q += qq
+                vals.append(y)
+            return [(dst[0], self.enc(f, q))], (self.enc(f, vals) if values else None)
+        return self._run(f, [a], [dst], compute)
+
+    def op_dot(self, f, a, b, batch):
+        def compute():
+            rows, other = frpoly_model.rows_of(self.plain(f, a), batch), self.plain(f, b)
+            n = len(rows[0])
+            return [], self.enc(f, [frpoly_model.dot(row, other[:n] if b[1] == n else other[k * n:(k + 1) * n], self.r[f]) for k, row in enumerate(rows)])
+        return self._run(f, [a, b], [], compute)
+
+    def op_combine(self, f, a, coeffs, out):
+        if self._partial(out, [a]):
+            return self._fail(ERR_INVALID_ARG)
+        return self._run(f, [a], [out], lambda: ([(out[0], self.enc(f, frpoly_model.combine(frpoly_model.rows_of(self.plain(f, a), len(coeffs)), coeffs, self.r[f])))], None))
+
+    def op_powers(self, f, g, n, scale, out):
+        assert out[1] == n
+        return self._run(f, [], [out], lambda: ([(out[0], self.enc(f, frpoly_model.powers(g, n, self.r[f], scale)))], None))
+
+    # ---- libmsm_frmle --------------------------------------------------------------------------------------------------------------------------
+    def _rows(self, f, a, batch, n):
+        """-> (stride, the first n plain values of every row, the ranges of those)"""
+        stride = a[1] // batch
+        assert stride * batch == a[1] and n <= stride
+        v = self.plain(f, a)
+        return stride, [v[k * stride:k * stride + n] for k in range(batch)], [(a[0] + 2 * k * stride, n) for k in range(batch)]
+
+    def op_mle_fold(self, f, a, c, batch, n, out):
+        dst = a if out is None else out
+        stride = a[1] // batch
+        span = (dst[0], (batch - 1) * stride + n)
+        if self._partial(span, [(a[0], span[1])]):
+            return self._fail(ERR_INVALID_ARG)
+        _, rows, reads = self._rows(f, a, batch, n)
+        return self._run(f, reads, [(dst[0] + 2 * k * stride, n // 2) for k in range(batch)],
+                         lambda: ([(dst[0] + 2 * k * stride, self.enc(f, frmle_model.fold(row, c, self.r[f]))) for k, row in enumerate(rows)], None))
+
+    def op_mle_eval(self, f, a, point, batch, n):
+        _, rows, reads = self._rows(f, a, batch, n)
+        return self._run(f, reads, [], lambda: ([], self.enc(f, [frmle_model.evaluate(row, point, self.r[f]) for row in rows])))
+
+    def op_eq(self, f, point, scale, out):
+        assert out[1] == 1 << len(point)
+        return self._run(f, [], [out], lambda: ([(out[0], self.enc(f, frmle_model.eq(point, self.r[f], scale)))], None))
+
+    def op_round(self, f, a, terms, batch, n, fold):
+        stride, rows, ranges = self._rows(f, a, batch, n)
+        named = sorted({row for _, which in terms for row in which})
+        reads = ranges if fold is not None else [ranges[k] for k in named]
+
+        def compute():
+            puts, cur = [], rows
+            if fold is not None:
+                cur = [frmle_model.fold(row, fold, self.r[f]) for row in rows]
+                puts = [(a[0] + 2 * k * stride, self.enc(f, row)) for k, row in enumerate(cur)]
+            return puts, self.enc(f, frmle_model.round_values(cur, [(c, tuple(w)) for c, w in terms], self.r[f]))
+        return self._run(f, reads, [(rg[0], n // 2) for rg in ranges] if fold is not None else [], compute)
+
+    # ---- libmsm_frmat --------------------------------------------------------------------------------------------------------------------------
+    def op_matrix(self, f, slot, rows, cols, row_ptr, col_idx, vseed, transpose):
+        assert slot not in self.mats[f] and len(self.mats[f]) < 3
+        self.mats[f][slot] = (rows, cols, list(row_ptr), list(col_idx), expand(vseed, len(col_idx), self.r[f]), bool(transpose))
+        return self._fail(None)
+
+    def op_matvec(self, f, slot, x, out, transpose, pad_to):
+        rows, cols, row_ptr, col_idx, values, has_t = self.mats[f][slot]
+        assert has_t or not transpose
+        in_len, out_len = (rows, cols) if transpose else (cols, rows)
+        y_len = out_len if pad_to is None else pad_to
+        assert x[1] == in_len and out[1] == y_len
+        if _cuts(out, x):
+            return self._fail(ERR_INVALID_ARG)
+        used = sorted({i for i in range(rows) if row_ptr[i + 1] > row_ptr[i]} if transpose else set(col_idx))  # the elements of x that are read
+
+        def compute():
+            y = frmat_model.matvec(rows, cols, row_ptr, col_idx, values, self.plain(f, x), self.r[f], transpose)
+            return [(out[0], self.enc(f, y + [0] * (y_len - out_len)))], None
+        return self._run(f, [(x[0] + 2 * j, 1) for j in used], [out], compute)
+
+    # ---- libmsm_frgate -------------------------------------------------------------------------------------------------------------------------
+    def op_gate(self, f, a, terms, batch, n, step, scale, out, accumulate):
+        stride, rows, ranges = self._rows(f, a, batch, n)
+        assert out[1] == n
+        if _cuts(out, a) or (scale is not None and _cuts(out, scale)):
+            return self._fail(REFUSED)  # (never in place: the Python layer raises before the C call)
+        named = sorted({fr[0] for _, factors in terms for fr in factors})
+        reads = [ranges[k] for k in named] + ([scale] if scale is not None else []) + ([out] if accumulate else [])
+
+        def compute():
+            res = frgate_model.apply(rows, terms, n, step, self.plain(f, scale) if scale is not None else None, self.plain(f, out) if accumulate else None, self.r[f])
+            return [(out[0], self.enc(f, res))], None
+        return self._run(f, reads, [out], compute)
+
+    def op_vanishing_inverse(self, f, log_n, log_ext, shift, out):
+        r = self.r[f]
+        assert out[1] == 1 << log_ext
+        return self._run(f, [], [out], lambda: ([(out[0], self.enc(f, frgate_model.vanishing_inverse(log_n, log_ext, shift, root_of_unity(r, log_n + log_ext), r)))], None))
+
+    def op_quotient(self, f, a, terms, batch, log_n, log_ext, shift, out):
+        r, n = self.r[f], 1 << log_n
+        assert a[1] == batch * n and out[1] == n << log_ext
+
+        def compute():
+            cols = frpoly_model.rows_of(self.plain(f, a), batch)
+            return [(out[0], self.enc(f, frgate_model.quotient(cols, terms, log_n, log_ext, shift, root_of_unity(r, log_n + log_ext), r)))], None
+        return self._run(f, [a], [out], compute)
+
+    # ---- libmsm_frlook -------------------------------------------------------------------------------------------------------------------------
+    def op_table(self, f, slot, t, n):
+        assert slot not in self.tabs[f] and len(self.tabs[f]) < 3 and n <= t[1]
+
+        def compute():
+            self.tabs[f][slot] = (self.stored(f, (t[0], n)), self.mont[f])  # keys are compared AS STORED; the form belongs to the handle
+            return [], len(set(self.tabs[f][slot][0]))
+        return self._run(f, [(t[0], n)], [], compute)  # (ERR_NONCANONICAL: no handle is made)
+
+    def op_mult(self, f, slot, v, batch, n, out, indices, counts):
+        keys, form = self.tabs[f][slot]
+        stride = v[1] // batch
+        assert out[1] == len(keys) and stride * batch == v[1] and 1 <= n <= stride and not _cuts(out, v)
+        if form != self.mont[f]:
+            return self._fail(REFUSED)  # (a count whose form differs from the handle's is refused)
+        stored = self.stored(f, v)
+
+        def compute():
+            cnt, idx, missing, first, _ = frlook_model.lookup(keys, [stored[k * stride:(k + 1) * stride] for k in range(batch)], n)
+            host = ((idx,) if indices else ()) + ((cnt,) if counts else ()) + ((missing, first if missing else None),)
+            return [(out[0], self.enc(f, cnt))], host
+        return self._run(f, [(v[0] + 2 * k * stride, n) for k in range(batch)], [out], compute)
+
+
+class Refused(Exception):
+    """what a backend raises where a call fails: code is ERR_* or REFUSED"""
+
+    def __init__(self, code):
+        super().__init__("refused: %r" % (code,))
+        self.code = code
+
+
+class ModelBackend:
+    """a backend that IS the model: tools/fuzz_fr.py run against it must report success (tests/test_fr_program.py plants its faults in
+    subclasses of this).  One method per step kind, plus the arena's read and write."""
+
+    def __init__(self, fields):
+        self.m = Model(fields)
+
+    def read16(self, f, lo, hi):
+        """the bytes of the 16-byte units lo .. hi of the arena"""
+        return bytes(self.m.arena[f][16 * lo:16 * hi])
+
+    def write(self, f, off16, data):
+        self.m.put(f, off16, data)
+
+    def reset(self):
+        """between programs: no hook, no handle, the canonical form; the arenas stay as they are"""
+        arenas = self.m.arena
+        self.m = Model(self.m.fields)
+        self.m.arena = arenas
+
+    def close(self):
+        pass
+
+    def __getattr__(self, name):
+        if not name.startswith("op_"):
+            raise AttributeError(name)
+        return lambda f, **a: self.call(name[3:], f, a)
+
+    def call(self, kind, f, a):
+        """one step: the model's own; a call the model refuses raises Refused like the device side"""
+        out = getattr(self.m, "op_" + kind)(f, **a)
+        if out["error"] is not None:
+            raise Refused(out["error"])
+        return out["host"]
+
+
+def sizes(steps):
+    """-> [(index, kind, field, scalars per row)] of the steps that call a library and have a size: the length of a row of the largest operand; for
+    a sparse product the entries of its matrix (its work).  What "large" (>= LARGE) and "small" (<= SMALL) are measured on."""
+    out, nnz = [], {}
+    for i, (kind, f, a) in enumerate(steps):
+        if kind == "matrix":
+            nnz[f, a["slot"]] = len(a["col_idx"])
+        if a.get("overlap") or kind not in LIBRARY:
+            continue
+        if kind in ("map", "inverse"):
+            n = a["a"][1]
+        elif kind in ("scan", "eval", "divide", "dot"):
+            n = a["a"][1] // a["batch"]
+        elif kind == "fft":
+            n = 1 << a["log_n"]
+        elif kind in ("combine", "eq"):
+            n = a["out"][1]
+        elif kind in ("powers", "mle_fold", "mle_eval", "round", "gate", "mult"):
+            n = a["n"]
+        elif kind == "matvec":
+            n = nnz[f, a["slot"]]
+        elif kind == "table":
+            n = a["t"][1]
+        else:
+            continue
+        out.append((i, kind, f, n))
+    return out
+
+
+# ---- the generator ---------------------------------------------------------------------------------------------------------------------------------
+_WEIGHT = {"map": 10, "inverse": 5, "scan": 8, "fft": 8, "eval": 4, "divide": 5, "dot": 4, "combine": 4, "powers": 4, "mle_fold": 5, "mle_eval": 4, "eq": 3,
+           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "format": 5, "hook": 7, "close": 3,
+           "stream": 3, "overlap": 3}
+_LEN_WEIGHT = {1: 6, 2: 6, 63: 6, 64: 6, 65: 6, 255: 3, 256: 3, 257: 3, 1023: 1.6, 1024: 1.6, 1025: 1.6, 2051: 0.9, 4097: 0.6}
+_PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "matvec", "gate", "table", "mult")
+_OVERLAPS = ("map", "inverse", "scan", "divide", "combine", "mle_fold", "matvec")
+
+
+class _Gen:
+    def __init__(self, rnd, fields, kinds):
+        self.rnd, self.fields, self.r = rnd, list(fields), [FIELD_R[f] for f in fields]
+        self.kinds = [k for k in _WEIGHT if kinds is None or k in kinds]
+        self.mont = [False] * len(fields)
+        self.mats = [{} for _ in fields]  # slot -> (rows, cols, transpose, row_ptr, col_idx)
+        self.tabs = [{} for _ in fields]  # slot -> (n, form, the range it was made of)
+        self.side = False
+        self.steps = []
+        self.prev_f, self.follow = None, None  # follow: (field, kind) of a large step that a small one of the same entry point is to follow
+        self.plant_ok = kinds is None or "plant" in kinds
+        self.last_fft = {}  # field -> (log_n, omega) of its last transform
+
+    # ---- draws ---------------------------------------------------------------------------------------------------------------------------
+    def scalar(self, f):
+        c = self.rnd.random()
+        return self.rnd.choice((0, 1, 2, self.r[f] - 1)) if c < 0.15 else self.rnd.randrange(self.r[f])
+
+    def length(self, small, cap=BANK):
+        if small:
+            return self.rnd.choice((1, 2, 63, 64, 65))
+        pool = [n for n in LENGTHS if n <= cap]
+        return self.rnd.choices(pool, [_LEN_WEIGHT[n] for n in pool])[0]
+
+    def log_n(self, small, least=0, most=12):
+        if small:
+            return self.rnd.randrange(least, 7)
+        pool = list(range(least, most + 1))
+        return self.rnd.choices(pool, [6 if k <= 6 else 3 if k <= 8 else 1.5 if k <= 10 else 0.8 for k in pool])[0]
+
+    def batch(self, n, most=5):
+        return self.rnd.choice([b for b in (1, 1, 2, 3, 5) if b * n <= BANK and b <= most])
+
+    def place(self, n, avoid=()):
+        """a range of n scalars in a bank that none of the ranges `avoid` touches: (off16, n)"""
+        taken = {self.bank_of(a) for a in avoid}
+        while True:
+            half, bank = (1 if self.rnd.random() < 0.4 else 0), self.rnd.randrange(BANKS)
+            if (half, bank) not in taken:
+                break
+        at = 0 if self.rnd.random() < 0.3 else self.rnd.randrange(BANK - n + 1)
+        return [half * (2 * HALF + 1) + 2 * (bank * BANK + at), n]
+
+    @staticmethod
+    def bank_of(rng):
+        half = 1 if rng[0] > 2 * HALF else 0
+        return half, (rng[0] - half * (2 * HALF + 1)) // 2 // BANK
+
+    def out_for(self, ins, n, same):
+        """an output of n scalars: exactly one of the ranges `same` (in place), or in a bank of its own"""
+        same = [s for s in same if s[1] == n and not Model._partial(s, ins)]  # (two inputs may overlap one another, but then neither is the output)
+        if same and self.rnd.random() < 0.5:
+            return list(self.rnd.choice(same))
+        return self.place(n, ins)
+
+    def emit(self, kind, f, **a):
+        self.steps.append((kind, f, a))
+
+    def maybe_plant(self, f, kind, spots):
+        """before a step that reads the scalars `spots` (off16 each): sometimes plant a value >= r in one of them"""
+        if self.plant_ok and kind in _PLANTABLE and spots and self.rnd.random() < 0.09:
+            r = self.r[f]
+            self.emit("plant", f, at=self.rnd.choice(spots), value=self.rnd.choice((r, r + 1, (1 << 256) - 1, r + self.rnd.randrange(1 << 200))))
+
+    @staticmethod
+    def spots(rng, rnd, rows=None, stride=None, n=None):
+        """some scalars of a range (of the first n of its rows): first, last, one between"""
+        if rows is None:
+            picks = {0, rng[1] - 1, rnd.randrange(rng[1])}
+        else:
+            picks = {k * stride + i for k in rows for i in (0, n - 1, rnd.randrange(n))}
+        return [rng[0] + 2 * i for i in sorted(picks)]
+
+    # ---- one step kind each; `small` asks for operands of at most SMALL scalars; -> the scalars per row, or None ---------------------------------
+    def g_map(self, f, small, overlap=False):
+        n = self.length(small, 2051 if overlap else BANK)
+        n = max(n, 2) if overlap else n
+        op = self.rnd.choice(frvec_model.MAPS)
+        a = self.place(n)
+        operand = lambda: self.scalar(f) if self.rnd.random() < 0.35 else (list(a) if self.rnd.random() < 0.15 else self.place(n))
+        b = operand()
+        c = operand() if op in ("mul_add", "mul_sub") else None
+        vecs = [v for v in (a, b, c) if isinstance(v, list)]
+        if overlap:
+            out = self.shifted(self.rnd.choice(vecs))
+        else:
+            out = self.out_for(vecs, n, vecs)
+            if out == a and self.rnd.random() < 0.5:
+                out = None
+            self.maybe_plant(f, "map", self.spots(self.rnd.choice(vecs), self.rnd))
+        self.emit("map", f, op=op, a=a, b=b, c=c, out=out, **({"overlap": True} if overlap else {}))
+        return n
+
+    def shifted(self, rng, n=None, least=1):
+        """a range of n scalars (default: as many) that starts `least` or more scalars into rng and stays inside its bank; rng is moved to the
+        start of the bank where there is no room behind it"""
+        n = rng[1] if n is None else n
+        half, bank = self.bank_of(rng)
+        base = half * (2 * HALF + 1) + 2 * bank * BANK
+        room = BANK - (rng[0] - base) // 2 - n  # the largest shift that keeps the n scalars inside the bank
+        if room < least:
+            rng[0], room = base, BANK - n
+        return [rng[0] + 2 * self.rnd.randrange(least, min(rng[1] - 1, room) + 1), n]
+
+    def g_inverse(self, f, small, overlap=False):
+        n = max(self.length(small, 2051 if overlap else BANK), 2 if overlap else 1)
+        a = self.place(n)
+        if overlap:
+            out = self.shifted(a)
+        else:
+            out = self.out_for([a], n, [a]) if self.rnd.random() < 0.6 else None
+            self.maybe_plant(f, "inverse", self.spots(a, self.rnd))
+        self.emit("inverse", f, a=a, out=out, **({"overlap": True} if overlap else {}))
+        return n
+
+    def g_scan(self, f, small, overlap=False):
+        n = self.length(small, 2051 if overlap else BANK)
+        batch = self.batch(n)
+        if overlap and n * batch < 2:
+            n = 2
+        a = self.place(n * batch)
+        if overlap:
+            out = self.shifted(a)
+        else:
+            out = self.out_for([a], n * batch, [a]) if self.rnd.random() < 0.6 else None
+            self.maybe_plant(f, "scan", self.spots(a, self.rnd))
+        self.emit("scan", f, a=a, op=self.rnd.choice(("sum", "product")), exclusive=self.rnd.random() < 0.5, batch=batch, out=out, totals=self.rnd.random() < 0.5,
+                  **({"overlap": True} if overlap else {}))
+        return n
+
+    def g_fft(self, f, small):
+        log_n = self.log_n(small)
+        again = self.last_fft.get(f)
+        if again and again[0] >= 2 and not small and self.rnd.random() < 0.4:  # the length of this field's last transform, with another root
+            log_n = again[0]
+        n = 1 << log_n
+        batch = self.batch(n, 3)
+        a = self.place(n * batch)
+        omega = None
+        if (again[1] is None) if again and again[0] == log_n else self.rnd.random() < 0.4:  # a caller's root: an odd power of the default one is primitive too
+            omega = pow(root_of_unity(self.r[f], log_n), self.rnd.choice((3, 5, 7)) if log_n else 1, self.r[f])
+        self.last_fft[f] = (log_n, omega)
+        self.maybe_plant(f, "fft", self.spots(a, self.rnd))
+        self.emit("fft", f, a=a, log_n=log_n, batch=batch, inverse=self.rnd.random() < 0.4, shift=self.rnd.randrange(1, self.r[f]) if self.rnd.random() < 0.4 else None,
+                  omega=omega)
+        return n
+
+    def g_eval(self, f, small):
+        n = self.length(small)
+        batch = self.batch(n)
+        a = self.place(n * batch)
+        self.maybe_plant(f, "eval", self.spots(a, self.rnd))
+        self.emit("eval", f, a=a, z=self.scalar(f), batch=batch)
+        return n
+
+    def g_divide(self, f, small, overlap=False):
+        n = self.length(small, 2051 if overlap else BANK)
+        batch = self.batch(n)
+        if overlap and n * batch < 2:
+            n = 2
+        a = self.place(n * batch)
+        if overlap:
+            out = self.shifted(a)
+        else:
+            out = self.out_for([a], n * batch, [a]) if self.rnd.random() < 0.6 else None
+            self.maybe_plant(f, "divide", self.spots(a, self.rnd))
+        self.emit("divide", f, a=a, z=self.scalar(f), batch=batch, out=out, values=self.rnd.random() < 0.5, **({"overlap": True} if overlap else {}))
+        return n
+
+    def g_dot(self, f, small):
+        n = self.length(small)
+        batch = self.batch(n)
+        a = self.place(n * batch)
+        b = list(a) if self.rnd.random() < 0.15 else self.place(n if batch > 1 and self.rnd.random() < 0.5 else n * batch)
+        self.maybe_plant(f, "dot", self.spots(self.rnd.choice((a, b)), self.rnd))
+        self.emit("dot", f, a=a, b=b, batch=batch)
+        return n
+
+    def g_combine(self, f, small, overlap=False):
+        n = max(self.length(small, 1025), 2 if overlap else 1)
+        k = self.rnd.choice([k for k in (1, 2, 3, 4) if k * n <= BANK])
+        a = self.place(n * k)
+        if overlap:
+            out = self.shifted(a, n)
+        else:
+            out = [a[0], n] if self.rnd.random() < 0.4 else self.place(n, [a])
+            self.maybe_plant(f, "combine", self.spots(a, self.rnd))
+        self.emit("combine", f, a=a, coeffs=[self.scalar(f) for _ in range(k)], out=out, **({"overlap": True} if overlap else {}))
+        return n
+
+    def g_powers(self, f, small):
+        n = self.length(small)
+        g = self.rnd.choice((1, self.r[f] - 1, 2)) if self.rnd.random() < 0.4 else self.scalar(f)  # (a base of small order: a table with repeated values)
+        self.emit("powers", f, g=g, n=n, scale=self.scalar(f) if self.rnd.random() < 0.5 else 1, out=self.place(n))
+        return n
+
+    def table_rows(self, small, least, most_batch):
+        """-> (n, batch, stride) of a call over rows `stride` apart whose first n = 2^k scalars are the table"""
+        n = 1 << self.log_n(small, least)
+        batch = self.batch(n + 1, most_batch)
+        return n, batch, n + self.rnd.choice((0, 0, 1, 3) if (n + 3) * batch <= BANK else (0,))
+
+    def g_mle_fold(self, f, small, overlap=False):
+        n, batch, stride = self.table_rows(small, 1, 5)
+        a = self.place(batch * stride)
+        if overlap:  # (what counts is the span from the first row's first scalar to the last row's n-th)
+            span = [a[0], (batch - 1) * stride + n]
+            out = self.shifted(span, batch * stride)
+            a[0] = span[0]
+        else:
+            out = self.out_for([a], batch * stride, [a]) if self.rnd.random() < 0.5 else None
+            self.maybe_plant(f, "mle_fold", self.spots(a, self.rnd, range(batch), stride, n))
+        self.emit("mle_fold", f, a=a, c=self.scalar(f), batch=batch, n=n, out=out, **({"overlap": True} if overlap else {}))
+        return n
+
+    def g_mle_eval(self, f, small):
+        n, batch, stride = self.table_rows(small, 0, 5)
+        a = self.place(batch * stride)
+        self.maybe_plant(f, "mle_eval", self.spots(a, self.rnd, range(batch), stride, n))
+        self.emit("mle_eval", f, a=a, point=[self.scalar(f) for _ in range(n.bit_length() - 1)], batch=batch, n=n)
+        return n
+
+    def g_eq(self, f, small):
+        k = self.log_n(small)
+        self.emit("eq", f, point=[self.scalar(f) for _ in range(k)], scale=self.scalar(f) if self.rnd.random() < 0.5 else 1, out=self.place(1 << k))
+        return 1 << k
+
+    def g_round(self, f, small):
+        fold = self.scalar(f) if self.rnd.random() < 0.5 else None
+        n, batch, stride = self.table_rows(small, 1 if fold is None else 2, 4)
+        terms = [[self.scalar(f), [self.rnd.randrange(batch) for _ in range(self.rnd.randrange(1, 4 if n > 256 else 5))]] for _ in range(self.rnd.randrange(1, 4))]
+        a = self.place(batch * stride)
+        named = sorted({row for _, which in terms for row in which})
+        self.maybe_plant(f, "round", self.spots(a, self.rnd, named, stride, n))
+        self.emit("round", f, a=a, terms=terms, batch=batch, n=n, fold=fold)
+        return n
+
+    def g_matrix(self, f, small):
+        if len(self.mats[f]) == 3:
+            self.g_close(f, small, "mat")
+        slot = self.rnd.choice([s for s in range(3) if s not in self.mats[f]])
+        rows, cols = self.rnd.choice((1, 2) if small else (1, 2, 63, 64, 65, 255, 257)), self.rnd.choice((1, 2, 63, 64, 65, 256, 257))
+        row_ptr, col_idx = [0], []
+        long_row = self.rnd.randrange(rows) if self.rnd.random() < 0.4 and not small else -1  # one row that crosses tiles, even without the hook's small ones
+        for i in range(rows):
+            k = self.rnd.choice((70, 300, 1100)) if i == long_row else (0 if self.rnd.random() < 0.3 else self.rnd.randrange(1, 5))
+            col_idx += [self.rnd.randrange(cols) for _ in range(k)]
+            row_ptr.append(len(col_idx))
+        transpose = self.rnd.random() < 0.5
+        self.mats[f][slot] = (rows, cols, transpose, row_ptr, col_idx)
+        self.emit("matrix", f, slot=slot, rows=rows, cols=cols, row_ptr=row_ptr, col_idx=col_idx, vseed=self.rnd.randrange(1 << 30), transpose=transpose)
+        return None
+
+    def g_matvec(self, f, small, overlap=False):
+        if not self.mats[f] or (small and min(len(m[4]) for m in self.mats[f].values()) > SMALL):
+            self.g_matrix(f, small)
+        slot = min(self.mats[f], key=lambda s: len(self.mats[f][s][4])) if small else self.rnd.choice(sorted(self.mats[f]))
+        rows, cols, has_t, row_ptr, col_idx = self.mats[f][slot]
+        transpose = has_t and self.rnd.random() < 0.5
+        in_len, out_len = (rows, cols) if transpose else (cols, rows)
+        pad_to = self.rnd.choice((None, None, out_len + 3, 1 << (out_len - 1).bit_length()))
+        y_len = pad_to or out_len
+        x = self.place(in_len)
+        if overlap:  # (x and y lie apart: the same start is refused too)
+            out = self.shifted(x, y_len, 0)
+        else:
+            out = self.place(y_len, [x])
+            used = sorted({i for i in range(rows) if row_ptr[i + 1] > row_ptr[i]} if transpose else set(col_idx))
+            self.maybe_plant(f, "matvec", [x[0] + 2 * j for j in used[:1] + used[-1:]])
+        self.emit("matvec", f, slot=slot, x=x, out=out, transpose=transpose, pad_to=pad_to, **({"overlap": True} if overlap else {}))
+        return len(col_idx)  # (the work of a product is its entries)
+
+    def g_gate(self, f, small):
+        n, batch, stride = self.table_rows(small, 0, 5)
+        big = n > 256
+        terms = []
+        for _ in range(self.rnd.randrange(1, 3 if big else 6)):
+            rot = lambda: self.rnd.choice((0, 0, 1, -1, 2, -3, 5, 2 ** 31 - 1, -2 ** 31))
+            terms.append([self.scalar(f), [[self.rnd.randrange(batch), rot()] for _ in range(self.rnd.randrange(1, 4 if big else 9))]])
+        a = self.place(batch * stride)
+        scale = self.place(1 << self.rnd.randrange(n.bit_length())) if self.rnd.random() < 0.5 else None
+        out = self.place(n, [a] + ([scale] if scale else []))
+        named = sorted({fr[0] for _, factors in terms for fr in factors})
+        self.maybe_plant(f, "gate", self.spots(a, self.rnd, named, stride, n) + (self.spots(scale, self.rnd) if scale else []))
+        self.emit("gate", f, a=a, terms=terms, batch=batch, n=n, step=self.rnd.choice((1, 1, n, 1 << self.rnd.randrange(n.bit_length()))), scale=scale, out=out,
+                  accumulate=self.rnd.random() < 0.4)
+        return n
+
+    def coset_shift(self, f, log_n):
+        while True:
+            shift = self.rnd.randrange(2, self.r[f])
+            if pow(shift, 1 << log_n, self.r[f]) not in (0, 1):
+                return shift
+
+    def g_vanishing_inverse(self, f, small):
+        log_n, log_ext = self.rnd.randrange(0, 7), self.rnd.randrange(0, 4)
+        self.emit("vanishing_inverse", f, log_n=log_n, log_ext=log_ext, shift=self.coset_shift(f, log_n + log_ext), out=self.place(1 << log_ext))
+        return None
+
+    def g_quotient(self, f, small):
+        log_n, log_ext, batch = self.rnd.randrange(0, 5), self.rnd.randrange(0, 3), self.rnd.randrange(1, 4)
+        top = (1 << log_ext) + 1  # 2^log_ext >= D - 1
+        terms = [[self.scalar(f), [[self.rnd.randrange(batch), self.rnd.choice((0, 1, -1))] for _ in range(self.rnd.randrange(1, top + 1))]]
+                 for _ in range(self.rnd.randrange(1, 4))]
+        a = self.place(batch << log_n)
+        self.emit("quotient", f, a=a, terms=terms, batch=batch, log_n=log_n, log_ext=log_ext, shift=self.coset_shift(f, log_n + log_ext),
+                  out=self.place(1 << (log_n + log_ext), [a]))
+        return None
+
+    def g_table(self, f, small):
+        if len(self.tabs[f]) == 3:
+            self.g_close(f, small, "tab")
+        slot = self.rnd.choice([s for s in range(3) if s not in self.tabs[f]])
+        total = self.length(small, 1025)
+        t = self.place(total)
+        if self.fields[f] != "grumpkin" and self.rnd.random() < 0.3:  # repeated values: the powers of 1 or -1
+            self.emit("powers", f, g=self.rnd.choice((1, self.r[f] - 1)), n=total, scale=self.scalar(f), out=list(t))
+        n = total if self.rnd.random() < 0.7 else self.rnd.randrange(1, total + 1)
+        before = len(self.steps)
+        self.maybe_plant(f, "table", [t[0], t[0] + 2 * (n - 1)])
+        if len(self.steps) == before:  # (a planted value: no handle is made)
+            self.tabs[f][slot] = (n, self.mont[f], list(t))
+        self.emit("table", f, slot=slot, t=t, n=n)
+        return total
+
+    def g_mult(self, f, small):
+        if not self.tabs[f]:
+            self.g_table(f, small)
+            if not self.tabs[f]:
+                return None
+        slot = self.rnd.choice(sorted(self.tabs[f]))
+        t_n, form, src = self.tabs[f][slot]
+        n = self.length(small, 2051)
+        batch = self.batch(n + 1, 3)
+        stride = n + self.rnd.choice((0, 0, 2))
+        c = self.rnd.random()
+        if c < 0.45 and batch * stride <= src[1]:  # the table's own source: found, while nobody has written there since
+            v = [src[0], batch * stride]
+        elif c < 0.75:  # a window that lies partly on the source
+            v = [src[0] + 2 * (src[1] // 2), batch * stride]
+            half, _ = self.bank_of(src)
+            if (v[0] - half * (2 * HALF + 1)) // 2 + v[1] > HALF:
+                v = self.place(batch * stride)
+        else:
+            v = self.place(batch * stride)
+        out = self.place(t_n, [v, [v[0] + 2 * v[1] - 2, 1]])
+        if form == self.mont[f]:
+            self.maybe_plant(f, "mult", self.spots(v, self.rnd, range(batch), stride, n))
+        self.emit("mult", f, slot=slot, v=v, batch=batch, n=n, out=out, indices=self.rnd.random() < 0.6, counts=self.rnd.random() < 0.5)
+        return n
+
+    def g_format(self, f, small):
+        self.mont[f] = not self.mont[f] if self.rnd.random() < 0.8 else self.mont[f]
+        self.emit("format", f, mont=self.mont[f])
+
+    def g_hook(self, f, small):
+        names = sorted(HOOKS)
+        for name in self.rnd.sample(names, self.rnd.choice((1, 2, 2, 3))):  # (more than one at a time: no suite sets two hooks at once)
+            value = self.rnd.choice(HOOKS[name])
+            self.emit("hook", 0, name=name, value=value)
+
+    def g_close(self, f, small, what=None):
+        live = [(w, s) for w, d in (("mat", self.mats[f]), ("tab", self.tabs[f])) for s in sorted(d) if what in (None, w)]
+        if live:
+            w, s = self.rnd.choice(live)
+            del (self.mats if w == "mat" else self.tabs)[f][s]
+            self.emit("close", f, what=w, slot=s)
+
+    def g_stream(self, f, small):
+        self.side = not self.side
+        self.emit("stream", 0, side=self.side)
+
+    def g_overlap(self, f, small):
+        ok = [k for k in _OVERLAPS if self.serves(f, k)]
+        getattr(self, "g_" + self.rnd.choice(ok))(f, small, overlap=True)
+
+    def serves(self, f, kind):
+        return self.fields[f] != "grumpkin" or kind in GRUMPKIN_KINDS or kind not in LIBRARY
+
+    # ---- the program ---------------------------------------------------------------------------------------------------------------------
+    def run(self, count):
+        for f in range(len(self.fields)):
+            self.emit("init", f, seed=self.rnd.randrange(1 << 30))
+        while len(self.steps) < count:
+            if self.follow and self.rnd.random() < 0.6:  # a small step on the entry point that has just run a large one
+                f, kind = self.follow
+                small = True
+            else:
+                f = self.rnd.randrange(len(self.fields))
+                if self.prev_f is not None and len(self.fields) > 1 and self.rnd.random() < 0.6:  # the other field's turn
+                    f = 1 - self.prev_f
+                pool = [k for k in self.kinds if self.serves(f, k)]
+                kind = self.rnd.choices(pool, [_WEIGHT[k] for k in pool])[0]
+                small = False
+            self.follow = None
+            per_row = getattr(self, "g_" + kind)(f, small)
+            self.prev_f = f
+            if per_row is not None and per_row >= LARGE and not small:
+                self.follow = (f, kind)
+        return self.steps
+
+
+def program(seed, case, fields, kinds=None, steps=28):
+    """the steps of case `case` of seed `seed` over `fields` (one or two names): the same on every run and on every machine.  kinds: None, or the
+    step kinds to draw from (FUZZ_FR_KINDS)."""
+    fields = [fields] if isinstance(fields, str) else list(fields)
+    assert 1 <= len(fields) <= 2 and all(f in FIELD_R for f in fields)
+    rnd = random.Random("fr_program/%d/%d/%s" % (seed, case, ",".join(fields)))
+    return _Gen(rnd, fields, kinds).run(steps + len(fields))
