@@ -511,6 +511,141 @@ class FrLookup:
             pass
 
 
+_frhash_lib = None
+
+
+def frhash_lib():
+    """Load libmsm_frhash.so (in-tree; include/msm_frhash.h): Poseidon over the scalar field -- batch permutations, sponges, Merkle trees.  Raises
+    if it has not been built (msm-webgpu_amd/build.py builds it beside the other eight)."""
+    global _frhash_lib
+    if _frhash_lib is None:
+        so = _build.FRHASH_SO
+        if not os.path.exists(so):
+            raise ImportError("libmsm_frhash.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
+        L = C.CDLL(so)
+        vp, sz, i, u32, u32p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)
+        L.msm_frhash_abi_version.restype = i
+        L.msm_frhash_create.argtypes = [i, i, u32, u32, u32, u32, vp, vp, u32, C.POINTER(vp)]
+        L.msm_frhash_info.argtypes = [vp, u32p, u32p, u32p]
+        L.msm_frhash_destroy.argtypes = [vp]
+        L.msm_frhash_destroy.restype = None
+        L.msm_frhash_permute_device.argtypes = [vp, vp, vp, vp, sz, u32]
+        L.msm_frhash_permute.argtypes = [vp, vp, vp, sz, u32]
+        L.msm_frhash_hash_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, u32, u32, u32]
+        L.msm_frhash_hash.argtypes = [vp, vp, vp, sz, sz, sz, vp, u32, u32, u32]
+        L.msm_frhash_merkle_device.argtypes = [vp, vp, vp, vp, sz, vp, u32, u32, u32]
+        L.msm_frhash_merkle.argtypes = [vp, vp, vp, sz, vp, u32, u32, u32]
+        L.msm_frhash_release.argtypes = []
+        L.msm_frhash_release.restype = None
+        L.msm_frhash_test_tile.argtypes = [i]
+        _frhash_lib = L
+    return _frhash_lib
+
+
+lib_frhash = frhash_lib
+
+
+def frhash_test_tile(lanes=0):
+    """test hook msm_frhash_test_tile: only the first `lanes` lanes of a workgroup take a permutation (0: the design's 64)"""
+    _check(frhash_lib().msm_frhash_test_tile(int(lanes)), "msm_frhash_test_tile")
+
+
+def frhash_release():
+    """msm_frhash_release: free the hashing library's staging buffers (they come back with the next call); the handles stay"""
+    frhash_lib().msm_frhash_release()
+
+
+# the partial rounds of the alpha = 5, 128-bit column of the Poseidon paper's round-number table for R_F = 8, t = 2 .. 12 (circomlib's)
+POSEIDON_PARTIAL_ROUNDS = {2: 56, 3: 57, 4: 56, 5: 60, 6: 60, 7: 63, 8: 64, 9: 63, 10: 60, 11: 66, 12: 60}
+
+
+def poseidon_parameters(curve, t, full_rounds=8, partial_rounds=None):
+    """(round_constants, mds) of a Poseidon permutation of width t over a curve's scalar field, as lists of integers: (full_rounds +
+    partial_rounds) * t round constants and the t rows of the matrix, by the Poseidon paper's generator -- an 80-bit Grain LFSR seeded with
+    the field's bit length, t and the round numbers; round constants rejected where they are not below r; the matrix 1 / (x_i + y_j) of
+    2 t values reduced mod r.  partial_rounds=None: POSEIDON_PARTIAL_ROUNDS[t].  For BN254 these are circomlib's constants.  It does NOT
+    run the paper's subspace-trail checks on the matrix (the reference script redraws a matrix that fails them): the caller vouches for
+    parameters outside the published sets.  Pure Python, remembered."""
+    t, full_rounds = int(t), int(full_rounds)
+    if curve not in SCALAR_FIELDS:
+        raise ValueError("no scalar field for %s" % (curve,))
+    if not 2 <= t <= 12 or full_rounds % 2 or not 2 <= full_rounds <= 16:
+        raise ValueError("a permutation has 2 <= t <= 12 and an even 2 <= full_rounds <= 16")
+    partial_rounds = POSEIDON_PARTIAL_ROUNDS[t] if partial_rounds is None else int(partial_rounds)
+    if not 0 <= partial_rounds <= 128:
+        raise ValueError("a permutation has 0 .. 128 partial rounds")
+    rc, mds = _poseidon_parameters(SCALAR_FIELDS[curve], t, full_rounds, partial_rounds)
+    return list(rc), [list(row) for row in mds]
+
+
+@functools.lru_cache(maxsize=None)
+def _poseidon_parameters(r, t, full_rounds, partial_rounds):
+    n = r.bit_length()
+    state = 0  # bit 79 is b[0], the oldest
+    for value, width in ((1, 2), (0, 4), (n, 12), (t, 12), (full_rounds, 10), (partial_rounds, 10), ((1 << 30) - 1, 30)):
+        state = state << width | value
+
+    def step():
+        nonlocal state
+        b = (state >> 17 ^ state >> 28 ^ state >> 41 ^ state >> 56 ^ state >> 66 ^ state >> 79) & 1  # b[62] ^ b[51] ^ b[38] ^ b[23] ^ b[13] ^ b[0]
+        state = (state << 1 | b) & ((1 << 80) - 1)
+        return b
+
+    for _ in range(160):
+        step()
+
+    def draw():
+        v = got = 0
+        while got < n:
+            if step():  # of every pair, the second bit where the first is 1
+                v = v << 1 | step()
+                got += 1
+            else:
+                step()
+        return v
+
+    rc = []
+    while len(rc) < (full_rounds + partial_rounds) * t:
+        v = draw()
+        if v < r:
+            rc.append(v)
+    while True:
+        xy = [draw() % r for _ in range(2 * t)]
+        if len(set(xy)) == 2 * t:
+            break
+    return tuple(rc), tuple(tuple(pow(xy[i] + xy[t + j], r - 2, r) for j in range(t)) for i in range(t))
+
+
+class FrHash:
+    """A Poseidon permutation over a scalar field (msm_frhash_create, include/msm_frhash.h): MsmContext.poseidon makes it,
+    MsmContext.scalars_permute, scalars_hash, merkle_tree and merkle_path use it.  t, full_rounds, partial_rounds: its shape; arity = t - 1;
+    capacity, capacity_at, out_at: the sponge's convention, remembered for the calls.  close() frees it; so does collecting it or leaving a
+    `with` block."""
+
+    def __init__(self, handle, curve, device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at):
+        self._h, self.curve, self.device = handle, curve, device
+        self.t, self.full_rounds, self.partial_rounds, self.arity = t, full_rounds, partial_rounds, t - 1
+        self.capacity, self.capacity_at, self.out_at = capacity, capacity_at, out_at
+
+    def close(self):
+        if self._h:
+            frhash_lib().msm_frhash_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FrMatrix:
     """A sparse matrix over a scalar field, resident on one device (msm_frmat_create, include/msm_frmat.h): MsmContext.scalars_matrix makes it,
     MsmContext.scalars_matvec multiplies by it.  close() frees it; so does collecting it."""
@@ -1869,6 +2004,195 @@ class MsmContext:
         prod = self.scalars_gate(pair, [(1, (0, 1))], batch=2)  # (zero behind the table: m is padded with zeros)
         sums = [total(v).to_bytes(32, "little") for v in (sum_rows, prod)]
         return sum_rows[:n].clone(), prod[:n_t].clone(), sums[0], sums[1]
+
+    # -- algebraic hashing over the scalar field (libmsm_frhash.so): Poseidon permutations, sponges and Merkle trees on the stream of the
+    # commitments
+    FRHASH_MONT256, FRHASH_MAX_WIDTH, FRHASH_MAX_FULL_ROUNDS, FRHASH_MAX_PARTIAL_ROUNDS = 2, 12, 16, 128  # MSM_FRHASH_MONT256, MSM_FRHASH_MAX_WIDTH, ..
+    FRHASH_MAX_ELEMENTS, FRHASH_MAX_LEVELS = 1 << 26, 64  # MSM_FRHASH_MAX_ELEMENTS, MSM_FRHASH_MAX_LEVELS
+
+    def poseidon(self, t=3, full_rounds=8, partial_rounds=None, round_constants=None, mds=None, capacity=0, capacity_at=0, out_at=0):
+        """A Poseidon permutation of width t over this context's scalar field (a G2 context takes its G1's) -> FrHash (msm_frhash_create,
+        include/msm_frhash.h).  round_constants ((full_rounds + partial_rounds) * t integers) and mds (t rows of t integers) default to
+        poseidon_parameters(curve, t, full_rounds, partial_rounds); give both or neither.  capacity, capacity_at, out_at: the sponge's
+        convention, which the handle remembers for scalars_hash and merkle_tree -- (0, 0, 0) is circomlib's poseidon(inputs), (L * 2^64,
+        t - 1, 0) halo2's ConstantLength<L>, (2^arity - 1, 0, 1) neptune's.  No device is touched: the tables go there with the first call."""
+        r = self._frmle_field("poseidon")
+        t, full_rounds = int(t), int(full_rounds)
+        if (round_constants is None) != (mds is None):
+            raise ValueError("give round_constants and mds, or neither")
+        if not 2 <= t <= self.FRHASH_MAX_WIDTH or full_rounds % 2 or not 2 <= full_rounds <= self.FRHASH_MAX_FULL_ROUNDS:
+            raise ValueError("a permutation has 2 <= t <= 12 and an even 2 <= full_rounds <= 16")
+        if round_constants is None:
+            partial_rounds = POSEIDON_PARTIAL_ROUNDS[t] if partial_rounds is None else int(partial_rounds)
+            round_constants, mds = poseidon_parameters(self.curve, t, full_rounds, partial_rounds)
+        elif partial_rounds is None:
+            raise ValueError("parameters of the caller's come with their partial_rounds")
+        partial_rounds = int(partial_rounds)
+        if not 0 <= partial_rounds <= self.FRHASH_MAX_PARTIAL_ROUNDS:
+            raise ValueError("a permutation has 0 .. 128 partial rounds")
+        round_constants = [int(c) for c in round_constants]
+        mds = [[int(c) for c in row] for row in mds]
+        if len(round_constants) != (full_rounds + partial_rounds) * t or len(mds) != t or any(len(row) != t for row in mds):
+            raise ValueError("round_constants holds (full_rounds + partial_rounds) * t integers and mds t rows of t")
+        if any(not 0 <= c < r for c in round_constants) or any(not 0 <= c < r for row in mds for c in row):
+            raise ValueError("round constants and matrix entries must lie in [0, r)")
+        capacity_at, out_at = int(capacity_at), int(out_at)
+        if not 0 <= capacity_at < t or not 0 <= out_at < t:
+            raise ValueError("capacity_at and out_at must lie in [0, t)")
+        capacity = int.from_bytes(self._frpoly_const(capacity, r, "capacity"), "little")
+        rc_b = b"".join(c.to_bytes(32, "little") for c in round_constants)
+        m_b = b"".join(c.to_bytes(32, "little") for row in mds for c in row)
+        h = C.c_void_p()
+        _check(frhash_lib().msm_frhash_create(self.curve_id, self.device, t, full_rounds, partial_rounds, 5, C.cast(C.c_char_p(rc_b), C.c_void_p),
+                                              C.cast(C.c_char_p(m_b), C.c_void_p), 0, C.byref(h)), "msm_frhash_create")
+        return FrHash(h, self.curve, self.device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at)
+
+    def _frhash_handle(self, h):
+        if not isinstance(h, FrHash) or not h._h:
+            raise TypeError("h must be an open FrHash (poseidon)")
+        if SCALAR_FIELDS[h.curve] != SCALAR_FIELDS.get(self.curve) or h.device != self.device:
+            raise ValueError("the permutation belongs to the scalar field of %s on device %d" % (h.curve, h.device))
+        self._frmle_field("hashing")
+        return self.FRHASH_MONT256 if getattr(self, "scalar_mont256", False) else 0
+
+    def scalars_permute(self, h, state, out=None):
+        """out = the permutation of every state (msm_frhash_permute_device): state is a CUDA uint8 tensor of n x t x 32 bytes in this
+        context's scalar format -- state i is scalars [i t, (i + 1) t) --, or host bytes of the same layout, which return bytes.  out: a
+        contiguous CUDA uint8 tensor of the same size, `state` itself (in place) or one that does not overlap it (a new one by default).  An
+        element that is not below r raises MsmHipError (code -4)."""
+        flags = self._frhash_handle(h)
+        ts, bs, total = self._frvec_vector(state, "state")
+        if total < h.t or total % h.t or total > self.FRHASH_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not 1 .. 2^26 / t states of t = %d" % (total, h.t))
+        n = total // h.t
+        if ts is None:
+            if out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            buf = C.create_string_buffer(32 * total)
+            _check(frhash_lib().msm_frhash_permute(h._h, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(bs), C.c_void_p), n, flags), "msm_frhash_permute")
+            return buf.raw
+        if out is None:
+            out = torch.empty((n, h.t, 32), dtype=torch.uint8, device=ts.device)
+        else:
+            self._frvec_out(out, ts, total, True)
+            if out.data_ptr() != ts.data_ptr() and out.data_ptr() < ts.data_ptr() + 32 * total and ts.data_ptr() < out.data_ptr() + 32 * total:
+                raise ValueError("out is state itself or does not overlap it")
+        self._order_after_torch(ts)
+        _check(frhash_lib().msm_frhash_permute_device(h._h, lib().msm_hip_stream(self._h), out.data_ptr(), ts.data_ptr(), n, flags), "msm_frhash_permute_device")
+        return out
+
+    def scalars_hash(self, h, a, length, batch=1, stride=None, out=None):
+        """out[row] = the sponge of the first `length` scalars of row `row` of a (msm_frhash_hash_device), rate t - 1, under the handle's
+        capacity convention; nothing is padded.  a: a CUDA uint8 tensor of 32-byte scalars in this context's scalar format holding `batch`
+        rows `stride` scalars apart (default: scalars / batch), of which the scalars behind `length` are not read; or host bytes of the same
+        layout, which return bytes.  out: a contiguous CUDA uint8 tensor of batch x 32 bytes that does not overlap a."""
+        flags = self._frhash_handle(h)
+        ta, ba, total = self._frvec_vector(a, "a")
+        batch, length = int(batch), int(length)
+        if batch < 1 or total < 1 or total > self.FRHASH_MAX_ELEMENTS:
+            raise ValueError("%d scalars are not %d rows of 1 .. 2^26 / batch scalars" % (total, batch))
+        if stride is None:
+            if total % batch:
+                raise ValueError("%d scalars are not %d rows" % (total, batch))
+            stride = total // batch
+        stride = int(stride)
+        if not 1 <= length <= stride or (batch - 1) * stride + length > total:
+            raise ValueError("%d rows of %d scalars, %d apart, do not fit the %d scalars given" % (batch, length, stride, total))
+        cap = h.capacity.to_bytes(32, "little")
+        cap_p = C.cast(C.c_char_p(cap), C.c_void_p)
+        if ta is None:
+            if out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            buf = C.create_string_buffer(32 * batch)
+            _check(frhash_lib().msm_frhash_hash(h._h, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(ba), C.c_void_p), batch, length, stride, cap_p, h.capacity_at, h.out_at,
+                                                flags), "msm_frhash_hash")
+            return buf.raw
+        if out is None:
+            out = torch.empty((batch, 32), dtype=torch.uint8, device=ta.device)
+        else:
+            self._frvec_out(out, ta, batch, True)
+            if out.data_ptr() < ta.data_ptr() + 32 * total and ta.data_ptr() < out.data_ptr() + 32 * batch:
+                raise ValueError("out overlaps a")
+        self._order_after_torch(ta)
+        _check(frhash_lib().msm_frhash_hash_device(h._h, lib().msm_hip_stream(self._h), out.data_ptr(), ta.data_ptr(), batch, length, stride, cap_p, h.capacity_at,
+                                                   h.out_at, flags), "msm_frhash_hash_device")
+        return out
+
+    def _merkle_levels(self, h, n_leaves):
+        """the number of nodes of every level above the leaves, the lowest first"""
+        a = h.arity
+        if a == 1:
+            if not 1 <= n_leaves <= self.FRHASH_MAX_LEVELS:
+                raise ValueError("a tree of arity 1 is a chain of 1 .. %d levels over one leaf" % self.FRHASH_MAX_LEVELS)
+            return [1] * n_leaves
+        levels, n = [], n_leaves
+        if n < a or n > self.FRHASH_MAX_ELEMENTS:
+            raise ValueError("a tree of arity %d has %d^k leaves, k >= 1, at most 2^26, not %d" % (a, a, n_leaves))
+        while n > 1:
+            if n % a:
+                raise ValueError("a tree of arity %d has %d^k leaves, k >= 1, not %d" % (a, a, n_leaves))
+            n //= a
+            levels.append(n)
+        return levels
+
+    def merkle_tree(self, h, leaves, out=None, levels=None):
+        """The nodes above the leaves of the tree of arity t - 1 (msm_frhash_merkle_device): the level above the leaves first, the root
+        last -- (n - 1) / (arity - 1) scalars for n = arity^k leaves, every node the sponge of the `arity` scalars below it under the handle's
+        capacity convention.  leaves: a CUDA uint8 tensor of n x 32 bytes in this context's scalar format, or host bytes (which return
+        bytes).  At arity 1 (t = 2) the tree is a chain over ONE leaf and `levels` (1 .. 64) says how long.  out: a contiguous CUDA uint8
+        tensor of that many x 32 bytes that does not overlap the leaves.  One launch per level, on this context's stream."""
+        flags = self._frhash_handle(h)
+        tl, bl, n = self._frvec_vector(leaves, "leaves")
+        if h.arity == 1:
+            if n != 1 or levels is None:
+                raise ValueError("at arity 1 the tree is a chain over one leaf: give levels")
+            n = int(levels)
+        elif levels is not None:
+            raise ValueError("levels is for arity 1; the leaves say how deep a wider tree is")
+        count = sum(self._merkle_levels(h, n))
+        cap = h.capacity.to_bytes(32, "little")
+        cap_p = C.cast(C.c_char_p(cap), C.c_void_p)
+        if tl is None:
+            if out is not None:
+                raise TypeError("out is for device vectors; host bytes return bytes")
+            buf = C.create_string_buffer(32 * count)
+            _check(frhash_lib().msm_frhash_merkle(h._h, C.cast(buf, C.c_void_p), C.cast(C.c_char_p(bl), C.c_void_p), n, cap_p, h.capacity_at, h.out_at, flags),
+                   "msm_frhash_merkle")
+            return buf.raw
+        if out is None:
+            out = torch.empty((count, 32), dtype=torch.uint8, device=tl.device)
+        else:
+            self._frvec_out(out, tl, count, True)
+            if out.data_ptr() < tl.data_ptr() + tl.numel() and tl.data_ptr() < out.data_ptr() + 32 * count:
+                raise ValueError("out overlaps the leaves")
+        self._order_after_torch(tl)
+        _check(frhash_lib().msm_frhash_merkle_device(h._h, lib().msm_hip_stream(self._h), out.data_ptr(), tl.data_ptr(), n, cap_p, h.capacity_at, h.out_at, flags),
+               "msm_frhash_merkle_device")
+        return out
+
+    def merkle_path(self, h, leaves, nodes, index):
+        """The siblings of leaf `index` on its way to the root: a tensor of k x (arity - 1) x 32 bytes, level by level from the leaves up,
+        each level's siblings in index order -- with plain torch indexing, nothing is hashed.  leaves and nodes: as merkle_tree took and
+        returned them (CUDA tensors, or bytes, which return a list of k lists of 32-byte strings)."""
+        if not isinstance(h, FrHash):
+            raise TypeError("h must be an FrHash (poseidon)")
+        a, index = h.arity, int(index)
+        on_device = isinstance(leaves, torch.Tensor)
+        lv = leaves.reshape(-1, 32) if on_device else [bytes(leaves)[i:i + 32] for i in range(0, len(bytes(leaves)), 32)]
+        nd = nodes.reshape(-1, 32) if on_device else [bytes(nodes)[i:i + 32] for i in range(0, len(bytes(nodes)), 32)]
+        n = len(lv)
+        counts = self._merkle_levels(h, len(nd) if a == 1 else n)
+        if sum(counts) != len(nd) or not 0 <= index < n:
+            raise ValueError("nodes is not the tree over these leaves, or index is not a leaf")
+        rows, below, first_node = [], lv, 0
+        for count in counts:
+            first = index - index % a
+            rows.append([below[first + p] for p in range(a) if first + p != index])
+            index //= a
+            below, first_node = nd[first_node:first_node + count], first_node + count
+        if on_device:
+            return torch.stack([torch.stack(row) if row else lv.new_empty((0, 32)) for row in rows]) if rows else lv.new_empty((0, a - 1, 32))
+        return rows
 
     def msm_batch(self, scalars_dev, n):
         """`batch` MSMs over the resident bases: scalars_dev is a CUDA uint8 tensor of batch x n x 32 bytes -- batch x n x width bytes under

@@ -1,4 +1,4 @@
-"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so, libmsm_frmle.so, libmsm_frmat.so, libmsm_frgate.so and libmsm_frlook.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so, libmsm_frmle.so, libmsm_frmat.so, libmsm_frgate.so, libmsm_frlook.so and libmsm_frhash.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import os
 import subprocess
 
@@ -55,6 +55,13 @@ FRLOOK_UNITS = ["frlook_bn254.hip", "frlook_grumpkin.hip", "frlook_pallas.hip", 
 FRLOOK_SOURCES = FRLOOK_UNITS + ["frlook_unit.h", "frlook_kernels.h", "frlook_host.h", "frlook_plan.h", "host_fr.h", "fr_bn254_constants.h",
                                  "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
 FRLOOK_HEADERS = [os.path.join(HERE, "..", "include", "msm_frlook.h"), HEADER]
+# libmsm_frhash.so (include/msm_frhash.h): Poseidon over the scalar field -- batch permutations, sponges and Merkle trees --, the ninth library;
+# a unit for every scalar field, Grumpkin's included
+FRHASH_SO = os.path.join(HERE, "libmsm_frhash.so")
+FRHASH_UNITS = ["frhash_bn254.hip", "frhash_grumpkin.hip", "frhash_pallas.hip", "frhash_vesta.hip", "frhash_bls12_381.hip"]
+FRHASH_SOURCES = FRHASH_UNITS + ["frhash_unit.h", "frhash_kernels.h", "frhash_host.h", "frhash_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
+                                 "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
+FRHASH_HEADERS = [os.path.join(HERE, "..", "include", "msm_frhash.h"), HEADER]
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
@@ -337,6 +344,44 @@ def frlook_device_asm_is_current():
     return all(os.path.getmtime(f) >= newest for f in frlook_device_asm_paths())
 
 
+def frhash_device_asm_paths():
+    """The device assembly of libmsm_frhash.so's units, as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRHASH_UNITS]
+
+
+def frhash_build_stamp():
+    """build_stamp() for libmsm_frhash.so: the compile flags and the contents of its own sources"""
+    import hashlib
+
+    h = hashlib.sha256()
+    h.update("\0".join(compile_flags()).encode())
+    for path in [os.path.join(CSRC, f) for f in sorted(FRHASH_SOURCES)] + FRHASH_HEADERS:
+        if os.path.exists(path):
+            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
+            with open(path, "rb") as fh:
+                h.update(fh.read())
+    return h.hexdigest()
+
+
+def frhash_needs_build():
+    """libmsm_frhash.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
+    if os.environ.get("MSM_HIP_SO"):
+        return False
+    try:
+        with open(FRHASH_SO + ".stamp") as f:
+            return not os.path.exists(FRHASH_SO) or f.read().strip() != frhash_build_stamp()
+    except OSError:
+        return True
+
+
+def frhash_device_asm_is_current():
+    """device_asm_is_current() for libmsm_frhash.so's units"""
+    if frhash_needs_build() or not all(os.path.exists(f) for f in frhash_device_asm_paths()):
+        return False
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRHASH_SOURCES if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in frhash_device_asm_paths())
+
+
 def build_stamp():
     """what the library on disk must have been built FROM to be the product: a hash over the compile flags (the environment switches of the
     diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source.  Written next to the
@@ -412,7 +457,7 @@ def compile_flags():
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
     from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so, msm-webgpu_amd/libmsm_frpoly.so,
-    msm-webgpu_amd/libmsm_frmle.so, msm-webgpu_amd/libmsm_frmat.so, msm-webgpu_amd/libmsm_frgate.so and msm-webgpu_amd/libmsm_frlook.so.  Each library is rebuilt only when its own sources or the flags changed."""
+    msm-webgpu_amd/libmsm_frmle.so, msm-webgpu_amd/libmsm_frmat.so, msm-webgpu_amd/libmsm_frgate.so, msm-webgpu_amd/libmsm_frlook.so and msm-webgpu_amd/libmsm_frhash.so.  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
     do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
     do_frpoly = (force and not os.environ.get("MSM_HIP_SO")) or frpoly_needs_build()
@@ -420,7 +465,8 @@ def build(force=False, verbose=False):
     do_frmat = (force and not os.environ.get("MSM_HIP_SO")) or frmat_needs_build()
     do_frgate = (force and not os.environ.get("MSM_HIP_SO")) or frgate_needs_build()
     do_frlook = (force and not os.environ.get("MSM_HIP_SO")) or frlook_needs_build()
-    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle and not do_frmat and not do_frgate and not do_frlook:
+    do_frhash = (force and not os.environ.get("MSM_HIP_SO")) or frhash_needs_build()
+    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle and not do_frmat and not do_frgate and not do_frlook and not do_frhash:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -448,8 +494,8 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of all eight libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else []) + (FRMAT_UNITS if do_frmat else []) + (FRGATE_UNITS if do_frgate else []) + (FRLOOK_UNITS if do_frlook else [])
+    # one pool for the units of all nine libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else []) + (FRMAT_UNITS if do_frmat else []) + (FRGATE_UNITS if do_frgate else []) + (FRLOOK_UNITS if do_frlook else []) + (FRHASH_UNITS if do_frhash else [])
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
@@ -484,6 +530,10 @@ def build(force=False, verbose=False):
         link([objs[u] for u in FRLOOK_UNITS], FRLOOK_SO)
         with open(FRLOOK_SO + ".stamp", "w") as f:
             f.write(frlook_build_stamp() + "\n")
+    if do_frhash:
+        link([objs[u] for u in FRHASH_UNITS], FRHASH_SO)
+        with open(FRHASH_SO + ".stamp", "w") as f:
+            f.write(frhash_build_stamp() + "\n")
     return SO
 
 

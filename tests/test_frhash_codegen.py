@@ -1,0 +1,112 @@
+"""The code-generation gates (tools/check_long_branch_hazard.py, tools/check_machine_verifier.py) over the five units of libmsm_frhash.so, which
+are not among the other eight libraries' units; every unit's kernels sit in the unit's own namespace, they use no scratch memory and spill
+nothing, their LDS and vector registers are what DESIGN.md section 4.24 states, and the libraries on disk are the current sources'.  Resource
+metadata only."""
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import check_long_branch_hazard as chk  # noqa: E402
+
+KERNELS = ("k_frhash_permute", "k_frhash_hash")
+
+
+def _units():
+    import importlib
+
+    return list(importlib.import_module("msm_webgpu_amd.build").FRHASH_UNITS)
+
+
+def _stated():
+    """kernel -> (VGPRs, LDS bytes) from the table of DESIGN.md section 4.24"""
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        design = f.read()
+    section = design[design.index("### 4.24"):]
+    section = section[:section.index("\n## ")]
+    rows = dict((k, (int(v), int(lds))) for k, v, lds in re.findall(r"^\| `(k_frhash_\w+)` \| (\d+) \| \d+ \| (\d+) B \| 0 B \| 0 \|$", section, flags=re.M))
+    assert sorted(rows) == sorted(KERNELS), rows
+    return rows
+
+
+def test_frhash_units_have_no_long_branch_hazard(built):
+    paths = chk.compile_to_asm([], units=_units())
+    assert len(paths) == 5 and all("frhash_" in os.path.basename(p) for p in paths)
+    for path in paths:
+        long_branches, found, live = chk.check_file(path)
+        assert found == [] and live == [], (path, found, live)
+
+
+def test_frhash_units_pass_the_machine_verifier():
+    import check_machine_verifier as mv
+
+    reports = mv.check(units=_units())
+    assert sorted(reports) == sorted(_units())
+    for unit, found in reports.items():
+        assert found == [], (unit, found)
+
+
+def test_each_unit_holds_its_kernels_in_its_own_namespace_without_scratch(built):
+    stated = _stated()
+    for path in chk.compile_to_asm([], units=_units()):
+        with open(path) as f:
+            text = f.read()
+        names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", text, flags=re.M)
+        field = "frh_" + os.path.basename(path).split("-hip-")[0][len("frhash_"):]
+        assert len(names) == len(KERNELS), (path, names)
+        for k in KERNELS:
+            mine = [n for n in names if ("%d%s" % (len(field), field)) in n and ("%d%s" % (len(k), k)) in n]
+            assert len(mine) == 1, (path, k, names)
+        # the kernel descriptors and the metadata: no private segment, nothing spilled, no dynamic stack
+        assert re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.private_segment_fixed_size:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert re.findall(r"\.vgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS) and re.findall(r"\.sgpr_spill_count:\s+(\d+)", text) == ["0"] * len(KERNELS), path
+        assert not re.search(r"\.uses_dynamic_stack:\s+true", text), path
+        # LDS (fixed: none -- a lane's slab is sized by t and given with the launch) and vector registers, kernel by kernel, as DESIGN.md section 4.24 states them
+        meta = re.findall(r"\.group_segment_fixed_size:\s+(\d+).*?\.symbol:\s+(\S+?)\.kd.*?\.vgpr_count:\s+(\d+)", text, flags=re.S)
+        assert len(meta) == len(KERNELS), path
+        for lds, symbol, vgprs in meta:
+            k = [k for k in KERNELS if ("%d%s" % (len(k), k)) in symbol]
+            assert len(k) == 1 and (int(vgprs), int(lds)) == stated[k[0]], (path, symbol, vgprs, lds, stated)
+
+
+def test_the_state_lives_in_lds_and_the_tables_come_through_scalar_loads(built):
+    """a lane's state is read and written with LDS instructions -- no flat or scratch access stands in for them --, and the table of constants,
+    whose address no lane changes, is read with scalar loads"""
+    for path in chk.compile_to_asm([], units=_units()):
+        with open(path) as f:
+            text = f.read()
+        assert len(re.findall(r"^\s*ds_(?:read|load)\w*_b32\b", text, flags=re.M)) >= 9 and len(re.findall(r"^\s*ds_(?:write|store)\w*_b32\b", text, flags=re.M)) >= 9, path
+        assert not re.search(r"^\s*(?:flat|scratch)_(?:load|store)", text, flags=re.M), path
+        assert len(re.findall(r"^\s*s_load_dwordx8\b", text, flags=re.M)) >= 4, path
+
+
+def test_library_on_disk_was_built_from_the_current_sources(built):
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert os.path.exists(b.FRHASH_SO) and not b.frhash_needs_build()
+    assert b.frhash_device_asm_is_current()
+    for needs in (b.needs_build, b.fr_needs_build, b.frvec_needs_build, b.frpoly_needs_build, b.frmle_needs_build, b.frmat_needs_build, b.frgate_needs_build,
+                  b.frlook_needs_build):
+        assert not needs()  # the other eight stamps stay current
+
+
+def test_the_other_libraries_do_not_depend_on_this_one():
+    """libmsm_frhash.so has its own sources and stamp: none of its files is among the other libraries' -- but for the field arithmetic they all
+    share --, so adding it left their stamps current"""
+    import importlib
+
+    b = importlib.import_module("msm_webgpu_amd.build")
+    assert sorted(b.FRHASH_UNITS) == ["frhash_bls12_381.hip", "frhash_bn254.hip", "frhash_grumpkin.hip", "frhash_pallas.hip", "frhash_vesta.hip"]
+    for other in (b.TRANSLATION_UNITS, b.FR_UNITS, b.FRVEC_UNITS, b.FRPOLY_UNITS, b.FRMLE_UNITS, b.FRMAT_UNITS, b.FRGATE_UNITS, b.FRLOOK_UNITS):
+        assert not set(other) & set(b.FRHASH_UNITS)
+    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES + b.FRMAT_SOURCES + b.FRGATE_SOURCES + b.FRLOOK_SOURCES
+    assert not any(f.startswith("frhash_") for f in others)
+    shared = {"fq29.h", "fq29_asm.h", "host_fr.h", "fr_bn254_constants.h", "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"}
+    assert set(b.FRHASH_SOURCES) & set(others) == shared
+    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_", "frmat_", "frgate_", "frlook_", "fq2.")) for f in b.FRHASH_SOURCES)
+    for u in b.FRHASH_SOURCES:
+        assert os.path.exists(os.path.join(b.CSRC, u)), u

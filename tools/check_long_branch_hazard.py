@@ -226,7 +226,7 @@ def compile_to_asm(extra, units=None):
     current (msm-webgpu_amd/build.py keeps the compiler's intermediate files), else fresh -S compiles (minutes).  units: None -- the
     units of libmsm_hip.so; a list of unit names otherwise (libmsm_fr.so's: build.FR_UNITS; libmsm_frvec.so's: build.FRVEC_UNITS; libmsm_frpoly.so's: build.FRPOLY_UNITS;
     libmsm_frmle.so's: build.FRMLE_UNITS; libmsm_frmat.so's: build.FRMAT_UNITS; libmsm_frgate.so's: build.FRGATE_UNITS;
-    libmsm_frlook.so's: build.FRLOOK_UNITS)."""
+    libmsm_frlook.so's: build.FRLOOK_UNITS; libmsm_frhash.so's: build.FRHASH_UNITS)."""
     sys.path.insert(0, os.path.join(ROOT, "msm-webgpu_amd"))
     import build as _b
 
@@ -246,6 +246,8 @@ def compile_to_asm(extra, units=None):
         return [f for u, f in zip(_b.FRGATE_UNITS, _b.frgate_device_asm_paths()) if u in units]
     if not extra and units is not None and set(units) <= set(_b.FRLOOK_UNITS) and _b.frlook_device_asm_is_current():
         return [f for u, f in zip(_b.FRLOOK_UNITS, _b.frlook_device_asm_paths()) if u in units]
+    if not extra and units is not None and set(units) <= set(_b.FRHASH_UNITS) and _b.frhash_device_asm_is_current():
+        return [f for u, f in zip(_b.FRHASH_UNITS, _b.frhash_device_asm_paths()) if u in units]
     outdir = tempfile.mkdtemp(prefix="msm_hip_asm_")
     outs = []
     for unit in (_b.TRANSLATION_UNITS if units is None else units):

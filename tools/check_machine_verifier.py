@@ -33,7 +33,7 @@ CACHE = os.path.join(ROOT, "build", "machine_verifier_cache.json")
 
 
 def sources_hash(flags, units=()):
-    """hash of the flags and of the sources the units are built from (libmsm_fr.so's, libmsm_frvec.so's, libmsm_frpoly.so's, libmsm_frmle.so's, libmsm_frmat.so's, libmsm_frgate.so's and libmsm_frlook.so's units have source lists of
+    """hash of the flags and of the sources the units are built from (libmsm_fr.so's, libmsm_frvec.so's, libmsm_frpoly.so's, libmsm_frmle.so's, libmsm_frmat.so's, libmsm_frgate.so's, libmsm_frlook.so's and libmsm_frhash.so's units have source lists of
     their own)"""
     h = hashlib.sha256(" ".join(flags).encode())
     if units and set(units) <= set(_b.FR_UNITS):
@@ -50,6 +50,8 @@ def sources_hash(flags, units=()):
         sources = _b.FRGATE_SOURCES
     elif units and set(units) <= set(_b.FRLOOK_UNITS):
         sources = _b.FRLOOK_SOURCES
+    elif units and set(units) <= set(_b.FRHASH_UNITS):
+        sources = _b.FRHASH_SOURCES
     else:
         sources = _b.SOURCES
     for name in sorted(sources):
