@@ -179,27 +179,39 @@ def lib():
     return _lib
 
 
-_fr_lib = None
+_fr_libs = {}  # the scalar-field libraries loaded so far, by their name in msm-webgpu_amd/build.py's FR_LIBRARIES
+
+
+def _load_fr(name, what):
+    """Load libmsm_<name>.so (in-tree), once.  what: the argument types of its functions, by their name behind msm_<name>_ (release and destroy
+    return nothing, the others an int).  Raises if the library has not been built -- there is no fallback path."""
+    if name not in _fr_libs:
+        so = _build.FR_LIBRARIES[name].so
+        if not os.path.exists(so):
+            raise ImportError("libmsm_%s.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % (name, so))
+        L = C.CDLL(so)
+        getattr(L, "msm_%s_abi_version" % name).restype = C.c_int
+        for fn, argtypes in what.items():
+            f = getattr(L, "msm_%s_%s" % (name, fn))
+            f.argtypes = argtypes
+            if fn in ("release", "destroy"):
+                f.restype = None
+        _fr_libs[name] = L
+    return _fr_libs[name]
 
 
 def fr_lib():
     """Load libmsm_fr.so (in-tree; include/msm_fr.h): the scalar-field NTT.  Raises if it has not been built -- there is no fallback path."""
-    global _fr_lib
-    if _fr_lib is None:
-        so = _build.FR_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_fr.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, u8p, sz, i = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int
-        L.msm_fr_abi_version.restype = i
-        L.msm_fr_ntt_device.argtypes = [i, i, vp, vp, i, sz, u8p, u8p, u8p, C.c_uint32]
-        L.msm_fr_ntt.argtypes = [i, i, vp, i, sz, u8p, u8p, u8p, C.c_uint32]
-        L.msm_fr_release.argtypes = []
-        L.msm_fr_release.restype = None
-        L.msm_fr_test_pass_bits.argtypes = [i]
-        L.msm_fr_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
-        _fr_lib = L
-    return _fr_lib
+    if "fr" in _fr_libs:
+        return _fr_libs["fr"]
+    vp, u8p, sz, i = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int
+    return _load_fr("fr", {
+        "ntt_device": [i, i, vp, vp, i, sz, u8p, u8p, u8p, C.c_uint32],
+        "ntt": [i, i, vp, i, sz, u8p, u8p, u8p, C.c_uint32],
+        "release": [],
+        "test_pass_bits": [i],
+        "test_last": [C.POINTER(i), C.POINTER(i)],
+    })
 
 
 def fr_test_pass_bits(bits=0):
@@ -219,32 +231,23 @@ def fr_release():
     fr_lib().msm_fr_release()
 
 
-_frvec_lib = None
-
-
 def frvec_lib():
     """Load libmsm_frvec.so (in-tree; include/msm_frvec.h): vector arithmetic over the scalar field.  Raises if it has not been built -- there is no
     fallback path."""
-    global _frvec_lib
-    if _frvec_lib is None:
-        so = _build.FRVEC_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frvec.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
-        L.msm_frvec_abi_version.restype = i
-        L.msm_frvec_map_device.argtypes = [i, i, vp, vp, vp, vp, vp, sz, i, u8p, u8p, u32]
-        L.msm_frvec_inverse_device.argtypes = [i, i, vp, vp, vp, sz, u32]
-        L.msm_frvec_scan_device.argtypes = [i, i, vp, vp, vp, sz, sz, i, u32, vp]
-        L.msm_frvec_map.argtypes = [i, i, vp, vp, vp, vp, sz, i, u8p, u8p, u32]
-        L.msm_frvec_inverse.argtypes = [i, i, vp, vp, sz, u32]
-        L.msm_frvec_scan.argtypes = [i, i, vp, vp, sz, sz, i, u32, vp]
-        L.msm_frvec_release.argtypes = []
-        L.msm_frvec_release.restype = None
-        L.msm_frvec_test_tile.argtypes = [i]
-        L.msm_frvec_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
-        _frvec_lib = L
-    return _frvec_lib
+    if "frvec" in _fr_libs:
+        return _fr_libs["frvec"]
+    vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
+    return _load_fr("frvec", {
+        "map_device": [i, i, vp, vp, vp, vp, vp, sz, i, u8p, u8p, u32],
+        "inverse_device": [i, i, vp, vp, vp, sz, u32],
+        "scan_device": [i, i, vp, vp, vp, sz, sz, i, u32, vp],
+        "map": [i, i, vp, vp, vp, vp, sz, i, u8p, u8p, u32],
+        "inverse": [i, i, vp, vp, sz, u32],
+        "scan": [i, i, vp, vp, sz, sz, i, u32, vp],
+        "release": [],
+        "test_tile": [i],
+        "test_last": [C.POINTER(i), C.POINTER(i)],
+    })
 
 
 def frvec_test_tile(elements=0):
@@ -264,36 +267,27 @@ def frvec_release():
     frvec_lib().msm_frvec_release()
 
 
-_frpoly_lib = None
-
-
 def frpoly_lib():
     """Load libmsm_frpoly.so (in-tree; include/msm_frpoly.h): polynomial opening over the scalar field.  Raises if it has not been built -- there is
     no fallback path."""
-    global _frpoly_lib
-    if _frpoly_lib is None:
-        so = _build.FRPOLY_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frpoly.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
-        L.msm_frpoly_abi_version.restype = i
-        L.msm_frpoly_eval_device.argtypes = [i, i, vp, vp, sz, sz, u8p, u32, vp]
-        L.msm_frpoly_divide_device.argtypes = [i, i, vp, vp, vp, sz, sz, u8p, u32, vp]
-        L.msm_frpoly_dot_device.argtypes = [i, i, vp, vp, vp, sz, sz, u32, vp]
-        L.msm_frpoly_combine_device.argtypes = [i, i, vp, vp, vp, sz, sz, u8p, u32]
-        L.msm_frpoly_powers_device.argtypes = [i, i, vp, vp, sz, u8p, u8p, u32]
-        L.msm_frpoly_eval.argtypes = [i, i, vp, sz, sz, u8p, u32, vp]
-        L.msm_frpoly_divide.argtypes = [i, i, vp, vp, sz, sz, u8p, u32, vp]
-        L.msm_frpoly_dot.argtypes = [i, i, vp, vp, sz, sz, u32, vp]
-        L.msm_frpoly_combine.argtypes = [i, i, vp, vp, sz, sz, u8p, u32]
-        L.msm_frpoly_powers.argtypes = [i, i, vp, sz, u8p, u8p, u32]
-        L.msm_frpoly_release.argtypes = []
-        L.msm_frpoly_release.restype = None
-        L.msm_frpoly_test_tile.argtypes = [i]
-        L.msm_frpoly_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
-        _frpoly_lib = L
-    return _frpoly_lib
+    if "frpoly" in _fr_libs:
+        return _fr_libs["frpoly"]
+    vp, u8p, sz, i, u32 = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32
+    return _load_fr("frpoly", {
+        "eval_device": [i, i, vp, vp, sz, sz, u8p, u32, vp],
+        "divide_device": [i, i, vp, vp, vp, sz, sz, u8p, u32, vp],
+        "dot_device": [i, i, vp, vp, vp, sz, sz, u32, vp],
+        "combine_device": [i, i, vp, vp, vp, sz, sz, u8p, u32],
+        "powers_device": [i, i, vp, vp, sz, u8p, u8p, u32],
+        "eval": [i, i, vp, sz, sz, u8p, u32, vp],
+        "divide": [i, i, vp, vp, sz, sz, u8p, u32, vp],
+        "dot": [i, i, vp, vp, sz, sz, u32, vp],
+        "combine": [i, i, vp, vp, sz, sz, u8p, u32],
+        "powers": [i, i, vp, sz, u8p, u8p, u32],
+        "release": [],
+        "test_tile": [i],
+        "test_last": [C.POINTER(i), C.POINTER(i)],
+    })
 
 
 def frpoly_test_tile(elements=0):
@@ -313,9 +307,6 @@ def frpoly_release():
     frpoly_lib().msm_frpoly_release()
 
 
-_frmle_lib = None
-
-
 class FrmleTerm(C.Structure):
     """msm_frmle_term (include/msm_frmle.h): coeff * prod_{f < degree} row[rows[f]]"""
     _fields_ = [("coeff", C.c_uint8 * 32), ("degree", C.c_uint32), ("rows", C.c_uint32 * 4)]
@@ -324,28 +315,22 @@ class FrmleTerm(C.Structure):
 def frmle_lib():
     """Load libmsm_frmle.so (in-tree; include/msm_frmle.h): the sumcheck over multilinear tables of the scalar field.  Raises if it has not been built
     -- there is no fallback path."""
-    global _frmle_lib
-    if _frmle_lib is None:
-        so = _build.FRMLE_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frmle.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, u8p, sz, i, u32, tp = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrmleTerm)
-        L.msm_frmle_abi_version.restype = i
-        L.msm_frmle_fold_device.argtypes = [i, i, vp, vp, vp, sz, sz, sz, u8p, u32]
-        L.msm_frmle_eval_device.argtypes = [i, i, vp, vp, sz, sz, sz, u8p, u32, vp]
-        L.msm_frmle_eq_device.argtypes = [i, i, vp, vp, sz, u8p, u8p, u32]
-        L.msm_frmle_round_device.argtypes = [i, i, vp, vp, sz, sz, sz, tp, sz, u8p, u32, vp]
-        L.msm_frmle_fold.argtypes = [i, i, vp, vp, sz, sz, sz, u8p, u32]
-        L.msm_frmle_eval.argtypes = [i, i, vp, sz, sz, sz, u8p, u32, vp]
-        L.msm_frmle_eq.argtypes = [i, i, vp, sz, u8p, u8p, u32]
-        L.msm_frmle_round.argtypes = [i, i, vp, sz, sz, sz, tp, sz, u8p, u32, vp]
-        L.msm_frmle_release.argtypes = []
-        L.msm_frmle_release.restype = None
-        L.msm_frmle_test_tile.argtypes = [i]
-        L.msm_frmle_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
-        _frmle_lib = L
-    return _frmle_lib
+    if "frmle" in _fr_libs:
+        return _fr_libs["frmle"]
+    vp, u8p, sz, i, u32, tp = C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrmleTerm)
+    return _load_fr("frmle", {
+        "fold_device": [i, i, vp, vp, vp, sz, sz, sz, u8p, u32],
+        "eval_device": [i, i, vp, vp, sz, sz, sz, u8p, u32, vp],
+        "eq_device": [i, i, vp, vp, sz, u8p, u8p, u32],
+        "round_device": [i, i, vp, vp, sz, sz, sz, tp, sz, u8p, u32, vp],
+        "fold": [i, i, vp, vp, sz, sz, sz, u8p, u32],
+        "eval": [i, i, vp, sz, sz, sz, u8p, u32, vp],
+        "eq": [i, i, vp, sz, u8p, u8p, u32],
+        "round": [i, i, vp, sz, sz, sz, tp, sz, u8p, u32, vp],
+        "release": [],
+        "test_tile": [i],
+        "test_last": [C.POINTER(i), C.POINTER(i)],
+    })
 
 
 def frmle_test_tile(elements=0):
@@ -365,32 +350,22 @@ def frmle_release():
     frmle_lib().msm_frmle_release()
 
 
-_frmat_lib = None
-
-
 def frmat_lib():
     """Load libmsm_frmat.so (in-tree; include/msm_frmat.h): sparse matrix-vector products over the scalar field.  Raises if it has not been built
     (msm-webgpu_amd/build.py builds it beside the other five)."""
-    global _frmat_lib
-    if _frmat_lib is None:
-        so = _build.FRMAT_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frmat.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        i, sz, vp, u32 = C.c_int, C.c_size_t, C.c_void_p, C.c_uint32
-        L.msm_frmat_abi_version.restype = i
-        L.msm_frmat_create.argtypes = [i, i, sz, sz, sz, vp, vp, vp, u32, C.POINTER(vp)]
-        L.msm_frmat_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
-        L.msm_frmat_destroy.argtypes = [vp]
-        L.msm_frmat_destroy.restype = None
-        L.msm_frmat_mul_device.argtypes = [vp, vp, vp, sz, vp, sz, u32]
-        L.msm_frmat_mul.argtypes = [vp, vp, sz, vp, sz, u32]
-        L.msm_frmat_release.argtypes = []
-        L.msm_frmat_release.restype = None
-        L.msm_frmat_test_tile.argtypes = [i]
-        L.msm_frmat_test_last.argtypes = [C.POINTER(i), C.POINTER(i)]
-        _frmat_lib = L
-    return _frmat_lib
+    if "frmat" in _fr_libs:
+        return _fr_libs["frmat"]
+    i, sz, vp, u32 = C.c_int, C.c_size_t, C.c_void_p, C.c_uint32
+    return _load_fr("frmat", {
+        "create": [i, i, sz, sz, sz, vp, vp, vp, u32, C.POINTER(vp)],
+        "info": [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)],
+        "destroy": [vp],
+        "mul_device": [vp, vp, vp, sz, vp, sz, u32],
+        "mul": [vp, vp, sz, vp, sz, u32],
+        "release": [],
+        "test_tile": [i],
+        "test_last": [C.POINTER(i), C.POINTER(i)],
+    })
 
 
 def frmat_test_tile(entries=0):
@@ -410,9 +385,6 @@ def frmat_release():
     frmat_lib().msm_frmat_release()
 
 
-_frgate_lib = None
-
-
 class FrgateTerm(C.Structure):
     """msm_frgate_term (include/msm_frgate.h): coeff * prod_{f < degree} row[rows[f]] at the rotation rots[f]"""
     _fields_ = [("coeff", C.c_uint8 * 32), ("degree", C.c_uint32), ("rows", C.c_uint32 * 8), ("rots", C.c_int32 * 8)]
@@ -421,20 +393,14 @@ class FrgateTerm(C.Structure):
 def frgate_lib():
     """Load libmsm_frgate.so (in-tree; include/msm_frgate.h): constraint evaluation over rotated rows of the scalar field.  Raises if it has not been
     built (msm-webgpu_amd/build.py builds it beside the other six)."""
-    global _frgate_lib
-    if _frgate_lib is None:
-        so = _build.FRGATE_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frgate.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, sz, i, u32, tp = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrgateTerm)
-        L.msm_frgate_abi_version.restype = i
-        L.msm_frgate_apply_device.argtypes = [i, i, vp, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32]
-        L.msm_frgate_apply.argtypes = [i, i, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32]
-        L.msm_frgate_release.argtypes = []
-        L.msm_frgate_release.restype = None
-        _frgate_lib = L
-    return _frgate_lib
+    if "frgate" in _fr_libs:
+        return _fr_libs["frgate"]
+    vp, sz, i, u32, tp = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(FrgateTerm)
+    return _load_fr("frgate", {
+        "apply_device": [i, i, vp, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32],
+        "apply": [i, i, vp, vp, sz, sz, sz, tp, sz, sz, vp, sz, u32],
+        "release": [],
+    })
 
 
 def frgate_release():
@@ -442,32 +408,22 @@ def frgate_release():
     frgate_lib().msm_frgate_release()
 
 
-_frlook_lib = None
-
-
 def frlook_lib():
     """Load libmsm_frlook.so (in-tree; include/msm_frlook.h): lookup arguments over the scalar field -- multiplicities and table indices.  Raises
     if it has not been built (msm-webgpu_amd/build.py builds it beside the other seven)."""
-    global _frlook_lib
-    if _frlook_lib is None:
-        so = _build.FRLOOK_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frlook.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, sz, i, u32, u64p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)
-        L.msm_frlook_abi_version.restype = i
-        L.msm_frlook_create_device.argtypes = [i, i, vp, vp, sz, u32, C.POINTER(vp)]
-        L.msm_frlook_create.argtypes = [i, i, vp, sz, u32, C.POINTER(vp)]
-        L.msm_frlook_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)]
-        L.msm_frlook_destroy.argtypes = [vp]
-        L.msm_frlook_destroy.restype = None
-        L.msm_frlook_count_device.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p]
-        L.msm_frlook_count.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p]
-        L.msm_frlook_release.argtypes = []
-        L.msm_frlook_release.restype = None
-        L.msm_frlook_test_hash_bits.argtypes = [i]
-        _frlook_lib = L
-    return _frlook_lib
+    if "frlook" in _fr_libs:
+        return _fr_libs["frlook"]
+    vp, sz, i, u32, u64p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)
+    return _load_fr("frlook", {
+        "create_device": [i, i, vp, vp, sz, u32, C.POINTER(vp)],
+        "create": [i, i, vp, sz, u32, C.POINTER(vp)],
+        "info": [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(u32)],
+        "destroy": [vp],
+        "count_device": [vp, vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p],
+        "count": [vp, vp, vp, vp, vp, sz, sz, sz, u32, u64p, u64p],
+        "release": [],
+        "test_hash_bits": [i],
+    })
 
 
 lib_frlook = frlook_lib
@@ -511,35 +467,25 @@ class FrLookup:
             pass
 
 
-_frhash_lib = None
-
-
 def frhash_lib():
     """Load libmsm_frhash.so (in-tree; include/msm_frhash.h): Poseidon over the scalar field -- batch permutations, sponges, Merkle trees.  Raises
     if it has not been built (msm-webgpu_amd/build.py builds it beside the other eight)."""
-    global _frhash_lib
-    if _frhash_lib is None:
-        so = _build.FRHASH_SO
-        if not os.path.exists(so):
-            raise ImportError("libmsm_frhash.so is not built (%s); run `python -c 'import __graft_entry__ as g; g.build()'`" % so)
-        L = C.CDLL(so)
-        vp, sz, i, u32, u32p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)
-        L.msm_frhash_abi_version.restype = i
-        L.msm_frhash_create.argtypes = [i, i, u32, u32, u32, u32, vp, vp, u32, C.POINTER(vp)]
-        L.msm_frhash_info.argtypes = [vp, u32p, u32p, u32p]
-        L.msm_frhash_destroy.argtypes = [vp]
-        L.msm_frhash_destroy.restype = None
-        L.msm_frhash_permute_device.argtypes = [vp, vp, vp, vp, sz, u32]
-        L.msm_frhash_permute.argtypes = [vp, vp, vp, sz, u32]
-        L.msm_frhash_hash_device.argtypes = [vp, vp, vp, vp, sz, sz, sz, vp, u32, u32, u32]
-        L.msm_frhash_hash.argtypes = [vp, vp, vp, sz, sz, sz, vp, u32, u32, u32]
-        L.msm_frhash_merkle_device.argtypes = [vp, vp, vp, vp, sz, vp, u32, u32, u32]
-        L.msm_frhash_merkle.argtypes = [vp, vp, vp, sz, vp, u32, u32, u32]
-        L.msm_frhash_release.argtypes = []
-        L.msm_frhash_release.restype = None
-        L.msm_frhash_test_tile.argtypes = [i]
-        _frhash_lib = L
-    return _frhash_lib
+    if "frhash" in _fr_libs:
+        return _fr_libs["frhash"]
+    vp, sz, i, u32, u32p = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.POINTER(C.c_uint32)
+    return _load_fr("frhash", {
+        "create": [i, i, u32, u32, u32, u32, vp, vp, u32, C.POINTER(vp)],
+        "info": [vp, u32p, u32p, u32p],
+        "destroy": [vp],
+        "permute_device": [vp, vp, vp, vp, sz, u32],
+        "permute": [vp, vp, vp, sz, u32],
+        "hash_device": [vp, vp, vp, vp, sz, sz, sz, vp, u32, u32, u32],
+        "hash": [vp, vp, vp, sz, sz, sz, vp, u32, u32, u32],
+        "merkle_device": [vp, vp, vp, vp, sz, vp, u32, u32, u32],
+        "merkle": [vp, vp, vp, sz, vp, u32, u32, u32],
+        "release": [],
+        "test_tile": [i],
+    })
 
 
 lib_frhash = frhash_lib

@@ -1,4 +1,5 @@
-"""Build libmsm_hip.so, libmsm_fr.so, libmsm_frvec.so, libmsm_frpoly.so, libmsm_frmle.so, libmsm_frmat.so, libmsm_frgate.so, libmsm_frlook.so and libmsm_frhash.so in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so and the scalar-field libraries (FR_LIBRARIES: libmsm_fr.so ... libmsm_frhash.so) in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+import collections
 import os
 import subprocess
 
@@ -8,392 +9,65 @@ CSRC = os.path.join(HERE, "csrc")
 SO = os.environ.get("MSM_HIP_SO") or os.path.join(HERE, "libmsm_hip.so")
 SOURCES = ["msm_hip.hip", "curve_bn254.hip", "curve_grumpkin.hip", "curve_pallas.hip", "curve_vesta.hip", "curve_bls12_381.hip", "curve_bn254_g2.hip", "curve_bls12_381_g2.hip", "fq2.h", "bn254_g2_constants.h", "bls12_381_g2_constants.h", "fq28x14_asm.h", "bls12_381_constants.h", "curve_ops.h", "msm_layout.h", "recode.h", "sort_kernels.h", "msm_kernels.h", "g1.h", "fq29.h", "fq29_asm.h", "host_g1.h", "host_fr.h", "host_pool.h", "host_worker.h", "glv.h", "scalar_mul.h", "msm_mgpu.h", "curve_select.h", "curve_unit.h", "grumpkin_constants.h", "bn254_constants.h", "pallas_constants.h", "vesta_constants.h"]
 HEADER = os.path.join(HERE, "..", "include", "msm_hip.h")
-# libmsm_fr.so (include/msm_fr.h): the scalar-field NTT, a library of its own -- one translation unit per field, its own sources and stamp.  None
-# of it is part of libmsm_hip.so (TRANSLATION_UNITS, SOURCES and device_asm_files() below are that library's alone).
-FR_SO = os.path.join(HERE, "libmsm_fr.so")
-FR_UNITS = ["fr_bn254.hip", "fr_pallas.hip", "fr_vesta.hip", "fr_bls12_381.hip"]
-FR_SOURCES = FR_UNITS + ["fr_unit.h", "ntt_kernels.h", "ntt_host.h", "ntt_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h", "fr_pallas_constants.h",
-                         "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FR_HEADERS = [os.path.join(HERE, "..", "include", "msm_fr.h"), HEADER]
-# libmsm_frvec.so (include/msm_frvec.h): vector arithmetic over the scalar field -- map, batch inverse, scan --, the third library, built the same way
-FRVEC_SO = os.path.join(HERE, "libmsm_frvec.so")
-FRVEC_UNITS = ["frvec_bn254.hip", "frvec_pallas.hip", "frvec_vesta.hip", "frvec_bls12_381.hip"]
-FRVEC_SOURCES = FRVEC_UNITS + ["frvec_unit.h", "frvec_kernels.h", "frvec_host.h", "frvec_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                               "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRVEC_HEADERS = [os.path.join(HERE, "..", "include", "msm_frvec.h"), HEADER]
-# libmsm_frpoly.so (include/msm_frpoly.h): polynomial opening over the scalar field -- eval, divide, dot, combine, powers --, the fourth library
-FRPOLY_SO = os.path.join(HERE, "libmsm_frpoly.so")
-FRPOLY_UNITS = ["frpoly_bn254.hip", "frpoly_pallas.hip", "frpoly_vesta.hip", "frpoly_bls12_381.hip"]
-FRPOLY_SOURCES = FRPOLY_UNITS + ["frpoly_unit.h", "frpoly_kernels.h", "frpoly_host.h", "frpoly_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                                 "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRPOLY_HEADERS = [os.path.join(HERE, "..", "include", "msm_frpoly.h"), HEADER]
-# libmsm_frmle.so (include/msm_frmle.h): the sumcheck over multilinear tables -- fold, eval, eq, round --, the fifth library; the only one with a
-# unit for Grumpkin's scalar field (no transform needs it here)
-FRMLE_SO = os.path.join(HERE, "libmsm_frmle.so")
-FRMLE_UNITS = ["frmle_bn254.hip", "frmle_grumpkin.hip", "frmle_pallas.hip", "frmle_vesta.hip", "frmle_bls12_381.hip"]
-FRMLE_SOURCES = FRMLE_UNITS + ["frmle_unit.h", "frmle_kernels.h", "frmle_host.h", "frmle_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                               "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRMLE_HEADERS = [os.path.join(HERE, "..", "include", "msm_frmle.h"), HEADER]
-# libmsm_frmat.so (include/msm_frmat.h): sparse matrix-vector products over the scalar field -- the rows Az, Bz, Cz of an R1CS --, the sixth library;
-# like the fifth it has a unit for Grumpkin's scalar field
-FRMAT_SO = os.path.join(HERE, "libmsm_frmat.so")
-FRMAT_UNITS = ["frmat_bn254.hip", "frmat_grumpkin.hip", "frmat_pallas.hip", "frmat_vesta.hip", "frmat_bls12_381.hip"]
-FRMAT_SOURCES = FRMAT_UNITS + ["frmat_unit.h", "frmat_kernels.h", "frmat_host.h", "frmat_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                               "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRMAT_HEADERS = [os.path.join(HERE, "..", "include", "msm_frmat.h"), HEADER]
-# libmsm_frgate.so (include/msm_frgate.h): constraint evaluation over the scalar field -- sums of products of rotated rows, the numerator of a
-# PLONK quotient --, the seventh library; like the fifth and sixth it has a unit for Grumpkin's scalar field
-FRGATE_SO = os.path.join(HERE, "libmsm_frgate.so")
-FRGATE_UNITS = ["frgate_bn254.hip", "frgate_grumpkin.hip", "frgate_pallas.hip", "frgate_vesta.hip", "frgate_bls12_381.hip"]
-FRGATE_SOURCES = FRGATE_UNITS + ["frgate_unit.h", "frgate_kernels.h", "frgate_host.h", "frgate_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                                 "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRGATE_HEADERS = [os.path.join(HERE, "..", "include", "msm_frgate.h"), HEADER]
-# libmsm_frlook.so (include/msm_frlook.h): lookup arguments over the scalar field -- the multiplicity column and the table indices of a logUp --,
-# the eighth library; it matches keys and computes nothing, so of the field's files it needs the constants alone (no fq29.h)
-FRLOOK_SO = os.path.join(HERE, "libmsm_frlook.so")
-FRLOOK_UNITS = ["frlook_bn254.hip", "frlook_grumpkin.hip", "frlook_pallas.hip", "frlook_vesta.hip", "frlook_bls12_381.hip"]
-FRLOOK_SOURCES = FRLOOK_UNITS + ["frlook_unit.h", "frlook_kernels.h", "frlook_host.h", "frlook_plan.h", "host_fr.h", "fr_bn254_constants.h",
-                                 "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRLOOK_HEADERS = [os.path.join(HERE, "..", "include", "msm_frlook.h"), HEADER]
-# libmsm_frhash.so (include/msm_frhash.h): Poseidon over the scalar field -- batch permutations, sponges and Merkle trees --, the ninth library;
-# a unit for every scalar field, Grumpkin's included
-FRHASH_SO = os.path.join(HERE, "libmsm_frhash.so")
-FRHASH_UNITS = ["frhash_bn254.hip", "frhash_grumpkin.hip", "frhash_pallas.hip", "frhash_vesta.hip", "frhash_bls12_381.hip"]
-FRHASH_SOURCES = FRHASH_UNITS + ["frhash_unit.h", "frhash_kernels.h", "frhash_host.h", "frhash_plan.h", "host_fr.h", "fq29.h", "fq29_asm.h", "fr_bn254_constants.h",
-                                 "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"]
-FRHASH_HEADERS = [os.path.join(HERE, "..", "include", "msm_frhash.h"), HEADER]
+# The scalar-field libraries (include/msm_<name>.h), each a library of its own beside libmsm_hip.so: one translation unit per scalar field, its
+# own sources and stamp.  None of them is part of libmsm_hip.so (SO, SOURCES, TRANSLATION_UNITS and the no-argument forms of the functions
+# below are that library's alone).  A new library is one more row of FR_LIBRARIES.
+FrLibrary = collections.namedtuple("FrLibrary", "name so units sources headers")
+FIELDS = ["bn254", "grumpkin", "pallas", "vesta", "bls12_381"]
+NO_GRUMPKIN = [f for f in FIELDS if f != "grumpkin"]  # (no transform needs Grumpkin's scalar field: r - 1 = 2 * odd)
+
+
+def _fr_library(name, fields=FIELDS, stem=None, field_math=True):
+    """stem: what the kernels, host and plan headers are called (the library's name, but for the NTT); field_math: csrc/fq29.h, the multipliers"""
+    units = ["%s_%s.hip" % (name, f) for f in fields]
+    own = [name + "_unit.h"] + ["%s_%s.h" % (stem or name, part) for part in ("kernels", "host", "plan")]
+    math = ["fq29.h", "fq29_asm.h"] if field_math else []
+    sources = units + own + ["fr_host_common.h", "host_fr.h"] + math + ["fr_%s_constants.h" % f for f in fields]
+    return FrLibrary(name, os.path.join(HERE, "libmsm_%s.so" % name), units, sources, [os.path.join(HERE, "..", "include", "msm_%s.h" % name), HEADER])
+
+
+FR_LIBRARIES = collections.OrderedDict((lib.name, lib) for lib in [
+    _fr_library("fr", NO_GRUMPKIN, stem="ntt"),  # the NTT
+    _fr_library("frvec", NO_GRUMPKIN),  # vector arithmetic: map, batch inverse, scan
+    _fr_library("frpoly", NO_GRUMPKIN),  # polynomial opening: eval, divide, dot, combine, powers
+    _fr_library("frmle"),  # the sumcheck over multilinear tables: fold, eval, eq, round
+    _fr_library("frmat"),  # sparse matrix-vector products: the rows Az, Bz, Cz of an R1CS
+    _fr_library("frgate"),  # constraint evaluation: sums of products of rotated rows, the numerator of a PLONK quotient
+    _fr_library("frlook", field_math=False),  # lookup arguments: it matches keys and computes nothing, so of the field's files the constants alone
+    _fr_library("frhash"),  # Poseidon: batch permutations, sponges and Merkle trees
+])
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
-def device_asm_files():
-    """The device assembly of every translation unit, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in TRANSLATION_UNITS]
+def library_of(units):
+    """The scalar-field library whose units contain `units`; None for libmsm_hip.so's units (and for none at all)."""
+    return next((lib for lib in FR_LIBRARIES.values() if units and set(units) <= set(lib.units)), None)
 
 
-def device_asm_is_current():
-    """True if build() left the device assembly of the CURRENT sources behind (same staleness rule as the library itself)."""
-    if needs_build() or not all(os.path.exists(f) for f in device_asm_files()):
+def device_asm_files(lib=None):
+    """The device assembly of every translation unit of a library (lib: a row of FR_LIBRARIES; None: libmsm_hip.so), as build() leaves it behind."""
+    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in (lib.units if lib else TRANSLATION_UNITS)]
+
+
+def device_asm_is_current(lib=None):
+    """True if build() left the device assembly of the library's CURRENT sources behind (same staleness rule as the library itself)."""
+    if needs_build(lib) or not all(os.path.exists(f) for f in device_asm_files(lib)):
         return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in device_asm_files())
+    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in (lib.sources if lib else SOURCES) if os.path.exists(os.path.join(CSRC, f)))
+    return all(os.path.getmtime(f) >= newest for f in device_asm_files(lib))
 
 
-def fr_device_asm_files():
-    """The device assembly of libmsm_fr.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FR_UNITS]
-
-
-def fr_build_stamp():
-    """build_stamp() for libmsm_fr.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FR_SOURCES)] + FR_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def fr_needs_build():
-    """libmsm_fr.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FR_SO + ".stamp") as f:
-            return not os.path.exists(FR_SO) or f.read().strip() != fr_build_stamp()
-    except OSError:
-        return True
-
-
-def fr_device_asm_is_current():
-    """device_asm_is_current() for libmsm_fr.so's units"""
-    if fr_needs_build() or not all(os.path.exists(f) for f in fr_device_asm_files()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FR_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in fr_device_asm_files())
-
-
-def frvec_device_asm_files():
-    """The device assembly of libmsm_frvec.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRVEC_UNITS]
-
-
-def frvec_build_stamp():
-    """build_stamp() for libmsm_frvec.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRVEC_SOURCES)] + FRVEC_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frvec_needs_build():
-    """libmsm_frvec.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRVEC_SO + ".stamp") as f:
-            return not os.path.exists(FRVEC_SO) or f.read().strip() != frvec_build_stamp()
-    except OSError:
-        return True
-
-
-def frvec_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frvec.so's units"""
-    if frvec_needs_build() or not all(os.path.exists(f) for f in frvec_device_asm_files()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRVEC_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frvec_device_asm_files())
-
-
-def frpoly_device_asm_paths():
-    """The device assembly of libmsm_frpoly.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRPOLY_UNITS]
-
-
-def frpoly_build_stamp():
-    """build_stamp() for libmsm_frpoly.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRPOLY_SOURCES)] + FRPOLY_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frpoly_needs_build():
-    """libmsm_frpoly.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRPOLY_SO + ".stamp") as f:
-            return not os.path.exists(FRPOLY_SO) or f.read().strip() != frpoly_build_stamp()
-    except OSError:
-        return True
-
-
-def frpoly_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frpoly.so's units"""
-    if frpoly_needs_build() or not all(os.path.exists(f) for f in frpoly_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRPOLY_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frpoly_device_asm_paths())
-
-
-def frmle_device_asm_paths():
-    """The device assembly of libmsm_frmle.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRMLE_UNITS]
-
-
-def frmle_build_stamp():
-    """build_stamp() for libmsm_frmle.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRMLE_SOURCES)] + FRMLE_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frmle_needs_build():
-    """libmsm_frmle.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRMLE_SO + ".stamp") as f:
-            return not os.path.exists(FRMLE_SO) or f.read().strip() != frmle_build_stamp()
-    except OSError:
-        return True
-
-
-def frmle_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frmle.so's units"""
-    if frmle_needs_build() or not all(os.path.exists(f) for f in frmle_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRMLE_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frmle_device_asm_paths())
-
-
-def frmat_device_asm_paths():
-    """The device assembly of libmsm_frmat.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRMAT_UNITS]
-
-
-def frmat_build_stamp():
-    """build_stamp() for libmsm_frmat.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRMAT_SOURCES)] + FRMAT_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frmat_needs_build():
-    """libmsm_frmat.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRMAT_SO + ".stamp") as f:
-            return not os.path.exists(FRMAT_SO) or f.read().strip() != frmat_build_stamp()
-    except OSError:
-        return True
-
-
-def frmat_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frmat.so's units"""
-    if frmat_needs_build() or not all(os.path.exists(f) for f in frmat_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRMAT_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frmat_device_asm_paths())
-
-
-def frgate_device_asm_paths():
-    """The device assembly of libmsm_frgate.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRGATE_UNITS]
-
-
-def frgate_build_stamp():
-    """build_stamp() for libmsm_frgate.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRGATE_SOURCES)] + FRGATE_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frgate_needs_build():
-    """libmsm_frgate.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRGATE_SO + ".stamp") as f:
-            return not os.path.exists(FRGATE_SO) or f.read().strip() != frgate_build_stamp()
-    except OSError:
-        return True
-
-
-def frgate_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frgate.so's units"""
-    if frgate_needs_build() or not all(os.path.exists(f) for f in frgate_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRGATE_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frgate_device_asm_paths())
-
-
-def frlook_device_asm_paths():
-    """The device assembly of libmsm_frlook.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRLOOK_UNITS]
-
-
-def frlook_build_stamp():
-    """build_stamp() for libmsm_frlook.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRLOOK_SOURCES)] + FRLOOK_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frlook_needs_build():
-    """libmsm_frlook.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRLOOK_SO + ".stamp") as f:
-            return not os.path.exists(FRLOOK_SO) or f.read().strip() != frlook_build_stamp()
-    except OSError:
-        return True
-
-
-def frlook_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frlook.so's units"""
-    if frlook_needs_build() or not all(os.path.exists(f) for f in frlook_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRLOOK_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frlook_device_asm_paths())
-
-
-def frhash_device_asm_paths():
-    """The device assembly of libmsm_frhash.so's units, as build() leaves it behind."""
-    return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in FRHASH_UNITS]
-
-
-def frhash_build_stamp():
-    """build_stamp() for libmsm_frhash.so: the compile flags and the contents of its own sources"""
-    import hashlib
-
-    h = hashlib.sha256()
-    h.update("\0".join(compile_flags()).encode())
-    for path in [os.path.join(CSRC, f) for f in sorted(FRHASH_SOURCES)] + FRHASH_HEADERS:
-        if os.path.exists(path):
-            h.update(b"\0" + os.path.basename(path).encode() + b"\0")
-            with open(path, "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()
-
-
-def frhash_needs_build():
-    """libmsm_frhash.so is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)"""
-    if os.environ.get("MSM_HIP_SO"):
-        return False
-    try:
-        with open(FRHASH_SO + ".stamp") as f:
-            return not os.path.exists(FRHASH_SO) or f.read().strip() != frhash_build_stamp()
-    except OSError:
-        return True
-
-
-def frhash_device_asm_is_current():
-    """device_asm_is_current() for libmsm_frhash.so's units"""
-    if frhash_needs_build() or not all(os.path.exists(f) for f in frhash_device_asm_paths()):
-        return False
-    newest = max(os.path.getmtime(os.path.join(CSRC, f)) for f in FRHASH_SOURCES if os.path.exists(os.path.join(CSRC, f)))
-    return all(os.path.getmtime(f) >= newest for f in frhash_device_asm_paths())
-
-
-def build_stamp():
+def build_stamp(lib=None):
     """what the library on disk must have been built FROM to be the product: a hash over the compile flags (the environment switches of the
-    diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source.  Written next to the
-    library by build(); a library whose stamp differs (built once with variant flags, or from other sources) is rebuilt instead of being
-    silently reused, and the code-generation gates (tools/check_machine_verifier.py, tools/check_long_branch_hazard.py) check the stamp of the
-    library they vouch for."""
+    diagnostic builds included -- MSM_HIP_SLP, MSM_HIP_NO_ASM, MSM_HIP_EXTRA_FLAGS ...) and the contents of every source and public header.
+    Written next to the library by build(); a library whose stamp differs (built once with variant flags, or from other sources) is rebuilt
+    instead of being silently reused, and the code-generation gates (tools/check_machine_verifier.py, tools/check_long_branch_hazard.py) check
+    the stamp of the library they vouch for."""
     import hashlib
 
     h = hashlib.sha256()
     h.update("\0".join(compile_flags()).encode())
-    for f in sorted(SOURCES) + [HEADER]:
-        path = f if os.path.isabs(f) else os.path.join(CSRC, f)
+    for path in [os.path.join(CSRC, f) for f in sorted(lib.sources if lib else SOURCES)] + (lib.headers if lib else [HEADER]):
         if os.path.exists(path):
             h.update(b"\0" + os.path.basename(path).encode() + b"\0")
             with open(path, "rb") as fh:
@@ -419,7 +93,16 @@ def variant_flags():
     return [k for k in ("MSM_HIP_SLP", "MSM_HIP_NO_ASM", "MSM_HIP_ASM_SMVP_ONLY", "MSM_HIP_EXTRA_FLAGS") if os.environ.get(k)]
 
 
-def needs_build():
+def needs_build(lib=None):
+    if lib:
+        # a scalar-field library is missing, or was built from other sources or flags (a diagnostic MSM_HIP_SO build leaves it alone)
+        if os.environ.get("MSM_HIP_SO"):
+            return False
+        try:
+            with open(lib.so + ".stamp") as f:
+                return not os.path.exists(lib.so) or f.read().strip() != build_stamp(lib)
+        except OSError:
+            return True
     if not os.path.exists(SO):
         return True
     if os.environ.get("MSM_HIP_SO"):
@@ -456,17 +139,11 @@ def compile_flags():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
-    from the scalar-field units, msm-webgpu_amd/libmsm_fr.so, msm-webgpu_amd/libmsm_frvec.so, msm-webgpu_amd/libmsm_frpoly.so,
-    msm-webgpu_amd/libmsm_frmle.so, msm-webgpu_amd/libmsm_frmat.so, msm-webgpu_amd/libmsm_frgate.so, msm-webgpu_amd/libmsm_frlook.so and msm-webgpu_amd/libmsm_frhash.so.  Each library is rebuilt only when its own sources or the flags changed."""
-    do_hip, do_fr = force or needs_build(), (force and not os.environ.get("MSM_HIP_SO")) or fr_needs_build()
-    do_frvec = (force and not os.environ.get("MSM_HIP_SO")) or frvec_needs_build()
-    do_frpoly = (force and not os.environ.get("MSM_HIP_SO")) or frpoly_needs_build()
-    do_frmle = (force and not os.environ.get("MSM_HIP_SO")) or frmle_needs_build()
-    do_frmat = (force and not os.environ.get("MSM_HIP_SO")) or frmat_needs_build()
-    do_frgate = (force and not os.environ.get("MSM_HIP_SO")) or frgate_needs_build()
-    do_frlook = (force and not os.environ.get("MSM_HIP_SO")) or frlook_needs_build()
-    do_frhash = (force and not os.environ.get("MSM_HIP_SO")) or frhash_needs_build()
-    if not do_hip and not do_fr and not do_frvec and not do_frpoly and not do_frmle and not do_frmat and not do_frgate and not do_frlook and not do_frhash:
+    from the scalar-field units, every library of FR_LIBRARIES (msm-webgpu_amd/libmsm_fr.so ... msm-webgpu_amd/libmsm_frhash.so).  Each library
+    is rebuilt only when its own sources or the flags changed."""
+    do_hip = force or needs_build()
+    todo = [lib for lib in FR_LIBRARIES.values() if (force and not os.environ.get("MSM_HIP_SO")) or needs_build(lib)]
+    if not do_hip and not todo:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
         # the product library is only ever built with the gated flags: a variant build must name its own file
@@ -494,46 +171,18 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd, cwd=TEMPS)
         os.replace(so + ".tmp", so)
 
-    # one pool for the units of all nine libraries (the long curve units first), never more than 16 compilers at once
-    units = (TRANSLATION_UNITS if do_hip else []) + (FR_UNITS if do_fr else []) + (FRVEC_UNITS if do_frvec else []) + (FRPOLY_UNITS if do_frpoly else []) + (FRMLE_UNITS if do_frmle else []) + (FRMAT_UNITS if do_frmat else []) + (FRGATE_UNITS if do_frgate else []) + (FRLOOK_UNITS if do_frlook else []) + (FRHASH_UNITS if do_frhash else [])
+    # one pool for the units of all the libraries (the long curve units first), never more than 16 compilers at once
+    units = (TRANSLATION_UNITS if do_hip else []) + [u for lib in todo for u in lib.units]
     with ThreadPoolExecutor(max_workers=min(len(units), os.cpu_count() or 1, 16)) as pool:
         objs = dict(zip(units, pool.map(compile_unit, units)))
     if do_hip:
         link([objs[u] for u in TRANSLATION_UNITS], SO)
         with open(stamp_path(), "w") as f:
             f.write(build_stamp() + "\n")
-    if do_fr:
-        link([objs[u] for u in FR_UNITS], FR_SO)
-        with open(FR_SO + ".stamp", "w") as f:
-            f.write(fr_build_stamp() + "\n")
-    if do_frvec:
-        link([objs[u] for u in FRVEC_UNITS], FRVEC_SO)
-        with open(FRVEC_SO + ".stamp", "w") as f:
-            f.write(frvec_build_stamp() + "\n")
-    if do_frpoly:
-        link([objs[u] for u in FRPOLY_UNITS], FRPOLY_SO)
-        with open(FRPOLY_SO + ".stamp", "w") as f:
-            f.write(frpoly_build_stamp() + "\n")
-    if do_frmle:
-        link([objs[u] for u in FRMLE_UNITS], FRMLE_SO)
-        with open(FRMLE_SO + ".stamp", "w") as f:
-            f.write(frmle_build_stamp() + "\n")
-    if do_frmat:
-        link([objs[u] for u in FRMAT_UNITS], FRMAT_SO)
-        with open(FRMAT_SO + ".stamp", "w") as f:
-            f.write(frmat_build_stamp() + "\n")
-    if do_frgate:
-        link([objs[u] for u in FRGATE_UNITS], FRGATE_SO)
-        with open(FRGATE_SO + ".stamp", "w") as f:
-            f.write(frgate_build_stamp() + "\n")
-    if do_frlook:
-        link([objs[u] for u in FRLOOK_UNITS], FRLOOK_SO)
-        with open(FRLOOK_SO + ".stamp", "w") as f:
-            f.write(frlook_build_stamp() + "\n")
-    if do_frhash:
-        link([objs[u] for u in FRHASH_UNITS], FRHASH_SO)
-        with open(FRHASH_SO + ".stamp", "w") as f:
-            f.write(frhash_build_stamp() + "\n")
+    for lib in todo:
+        link([objs[u] for u in lib.units], lib.so)
+        with open(lib.so + ".stamp", "w") as f:
+            f.write(build_stamp(lib) + "\n")
     return SO
 
 

@@ -13,6 +13,7 @@
 
 #include "../../include/msm_frgate.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "frgate_plan.h"
 // (csrc/frgate_kernels.h -- FrgateArgs, FrgateOps -- is already in: csrc/frgate_unit.h includes this file behind the unit's kernels)
 
@@ -24,25 +25,8 @@ extern "C" const FrgateOps* msm_frgate_ops_bls12_381(void);
 
 namespace msm_frgate {
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
+using namespace fr_host;
 
-struct Buffer {
-  uint32_t* p = nullptr;
-  size_t words = 0;
-};
 struct DeviceState {
   hipStream_t stream = nullptr;
   Buffer result;    // word 0: the error word
@@ -52,48 +36,11 @@ struct DeviceState {
   std::vector<uint32_t> h_consts;  // what is on its way into consts (it outlives the call that uploads it)
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 
 inline const FrgateOps* field_of(int curve) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: return msm_frgate_ops_bn254();
-    case MSM_HIP_CURVE_GRUMPKIN: return msm_frgate_ops_grumpkin();
-    case MSM_HIP_CURVE_PALLAS: return msm_frgate_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: return msm_frgate_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: return msm_frgate_ops_bls12_381();
-    default: return nullptr;
-  }
-}
-
-inline int grow(Buffer& b, size_t want_words, bool pinned = false) {
-  if (b.words >= want_words) return MSM_HIP_OK;
-  if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-  b.p = nullptr;
-  b.words = 0;
-  const hipError_t e = pinned ? hipHostMalloc(reinterpret_cast<void**>(&b.p), want_words * 4, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void**>(&b.p), want_words * 4);
-  if (e != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  b.words = want_words;
-  return MSM_HIP_OK;
-}
-inline bool apart(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p + a_bytes <= q || q + b_bytes <= p;
-}
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-inline int have_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
-  return MSM_HIP_OK;
+  return fr_host::field_of<FrgateOps>(curve, msm_frgate_ops_bn254, msm_frgate_ops_grumpkin, msm_frgate_ops_pallas, msm_frgate_ops_vesta, msm_frgate_ops_bls12_381);
 }
 
 inline int apply_impl(int curve, int device, void* stream, void* out, const void* a, size_t n, size_t batch, size_t stride, const msm_frgate_term* terms, size_t num_terms,
@@ -168,12 +115,7 @@ void msm_frgate_release(void) {
     if (!guard.ok) continue;
     msm_frgate::DeviceState& ds = kv.second;
     if (ds.stream) (void)hipStreamSynchronize(ds.stream);
-    msm_frgate::Buffer* all[2] = {&ds.consts, &ds.staging};
-    for (msm_frgate::Buffer* b : all) {
-      if (b->p) (void)hipFree(b->p);
-      b->p = nullptr;
-      b->words = 0;
-    }
+    for (fr_host::Buffer* b : {&ds.consts, &ds.staging}) fr_host::drop(*b);
   }
 }
 }  // extern "C"

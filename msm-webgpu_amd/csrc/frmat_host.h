@@ -15,6 +15,7 @@
 
 #include "../../include/msm_frmat.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "frmat_plan.h"
 // (csrc/frmat_kernels.h -- FrmatLevelArgs, FrmatOps -- is already in: csrc/frmat_unit.h includes this file behind the unit's kernels)
 
@@ -57,28 +58,11 @@ struct msm_frmat {
 
 namespace frmat {
 
+using namespace fr_host;
+
 constexpr uint32_t CREATE_FLAGS = MSM_FRMAT_WITH_TRANSPOSE;
 constexpr uint32_t MUL_FLAGS = MSM_FRMAT_MONT256 | MSM_FRMAT_TRANSPOSE;
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-struct Buffer {
-  uint32_t* p = nullptr;
-  size_t words = 0;
-};
 struct DeviceState {
   hipStream_t stream = nullptr;
   Buffer result;    // word 0: the error word
@@ -86,14 +70,8 @@ struct DeviceState {
   Buffer staging;   // the host form's x and y
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 inline uint32_t& tile_hook() {
   static uint32_t t = 0;
   return t;
@@ -104,39 +82,9 @@ inline int (&last_shape())[2] {
 }
 
 inline const FrmatOps* field_of(int curve) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: return msm_frmat_ops_bn254();
-    case MSM_HIP_CURVE_GRUMPKIN: return msm_frmat_ops_grumpkin();
-    case MSM_HIP_CURVE_PALLAS: return msm_frmat_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: return msm_frmat_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: return msm_frmat_ops_bls12_381();
-    default: return nullptr;
-  }
+  return fr_host::field_of<FrmatOps>(curve, msm_frmat_ops_bn254, msm_frmat_ops_grumpkin, msm_frmat_ops_pallas, msm_frmat_ops_vesta, msm_frmat_ops_bls12_381);
 }
 
-inline int grow(Buffer& b, size_t want_words, bool pinned = false) {
-  if (b.words >= want_words) return MSM_HIP_OK;
-  if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-  b.p = nullptr;
-  b.words = 0;
-  const hipError_t e = pinned ? hipHostMalloc(reinterpret_cast<void**>(&b.p), want_words * 4, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void**>(&b.p), want_words * 4);
-  if (e != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  b.words = want_words;
-  return MSM_HIP_OK;
-}
-inline bool apart(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p + a_bytes <= q || q + b_bytes <= p;
-}
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-inline int have_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
-  return MSM_HIP_OK;
-}
 inline size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }
 
 // `words` words of device memory holding the `have` words at src, zero behind them
@@ -322,9 +270,7 @@ void msm_frmat_release(void) {
     if (!guard.ok) continue;
     frmat::DeviceState& ds = kv.second;
     if (ds.stream) (void)hipStreamSynchronize(ds.stream);
-    if (ds.staging.p) (void)hipFree(ds.staging.p);
-    ds.staging.p = nullptr;
-    ds.staging.words = 0;
+    fr_host::drop(ds.staging);
   }
 }
 

@@ -14,6 +14,7 @@
 
 #include "../../include/msm_frmle.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "frmle_plan.h"
 // (csrc/frmle_kernels.h -- the Frmle*Args, FrmleOps -- is already in: csrc/frmle_unit.h includes this file behind the unit's kernels)
 
@@ -29,28 +30,11 @@ static_assert(FRMLE_MAX_DEGREE == 4, "msm_frmle_term holds four rows");
 
 namespace msm_frmle {
 
+using namespace fr_host;
+
 constexpr size_t MAX_ELEMENTS = (size_t)1 << 26;
 constexpr uint32_t KNOWN_FLAGS = MSM_FRMLE_MONT256;
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-struct Buffer {
-  uint32_t* p = nullptr;
-  size_t words = 0;
-};
 struct DeviceState {
   hipStream_t stream = nullptr;
   Buffer result;    // word 0: the error word; from word FRMLE_RESULT_HEAD: the values of the call
@@ -61,14 +45,8 @@ struct DeviceState {
   std::vector<uint32_t> h_consts;  // what is on its way into consts (it outlives the call that uploads it)
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 inline uint32_t& tile_hook() {
   static uint32_t t = 0;
   return t;
@@ -79,27 +57,7 @@ inline int (&last_shape())[2] {
 }
 
 inline const FrmleOps* field_of(int curve) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: return msm_frmle_ops_bn254();
-    case MSM_HIP_CURVE_GRUMPKIN: return msm_frmle_ops_grumpkin();
-    case MSM_HIP_CURVE_PALLAS: return msm_frmle_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: return msm_frmle_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: return msm_frmle_ops_bls12_381();
-    default: return nullptr;
-  }
-}
-
-inline int grow(Buffer& b, size_t want_words, bool pinned = false) {
-  if (b.words >= want_words) return MSM_HIP_OK;
-  if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-  b.p = nullptr;
-  b.words = 0;
-  const hipError_t e = pinned ? hipHostMalloc(reinterpret_cast<void**>(&b.p), want_words * 4, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void**>(&b.p), want_words * 4);
-  if (e != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  b.words = want_words;
-  return MSM_HIP_OK;
+  return fr_host::field_of<FrmleOps>(curve, msm_frmle_ops_bn254, msm_frmle_ops_grumpkin, msm_frmle_ops_pallas, msm_frmle_ops_vesta, msm_frmle_ops_bls12_381);
 }
 
 // an output is its input exactly (the same first byte), or apart from it
@@ -107,13 +65,6 @@ inline bool overlap_ok(const void* out, const void* in, size_t bytes) {
   if (in == out) return true;
   const uintptr_t o = reinterpret_cast<uintptr_t>(out), i = reinterpret_cast<uintptr_t>(in);
   return o + bytes <= i || i + bytes <= o;
-}
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-inline int have_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
-  return MSM_HIP_OK;
 }
 
 struct Call {
@@ -361,12 +312,7 @@ void msm_frmle_release(void) {
     if (!guard.ok) continue;
     msm_frmle::DeviceState& ds = kv.second;
     if (ds.stream) (void)hipStreamSynchronize(ds.stream);
-    msm_frmle::Buffer* all[3] = {&ds.scratch, &ds.consts, &ds.staging};
-    for (msm_frmle::Buffer* b : all) {
-      if (b->p) (void)hipFree(b->p);
-      b->p = nullptr;
-      b->words = 0;
-    }
+    for (fr_host::Buffer* b : {&ds.scratch, &ds.consts, &ds.staging}) fr_host::drop(*b);
   }
 }
 

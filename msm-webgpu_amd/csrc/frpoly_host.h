@@ -11,6 +11,7 @@
 
 #include "../../include/msm_frpoly.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "frpoly_plan.h"
 // (csrc/frpoly_kernels.h -- the Frpoly*Args, FrpolyOps -- is already in: csrc/frpoly_unit.h includes this file behind the unit's kernels)
 
@@ -23,28 +24,11 @@ static_assert(FRPOLY_MAX_ROWS == MSM_FRPOLY_MAX_ROWS, "csrc/frpoly_kernels.h and
 
 namespace msm_frpoly {
 
+using namespace fr_host;
+
 constexpr size_t MAX_ELEMENTS = (size_t)1 << 26;
 constexpr uint32_t KNOWN_FLAGS = MSM_FRPOLY_MONT256;
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-struct Buffer {
-  uint32_t* p = nullptr;
-  size_t words = 0;
-};
 struct DeviceState {
   hipStream_t stream = nullptr;
   uint32_t* d_err = nullptr;
@@ -55,14 +39,8 @@ struct DeviceState {
   std::vector<uint32_t> h_consts;  // what is on its way into consts (it outlives the call that uploads it)
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 inline uint32_t& tile_hook() {
   static uint32_t t = 0;
   return t;
@@ -72,26 +50,8 @@ inline int (&last_shape())[2] {
   return s;
 }
 
-inline const FrpolyOps* field_of(int curve) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: return msm_frpoly_ops_bn254();
-    case MSM_HIP_CURVE_PALLAS: return msm_frpoly_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: return msm_frpoly_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: return msm_frpoly_ops_bls12_381();
-    default: return nullptr;  // Grumpkin: no constants for its scalar field
-  }
-}
-
-inline int grow(Buffer& b, size_t want_words) {
-  if (b.words >= want_words) return MSM_HIP_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.words = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&b.p), want_words * 4) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  b.words = want_words;
-  return MSM_HIP_OK;
+inline const FrpolyOps* field_of(int curve) {  // (Grumpkin: no constants for its scalar field, so no unit)
+  return fr_host::field_of<FrpolyOps>(curve, msm_frpoly_ops_bn254, nullptr, msm_frpoly_ops_pallas, msm_frpoly_ops_vesta, msm_frpoly_ops_bls12_381);
 }
 
 // an output is its input exactly (the same first byte), or apart from it
@@ -100,7 +60,6 @@ inline bool overlap_ok(const void* out, size_t out_bytes, const void* in, size_t
   const uintptr_t o = reinterpret_cast<uintptr_t>(out), i = reinterpret_cast<uintptr_t>(in);
   return o + out_bytes <= i || i + in_bytes <= o;
 }
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 struct Call {
   DeviceState* ds = nullptr;
@@ -113,12 +72,6 @@ inline int enter(int device, void* stream, bool host, Call* c) {  // (the caller
   if (!ds.h_err && hipHostMalloc(reinterpret_cast<void**>(&ds.h_err), 4, hipHostMallocDefault) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
   c->ds = &ds;
   c->st = stream && !host ? static_cast<hipStream_t>(stream) : ds.stream;
-  return MSM_HIP_OK;
-}
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-inline int have_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
   return MSM_HIP_OK;
 }
 // host form: vector `src` of `words` words into staging buffer k
@@ -317,12 +270,7 @@ void msm_frpoly_release(void) {
     if (!guard.ok) continue;
     msm_frpoly::DeviceState& ds = kv.second;
     if (ds.stream) (void)hipStreamSynchronize(ds.stream);
-    msm_frpoly::Buffer* all[4] = {&ds.scratch, &ds.consts, &ds.staging[0], &ds.staging[1]};
-    for (msm_frpoly::Buffer* b : all) {
-      if (b->p) (void)hipFree(b->p);
-      b->p = nullptr;
-      b->words = 0;
-    }
+    for (fr_host::Buffer* b : {&ds.scratch, &ds.consts, &ds.staging[0], &ds.staging[1]}) fr_host::drop(*b);
   }
 }
 

@@ -11,6 +11,7 @@
 
 #include "../../include/msm_frvec.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "frvec_plan.h"
 // (csrc/frvec_kernels.h -- the Frvec*Args, FrvecOps -- is already in: csrc/frvec_unit.h includes this file behind the unit's kernels)
 
@@ -26,27 +27,10 @@ static_assert(FRVEC_ADD == MSM_FRVEC_ADD && FRVEC_SUB == MSM_FRVEC_SUB && FRVEC_
 
 namespace msm_frvec {
 
+using namespace fr_host;
+
 constexpr size_t MAX_ELEMENTS = (size_t)1 << 26;
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-
-struct Buffer {
-  uint32_t* p = nullptr;
-  size_t words = 0;
-};
 struct DeviceState {
   hipStream_t stream = nullptr;
   uint32_t* d_err = nullptr;
@@ -55,14 +39,8 @@ struct DeviceState {
   Buffer staging[3];          // the host forms' a (and out), b, c
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 inline uint32_t& tile_hook() {
   static uint32_t t = 0;
   return t;
@@ -72,26 +50,8 @@ inline int (&last_shape())[2] {
   return s;
 }
 
-inline const FrvecOps* field_of(int curve) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: return msm_frvec_ops_bn254();
-    case MSM_HIP_CURVE_PALLAS: return msm_frvec_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: return msm_frvec_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: return msm_frvec_ops_bls12_381();
-    default: return nullptr;  // Grumpkin: no constants for its scalar field
-  }
-}
-
-inline int grow(Buffer& b, size_t want_words) {
-  if (b.words >= want_words) return MSM_HIP_OK;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.words = 0;
-  if (hipMalloc(reinterpret_cast<void**>(&b.p), want_words * 4) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  b.words = want_words;
-  return MSM_HIP_OK;
+inline const FrvecOps* field_of(int curve) {  // (Grumpkin: no constants for its scalar field, so no unit)
+  return fr_host::field_of<FrvecOps>(curve, msm_frvec_ops_bn254, nullptr, msm_frvec_ops_pallas, msm_frvec_ops_vesta, msm_frvec_ops_bls12_381);
 }
 
 // an output is one of its inputs exactly, or apart from it
@@ -100,7 +60,6 @@ inline bool overlap_ok(const void* out, const void* in, size_t bytes) {
   const uintptr_t o = reinterpret_cast<uintptr_t>(out), i = reinterpret_cast<uintptr_t>(in);
   return o + bytes <= i || i + bytes <= o;
 }
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
 // what every call shares once its own arguments are checked: the device, the state, the stream, the error word
 struct Call {
@@ -114,12 +73,6 @@ inline int enter(int device, void* stream, bool host, Call* c) {  // (the caller
   if (!ds.h_err && hipHostMalloc(reinterpret_cast<void**>(&ds.h_err), 4, hipHostMallocDefault) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
   c->ds = &ds;
   c->st = stream && !host ? static_cast<hipStream_t>(stream) : ds.stream;
-  return MSM_HIP_OK;
-}
-inline bool hip_ok(hipError_t e) { return e == hipSuccess; }
-inline int have_device(int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
   return MSM_HIP_OK;
 }
 // host form: vector `src` of `words` words into staging buffer k
@@ -305,12 +258,7 @@ void msm_frvec_release(void) {
     if (!guard.ok) continue;
     msm_frvec::DeviceState& ds = kv.second;
     if (ds.stream) (void)hipStreamSynchronize(ds.stream);
-    msm_frvec::Buffer* all[4] = {&ds.scratch, &ds.staging[0], &ds.staging[1], &ds.staging[2]};
-    for (msm_frvec::Buffer* b : all) {
-      if (b->p) (void)hipFree(b->p);
-      b->p = nullptr;
-      b->words = 0;
-    }
+    for (fr_host::Buffer* b : {&ds.scratch, &ds.staging[0], &ds.staging[1], &ds.staging[2]}) fr_host::drop(*b);
   }
 }
 

@@ -12,6 +12,7 @@
 
 #include "../../include/msm_fr.h"
 #include "../../include/msm_hip.h"
+#include "fr_host_common.h"  // the guard, buffers, pointer checks and the state scheme every scalar-field library shares
 #include "host_fr.h"
 #include "ntt_plan.h"
 // (csrc/ntt_kernels.h -- NttPass, NttTables, FrOps -- is already in: csrc/fr_unit.h includes this file behind the unit's kernels)
@@ -23,20 +24,7 @@ extern "C" const FrOps* msm_fr_ops_bls12_381(void);
 
 namespace msm_fr {
 
-struct DeviceGuard {  // every entry point runs on its device and leaves the caller's current device as it found it
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = prev == device || hipSetDevice(device) == hipSuccess;
-    if (prev == device) prev = -1;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
+using namespace fr_host;
 
 struct Table {  // a two-level power table on the device: lo[k] = g^k (k < 2^lo_bits), hi[k] = c g^(k 2^lo_bits), all times 2^261, canonical
   uint32_t *lo = nullptr, *hi = nullptr;
@@ -46,22 +34,13 @@ struct DeviceState {
   hipStream_t stream = nullptr;
   uint32_t* d_err = nullptr;
   uint32_t* h_err = nullptr;  // pinned: the error word comes back without a staging copy
-  uint32_t* scratch = nullptr;
-  size_t scratch_words = 0;
-  uint32_t* staging = nullptr;
-  size_t staging_words = 0;
+  Buffer scratch, staging;
   std::map<std::string, Table> tables;
   std::map<std::string, uint32_t*> butterflies;
 };
 
-inline std::mutex& lock() {
-  static std::mutex m;
-  return m;
-}
-inline std::map<int, DeviceState>& states() {
-  static std::map<int, DeviceState> s;
-  return s;
-}
+inline std::mutex& lock() { return lock_of<DeviceState>(); }
+inline std::map<int, DeviceState>& states() { return states_of<DeviceState>(); }
 inline int& pass_bits_cap() {
   static int b = 0;
   return b;
@@ -71,16 +50,8 @@ inline int (&last_shape())[2] {
   return s;
 }
 
-inline const FrOps* field_of(int curve, int* field_id) {
-  switch (curve) {
-    case MSM_HIP_CURVE_BN254_G1:
-    case MSM_HIP_CURVE_BN254_G2: *field_id = 0; return msm_fr_ops_bn254();
-    case MSM_HIP_CURVE_PALLAS: *field_id = 1; return msm_fr_ops_pallas();
-    case MSM_HIP_CURVE_VESTA: *field_id = 2; return msm_fr_ops_vesta();
-    case MSM_HIP_CURVE_BLS12_381:
-    case MSM_HIP_CURVE_BLS12_381_G2: *field_id = 3; return msm_fr_ops_bls12_381();
-    default: return nullptr;  // Grumpkin: r - 1 = 2 * odd
-  }
+inline const FrOps* field_of(int curve, int* field_id) {  // (Grumpkin: r - 1 = 2 * odd, so no unit)
+  return fr_host::field_of<FrOps>(curve, msm_fr_ops_bn254, nullptr, msm_fr_ops_pallas, msm_fr_ops_vesta, msm_fr_ops_bls12_381, field_id);
 }
 
 inline std::string key_of(const char* kind, int field, int bits, const uint8_t* g, int extra) {
@@ -134,16 +105,6 @@ inline int butterfly_table(DeviceState& ds, const host_fr::Field& f, int field, 
   return MSM_HIP_OK;
 }
 
-inline int grow(uint32_t** buf, size_t* have, size_t want_words) {
-  if (*have >= want_words) return MSM_HIP_OK;
-  if (*buf) (void)hipFree(*buf);
-  *buf = nullptr;
-  *have = 0;
-  if (hipMalloc(reinterpret_cast<void**>(buf), want_words * 4) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
-  *have = want_words;
-  return MSM_HIP_OK;
-}
-
 // every argument is checked before anything is enqueued; `host`: data is host memory, staged through the device
 inline int ntt_impl(int curve, int device, void* stream, void* data, int log_n, size_t batch, const uint8_t* omega, const uint8_t* pre, const uint8_t* post, uint32_t flags,
                     bool host) {
@@ -164,8 +125,8 @@ inline int ntt_impl(int curve, int device, void* stream, void* data, int log_n, 
   if (batch > ((size_t)1 << 40) / n) return MSM_HIP_ERR_INVALID_ARG;
   for (const NttPass& p : passes)
     if ((batch << (p.log_n - p.b - p.log_c)) >= ((size_t)1 << 31)) return MSM_HIP_ERR_INVALID_ARG;  // (workgroups of one launch)
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) return MSM_HIP_ERR_NO_DEVICE;
+  int rc = have_device(device);
+  if (rc) return rc;
   DeviceGuard guard(device);
   if (!guard.ok) return MSM_HIP_ERR_NO_DEVICE;
   std::lock_guard<std::mutex> hold(lock());
@@ -175,10 +136,9 @@ inline int ntt_impl(int curve, int device, void* stream, void* data, int log_n, 
   if (!ds.h_err && hipHostMalloc(reinterpret_cast<void**>(&ds.h_err), 4, hipHostMallocDefault) != hipSuccess) return MSM_HIP_ERR_OUT_OF_MEMORY;
   hipStream_t st = stream && !host ? static_cast<hipStream_t>(stream) : ds.stream;
   const size_t words = batch * n * 8;
-  int rc;
-  if (host && (rc = grow(&ds.staging, &ds.staging_words, words))) return rc;
-  if (passes.size() > 1 && (rc = grow(&ds.scratch, &ds.scratch_words, words))) return rc;
-  uint32_t* d_data = host ? ds.staging : static_cast<uint32_t*>(data);
+  if (host && (rc = grow(ds.staging, words))) return rc;
+  if (passes.size() > 1 && (rc = grow(ds.scratch, words))) return rc;
+  uint32_t* d_data = host ? ds.staging.p : static_cast<uint32_t*>(data);
 
   NttTables t;
   memset(&t, 0, sizeof t);
@@ -205,15 +165,14 @@ inline int ntt_impl(int curve, int device, void* stream, void* data, int log_n, 
     p.post_mode = p.last ? tpost.mode : 0, p.post_lo_bits = tpost.lo_bits;
   }
 
-  auto hip_ok = [](hipError_t e) { return e == hipSuccess; };
   if (host && !hip_ok(hipMemcpyAsync(d_data, data, words * 4, hipMemcpyHostToDevice, st))) return MSM_HIP_ERR_HIP;
   if (!hip_ok(hipMemsetAsync(ds.d_err, 0, 4, st))) return MSM_HIP_ERR_HIP;
   // all but the last two passes run in place; the last but one writes the scratch (same addresses), the last reads it and writes the data
   const size_t k = passes.size();
   for (size_t q = 0; q < k; q++) {
     const NttPass& p = passes[q];
-    const uint32_t* src = (k > 1 && q == k - 1) ? ds.scratch : d_data;
-    uint32_t* dst = (k > 1 && q == k - 2) ? ds.scratch : d_data;
+    const uint32_t* src = (k > 1 && q == k - 1) ? ds.scratch.p : d_data;
+    uint32_t* dst = (k > 1 && q == k - 2) ? ds.scratch.p : d_data;
     const unsigned blocks = (unsigned)(batch << (p.log_n - p.b - p.log_c));
     ops->launch(blocks, st, src, dst, &p, &t, ds.d_err);
     if (!hip_ok(hipGetLastError())) return MSM_HIP_ERR_HIP;
@@ -256,10 +215,8 @@ void msm_fr_release(void) {
     for (auto& b : ds.butterflies) (void)hipFree(b.second);
     ds.tables.clear();
     ds.butterflies.clear();
-    if (ds.scratch) (void)hipFree(ds.scratch);
-    if (ds.staging) (void)hipFree(ds.staging);
-    ds.scratch = ds.staging = nullptr;
-    ds.scratch_words = ds.staging_words = 0;
+    fr_host::drop(ds.scratch);
+    fr_host::drop(ds.staging);
   }
 }
 

@@ -134,7 +134,7 @@ def test_libmsm_hip_holds_the_kernels_it_held(built):
     b = importlib.import_module("msm_webgpu_amd.build")
     assert len(b.TRANSLATION_UNITS) == 8 and not any(u.startswith("fr_") for u in b.TRANSLATION_UNITS)
     assert not any(f.startswith(("fr_", "ntt_")) for f in b.SOURCES)
-    assert sorted(b.FR_UNITS) == ["fr_bls12_381.hip", "fr_bn254.hip", "fr_pallas.hip", "fr_vesta.hip"]
+    assert sorted(b.FR_LIBRARIES["fr"].units) == ["fr_bls12_381.hip", "fr_bn254.hip", "fr_pallas.hip", "fr_vesta.hip"]
     counts = []
     for path in chk.compile_to_asm([]):
         with open(path) as f:
@@ -142,7 +142,7 @@ def test_libmsm_hip_holds_the_kernels_it_held(built):
         assert not any("ntt" in n for n in names), path
         counts.append(len(names))
     assert len(counts) == 8 and sum(counts) == 141 + 5 * 42 + 2 * 36
-    for path in chk.compile_to_asm([], units=b.FR_UNITS):  # ... and each field's unit holds its one kernel, in its own namespace
+    for path in chk.compile_to_asm([], units=b.FR_LIBRARIES["fr"].units):  # ... and each field's unit holds its one kernel, in its own namespace
         with open(path) as f:
             names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", f.read(), flags=re.M)
         field = os.path.basename(path).split("-hip-")[0]

@@ -12,7 +12,7 @@ import check_long_branch_hazard as chk  # noqa: E402
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FR_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["fr"].units)
 
 
 def test_fr_units_have_no_long_branch_hazard(built):
@@ -38,5 +38,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FR_SO) and not b.fr_needs_build()
-    assert b.fr_device_asm_is_current()
+    assert os.path.exists(b.FR_LIBRARIES["fr"].so) and not b.needs_build(b.FR_LIBRARIES["fr"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["fr"])

@@ -16,7 +16,7 @@ KERNELS = ("k_frgate_apply",)
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRGATE_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frgate"].units)
 
 
 def test_frgate_units_have_no_long_branch_hazard(built):
@@ -65,22 +65,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRGATE_SO) and not b.frgate_needs_build()
-    assert b.frgate_device_asm_is_current()
-    for needs in (b.fr_needs_build, b.frvec_needs_build, b.frpoly_needs_build, b.frmle_needs_build, b.frmat_needs_build):  # the other stamps stay current
-        assert not needs()
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frgate.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRGATE_UNITS) == ["frgate_bls12_381.hip", "frgate_bn254.hip", "frgate_grumpkin.hip", "frgate_pallas.hip", "frgate_vesta.hip"]
-    for other in (b.TRANSLATION_UNITS, b.FR_UNITS, b.FRVEC_UNITS, b.FRPOLY_UNITS, b.FRMLE_UNITS, b.FRMAT_UNITS):
-        assert not set(other) & set(b.FRGATE_UNITS)
-    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES + b.FRMAT_SOURCES
-    assert not any(f.startswith("frgate_") for f in others)
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_", "frmat_")) for f in b.FRGATE_SOURCES)  # (no kernel of the other six)
-    for u in b.FRGATE_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frgate"].so) and not b.needs_build(b.FR_LIBRARIES["frgate"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frgate"])

@@ -17,7 +17,7 @@ KERNELS = ("k_frhash_permute", "k_frhash_hash")
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRHASH_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frhash"].units)
 
 
 def _stated():
@@ -87,26 +87,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRHASH_SO) and not b.frhash_needs_build()
-    assert b.frhash_device_asm_is_current()
-    for needs in (b.needs_build, b.fr_needs_build, b.frvec_needs_build, b.frpoly_needs_build, b.frmle_needs_build, b.frmat_needs_build, b.frgate_needs_build,
-                  b.frlook_needs_build):
-        assert not needs()  # the other eight stamps stay current
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frhash.so has its own sources and stamp: none of its files is among the other libraries' -- but for the field arithmetic they all
-    share --, so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRHASH_UNITS) == ["frhash_bls12_381.hip", "frhash_bn254.hip", "frhash_grumpkin.hip", "frhash_pallas.hip", "frhash_vesta.hip"]
-    for other in (b.TRANSLATION_UNITS, b.FR_UNITS, b.FRVEC_UNITS, b.FRPOLY_UNITS, b.FRMLE_UNITS, b.FRMAT_UNITS, b.FRGATE_UNITS, b.FRLOOK_UNITS):
-        assert not set(other) & set(b.FRHASH_UNITS)
-    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES + b.FRMAT_SOURCES + b.FRGATE_SOURCES + b.FRLOOK_SOURCES
-    assert not any(f.startswith("frhash_") for f in others)
-    shared = {"fq29.h", "fq29_asm.h", "host_fr.h", "fr_bn254_constants.h", "fr_grumpkin_constants.h", "fr_pallas_constants.h", "fr_vesta_constants.h", "fr_bls12_381_constants.h"}
-    assert set(b.FRHASH_SOURCES) & set(others) == shared
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_", "frmat_", "frgate_", "frlook_", "fq2.")) for f in b.FRHASH_SOURCES)
-    for u in b.FRHASH_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frhash"].so) and not b.needs_build(b.FR_LIBRARIES["frhash"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frhash"])

@@ -17,7 +17,7 @@ KERNELS = ("k_frlook_build", "k_frlook_count", "k_frlook_finish")
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRLOOK_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frlook"].units)
 
 
 def _stated():
@@ -87,23 +87,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRLOOK_SO) and not b.frlook_needs_build()
-    assert b.frlook_device_asm_is_current()
-    for needs in (b.needs_build, b.fr_needs_build, b.frvec_needs_build, b.frpoly_needs_build, b.frmle_needs_build, b.frmat_needs_build, b.frgate_needs_build):
-        assert not needs()  # the other seven stamps stay current
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frlook.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRLOOK_UNITS) == ["frlook_bls12_381.hip", "frlook_bn254.hip", "frlook_grumpkin.hip", "frlook_pallas.hip", "frlook_vesta.hip"]
-    for other in (b.TRANSLATION_UNITS, b.FR_UNITS, b.FRVEC_UNITS, b.FRPOLY_UNITS, b.FRMLE_UNITS, b.FRMAT_UNITS, b.FRGATE_UNITS):
-        assert not set(other) & set(b.FRLOOK_UNITS)
-    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES + b.FRMAT_SOURCES + b.FRGATE_SOURCES
-    assert not any(f.startswith("frlook_") for f in others)
-    # no kernel of the other seven, and no field arithmetic at all: keys are matched, not computed with
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_", "frmat_", "frgate_", "fq2")) for f in b.FRLOOK_SOURCES)
-    for u in b.FRLOOK_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frlook"].so) and not b.needs_build(b.FR_LIBRARIES["frlook"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frlook"])

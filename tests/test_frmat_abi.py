@@ -45,7 +45,7 @@ def test_symbols_are_declared_and_exported(built):
         assert hasattr(L, "msm_frmat_" + name), name
     declared = set(re.findall(r"\b(msm_frmat_\w+)\s*\(", text))
     assert declared == {"msm_frmat_" + n for n in names}  # the header and the library agree, name by name
-    out = os.popen("nm -D --defined-only %s" % api._build.FRMAT_SO).read()
+    out = os.popen("nm -D --defined-only %s" % api._build.FR_LIBRARIES["frmat"].so).read()
     assert set(re.findall(r" T (msm_frmat_(?!ops_)\w+)", out)) == declared
     assert L.msm_frmat_abi_version() == 1
     assert api.lib().msm_hip_abi_version() == 7 and api.fr_lib().msm_fr_abi_version() == 1 and api.frvec_lib().msm_frvec_abi_version() == 1

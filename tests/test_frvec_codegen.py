@@ -16,7 +16,7 @@ KERNELS = ("k_frvec_map", "k_frvec_inverse", "k_frvec_fold", "k_frvec_scan")
 def _units():
     import importlib
 
-    return list(importlib.import_module("msm_webgpu_amd.build").FRVEC_UNITS)
+    return list(importlib.import_module("msm_webgpu_amd.build").FR_LIBRARIES["frvec"].units)
 
 
 def test_frvec_units_have_no_long_branch_hazard(built):
@@ -56,5 +56,5 @@ def test_library_on_disk_was_built_from_the_current_sources(built):
     import importlib
 
     b = importlib.import_module("msm_webgpu_amd.build")
-    assert os.path.exists(b.FRVEC_SO) and not b.frvec_needs_build()
-    assert b.frvec_device_asm_is_current()
+    assert os.path.exists(b.FR_LIBRARIES["frvec"].so) and not b.needs_build(b.FR_LIBRARIES["frvec"])
+    assert b.device_asm_is_current(b.FR_LIBRARIES["frvec"])

@@ -224,30 +224,15 @@ def analyse_liveness(name, lines):
 def compile_to_asm(extra, units=None):
     """Device assembly of the product, one file per translation unit: the files the library's own build left behind when they are
     current (msm-webgpu_amd/build.py keeps the compiler's intermediate files), else fresh -S compiles (minutes).  units: None -- the
-    units of libmsm_hip.so; a list of unit names otherwise (libmsm_fr.so's: build.FR_UNITS; libmsm_frvec.so's: build.FRVEC_UNITS; libmsm_frpoly.so's: build.FRPOLY_UNITS;
-    libmsm_frmle.so's: build.FRMLE_UNITS; libmsm_frmat.so's: build.FRMAT_UNITS; libmsm_frgate.so's: build.FRGATE_UNITS;
-    libmsm_frlook.so's: build.FRLOOK_UNITS; libmsm_frhash.so's: build.FRHASH_UNITS)."""
+    units of libmsm_hip.so; a list of unit names otherwise (a scalar-field library's: build.FR_LIBRARIES[name].units)."""
     sys.path.insert(0, os.path.join(ROOT, "msm-webgpu_amd"))
     import build as _b
 
     if not extra and units is None and _b.device_asm_is_current():
         return _b.device_asm_files()
-    if not extra and units is not None and set(units) <= set(_b.FR_UNITS) and _b.fr_device_asm_is_current():
-        return [f for u, f in zip(_b.FR_UNITS, _b.fr_device_asm_files()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRVEC_UNITS) and _b.frvec_device_asm_is_current():
-        return [f for u, f in zip(_b.FRVEC_UNITS, _b.frvec_device_asm_files()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRPOLY_UNITS) and _b.frpoly_device_asm_is_current():
-        return [f for u, f in zip(_b.FRPOLY_UNITS, _b.frpoly_device_asm_paths()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRMLE_UNITS) and _b.frmle_device_asm_is_current():
-        return [f for u, f in zip(_b.FRMLE_UNITS, _b.frmle_device_asm_paths()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRMAT_UNITS) and _b.frmat_device_asm_is_current():
-        return [f for u, f in zip(_b.FRMAT_UNITS, _b.frmat_device_asm_paths()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRGATE_UNITS) and _b.frgate_device_asm_is_current():
-        return [f for u, f in zip(_b.FRGATE_UNITS, _b.frgate_device_asm_paths()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRLOOK_UNITS) and _b.frlook_device_asm_is_current():
-        return [f for u, f in zip(_b.FRLOOK_UNITS, _b.frlook_device_asm_paths()) if u in units]
-    if not extra and units is not None and set(units) <= set(_b.FRHASH_UNITS) and _b.frhash_device_asm_is_current():
-        return [f for u, f in zip(_b.FRHASH_UNITS, _b.frhash_device_asm_paths()) if u in units]
+    lib = _b.library_of(units)
+    if not extra and lib and _b.device_asm_is_current(lib):
+        return [f for u, f in zip(lib.units, _b.device_asm_files(lib)) if u in units]
     outdir = tempfile.mkdtemp(prefix="msm_hip_asm_")
     outs = []
     for unit in (_b.TRANSLATION_UNITS if units is None else units):

@@ -33,27 +33,10 @@ CACHE = os.path.join(ROOT, "build", "machine_verifier_cache.json")
 
 
 def sources_hash(flags, units=()):
-    """hash of the flags and of the sources the units are built from (libmsm_fr.so's, libmsm_frvec.so's, libmsm_frpoly.so's, libmsm_frmle.so's, libmsm_frmat.so's, libmsm_frgate.so's, libmsm_frlook.so's and libmsm_frhash.so's units have source lists of
-    their own)"""
+    """hash of the flags and of the sources the units are built from (a scalar-field library's units have that library's source list)"""
     h = hashlib.sha256(" ".join(flags).encode())
-    if units and set(units) <= set(_b.FR_UNITS):
-        sources = _b.FR_SOURCES
-    elif units and set(units) <= set(_b.FRVEC_UNITS):
-        sources = _b.FRVEC_SOURCES
-    elif units and set(units) <= set(_b.FRPOLY_UNITS):
-        sources = _b.FRPOLY_SOURCES
-    elif units and set(units) <= set(_b.FRMLE_UNITS):
-        sources = _b.FRMLE_SOURCES
-    elif units and set(units) <= set(_b.FRMAT_UNITS):
-        sources = _b.FRMAT_SOURCES
-    elif units and set(units) <= set(_b.FRGATE_UNITS):
-        sources = _b.FRGATE_SOURCES
-    elif units and set(units) <= set(_b.FRLOOK_UNITS):
-        sources = _b.FRLOOK_SOURCES
-    elif units and set(units) <= set(_b.FRHASH_UNITS):
-        sources = _b.FRHASH_SOURCES
-    else:
-        sources = _b.SOURCES
+    lib = _b.library_of(units)
+    sources = lib.sources if lib else _b.SOURCES
     for name in sorted(sources):
         path = os.path.join(_b.CSRC, name)
         if os.path.exists(path):
