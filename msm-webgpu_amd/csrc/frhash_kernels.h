@@ -31,6 +31,16 @@
 //   store   fq_mul(s, out), out < r: (t + 3) r^2.
 // The host program runs the pattern that reaches them (state, constants and matrix all r - 1, t = 12) under FQ_CHECK.
 //
+// The slack of these bounds.  They are sufficient, not tight: "< 2r" for a product is the multiplier's contract, but a Montgomery product of
+// value T is < T / R + r, and T / R <= 2 (t + 4) r^2 / R <= 2 (t + 4) / FQ_HEADROOM r is a fraction of r, so a sum of ceil(t / 2) pairs stays near
+// ceil(t / 2) r instead of (t + 1) r.  Measured in the host program (tests/test_frhash_host.py: constants, matrix, capacity and state all r - 1,
+// the standard parameters, sponges), the largest S-box input before fq_tidy was 4.9 r at t = 8 (Pallas; the bound says 12 r), 6.4 r at t = 10
+// (BN254, Grumpkin; 14 r), 5.7 r at t = 10 and 6.6 r at t = 12 for BLS12-381 (14 r, 16 r), 6.9 r at t = 12 overall (Grumpkin): its square is
+// below FQ_HEADROOM for every field at every width.  So with `tidy` forced to false at t = 8 alone, or at t = 10 alone, every FQ_CHECK run and
+// every comparison with the model still passes: the tests at each field's boundary widths (t = 4 | 5, 7 | 8, 9 | 10) check that both code
+// paths compute the permutation, they cannot show that the tidy is needed where the rule above asks for it.  The rule stays: it is what
+// the stated bounds prove.
+//
 // frg_load / frg_store of csrc/frgate_kernels.h are restated here (frh_load ..): including that file would instantiate libmsm_frgate.so's kernel in
 // every unit of this library.
 //

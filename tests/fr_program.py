@@ -1,4 +1,4 @@
-"""Programs over the seven scalar-field libraries (libmsm_fr, frvec, frpoly, frmle, frmat, frgate, frlook): a generator, and a model interpreter
+"""Programs over the eight scalar-field libraries (libmsm_fr, frvec, frpoly, frmle, frmat, frgate, frlook, frhash): a generator, and a model interpreter
 that predicts every byte a program leaves on the device.  Needs no GPU, no HIP and no torch: tools/fuzz_fr.py runs the programs on the device and
 compares, tests/test_fr_program.py checks the tester itself.
 
@@ -9,12 +9,18 @@ byte is always read at the same alignment and stays part of one canonical scalar
 or lies in a bank that no input of the call touches -- or, in an "overlap" step, overlaps an input in part, which the headers say is refused.
 
 The model mirrors an arena as its STORED bytes: a step decodes its operands under the field's current form (canonical, or a * 2^256 mod r),
-computes with the per-library models of this directory, and encodes again -- so set_scalar_format changes no byte, only how later steps read."""
+computes with the per-library models of this directory, and encodes again -- so set_scalar_format changes no byte, only how later steps read.
+
+libmsm_frhash's steps: "poseidon" makes a handle in a slot from a seed (its constants: poseidon_constants) and touches no device -- the handle's
+table goes there inside its first call, on whichever stream and under whichever form that call has; "permute", "sponge" and "tree" call it on
+ranges of the arena or, with host set, on the bytes of those ranges, in which case the result is the step's host value and no range is
+written.  An output that cuts the input is refused by the Python layer (REFUSED), not by the library.  A "plant" step with quiet set puts a value
+that is not below r where the next step does NOT read (the padding between a sponge's rows): that step must not be refused, and heals it."""
 import functools
 import hashlib
 import random
 
-from tests import frgate_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
+from tests import frgate_model, frhash_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
 
 FIELD_R = {
     "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
@@ -27,15 +33,26 @@ BANK, BANKS = 4608, 4  # scalars to a bank, banks to a half of the arena
 HALF = BANK * BANKS
 ARENA16 = 4 * HALF + 2  # the arena in units of 16 bytes: half A, 16 bytes that nobody writes, half B, 16 more
 LENGTHS = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2051, 4097)
+# The work of a Poseidon step is permutations x rounds x t^2, and the generator keeps it at or below HASH_WORK so that the Python model of one step
+# (frhash_model.Poseidon.permute) stays at about 0.1 s.  Measured on a CPU without a GPU, BN254 (BLS12-381 within 6 %), microseconds per unit of work:
+# t = 2, rounds (2, 0): 3.6; t = 3, (2, 0): 2.5; t = 3, (2, 1): 2.3; t = 4, (4, 2): 1.7; t = 5, (2, 3): 1.3; t = 7, (2, 2): 1.1; t = 9, (4, 2): 0.96;
+# t = 12, (2, 1): 0.83; t = 3, (8, 57): 1.8; t = 12, (8, 60): 0.69.  37000 units are 0.094 s at t = 3, the width of the widest step there is (a
+# tree over 2048 leaves, rounds (2, 0): 36846 units), and at most 0.09 s above it; at t = 2 the largest step the lengths below allow is 1025 lanes
+# of 8 rounds, 32800 units: 0.12 s.
+HASH_WORK = 37000
 LARGE, SMALL = 1023, 65  # a "large" step has an operand of at least LARGE scalars to a row, a "small" one at most SMALL
 ERR_INVALID_ARG, ERR_NONCANONICAL, REFUSED = -2, -4, "refused"  # MSM_HIP_ERR_*; REFUSED: the Python layer raises ValueError before the C call
 HOOKS = {"fr_test_pass_bits": (0, 1, 2, 3, 5), "frvec_test_tile": (0, 2, 3, 8, 64), "frpoly_test_tile": (0, 2, 3, 8, 64), "frmle_test_tile": (0, 2, 8, 64),
-         "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8)}
+         "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8), "frhash_test_tile": (0, 1, 3, 4, 64)}
 LIBRARY = {"map": "frvec", "inverse": "frvec", "scan": "frvec", "fft": "fr", "eval": "frpoly", "divide": "frpoly", "dot": "frpoly", "combine": "frpoly",
            "powers": "frpoly", "mle_fold": "frmle", "mle_eval": "frmle", "eq": "frmle", "round": "frmle", "matrix": "frmat", "matvec": "frmat", "gate": "frgate",
-           "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook"}
-LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook")
-GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult")  # the libraries that serve its scalar field
+           "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook", "poseidon": "frhash", "permute": "frhash", "sponge": "frhash", "tree": "frhash"}
+LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook", "frhash")
+GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult", "poseidon", "permute", "sponge", "tree")  # the libraries that serve its scalar field
+HASH_CALLS = ("permute", "sponge", "tree")  # the steps that call libmsm_frhash ("poseidon" touches no device)
+HASH_WIDTHS = (2, 3, 4, 5, 7, 8, 9, 10, 12)
+# the widest state whose S-box input the kernel leaves untidied, and the first it tidies: (t + 4)^2 against the field's FQ_HEADROOM (csrc/frhash_kernels.h)
+HASH_BOUNDARY = {"bls12_381": (4, 5), "pallas": (7, 8), "vesta": (7, 8), "bn254": (9, 10), "grumpkin": (9, 10)}
 KINDS = tuple(LIBRARY) + ("format", "hook", "close", "stream", "plant", "overlap")
 
 
@@ -83,7 +100,9 @@ class Model:
         self.mont = [False] * len(self.fields)
         self.mats = [{} for _ in self.fields]
         self.tabs = [{} for _ in self.fields]
+        self.hashes = [{} for _ in self.fields]  # slot -> frhash_model.Poseidon
         self.planted = [{} for _ in self.fields]  # off16 -> the 32 bytes a planted value replaced
+        self.quiet = [{} for _ in self.fields]  # the same for a value planted where the next step does NOT read: it must not be refused
         self.hooks = {h: 0 for h in HOOKS}
         self.side_stream = False
 
@@ -106,12 +125,12 @@ class Model:
     def put(self, f, off16, data):
         self.arena[f][16 * off16:16 * off16 + len(data)] = data
 
-    def _heal(self, f):
+    def _heal(self, f, planted):
         spots = []
-        for off16, old in self.planted[f].items():
+        for off16, old in planted.items():
             self.put(f, off16, old)
             spots.append((off16, 1))
-        self.planted[f].clear()
+        planted.clear()
         return spots
 
     def _run(self, f, reads, writes, compute):
@@ -119,11 +138,12 @@ class Model:
         if self.planted[f]:
             hit = any(_cuts((p, 1), rd) and (p - rd[0]) % 2 == 0 for p in self.planted[f] for rd in reads)
             assert hit, "a planted value must be read by the step that follows it"
-            return {"error": ERR_NONCANONICAL, "writes": [], "rewrite": [tuple(w) for w in writes] + self._heal(f), "host": None}
+            return {"error": ERR_NONCANONICAL, "writes": [], "rewrite": [tuple(w) for w in writes] + self._heal(f, self.planted[f]), "host": None}
+        assert not any(_cuts((p, 1), rd) for p in self.quiet[f] for rd in reads), "a quietly planted value lies where the step that follows it does not read"
         puts, host = compute()
         for off16, data in puts:
             self.put(f, off16, data)
-        return {"error": None, "writes": [(off16, len(data) // 32) for off16, data in puts], "rewrite": [], "host": host}
+        return {"error": None, "writes": [(off16, len(data) // 32) for off16, data in puts], "rewrite": self._heal(f, self.quiet[f]), "host": host}
 
     @staticmethod
     def _fail(code):
@@ -144,6 +164,7 @@ class Model:
     def op_init(self, f, seed):
         self.arena[f] = initial_arena(seed)
         self.planted[f].clear()
+        self.quiet[f].clear()
         return {"error": None, "writes": [], "rewrite": [(0, ARENA16 // 2)], "host": None}
 
     def op_format(self, f, mont):
@@ -160,12 +181,12 @@ class Model:
         return self._fail(None)
 
     def op_close(self, f, what, slot):
-        del (self.mats if what == "mat" else self.tabs)[f][slot]
+        del {"mat": self.mats, "tab": self.tabs, "hash": self.hashes}[what][f][slot]
         return self._fail(None)
 
-    def op_plant(self, f, at, value):
-        assert self.r[f] <= value < 1 << 256 and at not in self.planted[f]
-        self.planted[f][at] = self.raw(f, (at, 1))
+    def op_plant(self, f, at, value, quiet=False):
+        assert self.r[f] <= value < 1 << 256 and at not in self.planted[f] and at not in self.quiet[f]
+        (self.quiet if quiet else self.planted)[f][at] = self.raw(f, (at, 1))
         self.put(f, at, value.to_bytes(32, "little"))
         return {"error": None, "writes": [(at, 1)], "rewrite": [], "host": None}
 
@@ -356,6 +377,78 @@ class Model:
             return [(out[0], self.enc(f, cnt))], host
         return self._run(f, [(v[0] + 2 * k * stride, n) for k in range(batch)], [out], compute)
 
+    # ---- libmsm_frhash -------------------------------------------------------------------------------------------------------------------------
+    def op_poseidon(self, f, slot, t, full_rounds, partial_rounds, seed, capacity, capacity_at, out_at):
+        assert slot not in self.hashes[f] and len(self.hashes[f]) < 3 and t in HASH_WIDTHS
+        rc, mds = poseidon_constants(seed, t, full_rounds, partial_rounds, self.r[f])
+        self.hashes[f][slot] = frhash_model.Poseidon(self.r[f], t, full_rounds, partial_rounds, rc, mds, capacity, capacity_at, out_at)
+        return self._fail(None)  # (no device is touched: the table goes there with the handle's first call)
+
+    def _hashed(self, f, reads, out, host, values):
+        """a call of libmsm_frhash: values() -> the plain results, which go to `out`, or come back as host bytes in the data's form where `host` is set"""
+        def compute():
+            data = self.enc(f, values())
+            return ([], data) if host else ([(out[0], data)], None)
+        return self._run(f, reads, [] if host else [out], compute)
+
+    def op_permute(self, f, slot, a, out, host):
+        p = self.hashes[f][slot]
+        dst = a if out is None else out
+        assert a[1] % p.t == 0 and dst[1] == a[1] and not (host and out is not None)
+        if hash_cut(("permute", f, {"a": a, "out": out, "host": host})):
+            return self._fail(REFUSED)
+
+        def values():
+            v = self.plain(f, a)
+            return [x for i in range(0, len(v), p.t) for x in p.permute(v[i:i + p.t])]
+        return self._hashed(f, [a], dst, host, values)
+
+    def op_sponge(self, f, slot, a, batch, length, out, host):
+        p = self.hashes[f][slot]
+        stride = a[1] // batch
+        assert stride * batch == a[1] and 1 <= length <= stride and (host or out[1] == batch)
+        if hash_cut(("sponge", f, {"a": a, "out": out, "host": host})):
+            return self._fail(REFUSED)
+
+        def values():
+            v = self.plain(f, a)  # (the padding behind `length` decodes to whatever it does: it is not used)
+            return [p.hash(v[k * stride:k * stride + length]) for k in range(batch)]
+        return self._hashed(f, [(a[0] + 2 * k * stride, length) for k in range(batch)], out, host, values)
+
+    def op_tree(self, f, slot, leaves, levels, out, host):
+        p = self.hashes[f][slot]
+        assert (levels is not None and leaves[1] == 1) if p.t == 2 else levels is None
+        if hash_cut(("tree", f, {"leaves": leaves, "out": out, "host": host})):
+            return self._fail(REFUSED)
+
+        def values():
+            v = self.plain(f, leaves)
+            nodes = p.merkle_chain(v[0], levels) if p.t == 2 else [x for level in p.merkle(v) for x in level]
+            assert host or len(nodes) == out[1]
+            return nodes
+        return self._hashed(f, [leaves], out, host, values)
+
+
+def poseidon_constants(seed, t, full_rounds, partial_rounds, r):
+    """-> (round constants, matrix rows) of a handle from its integer seed, as expand gives matrix values; 0, 1 and r - 1 are among them"""
+    n = (full_rounds + partial_rounds) * t
+    vals = expand(seed, n + t * t, r)
+    for k, special in enumerate((0, 1, r - 1)):
+        vals[(seed + k) % n] = special  # among the round constants (there are at least four)
+        vals[n + ((seed >> 8) + k) % (t * t)] = special  # and in the matrix
+    return vals[:n], [vals[n + i * t:n + (i + 1) * t] for i in range(t)]
+
+
+def hash_cut(step):
+    """is this a device-form call of libmsm_frhash whose output shares bytes with its input where it must not: the Python layer refuses it
+    (REFUSED) before the C call.  A permutation may be in place; a sponge's and a tree's output lies apart from the whole input."""
+    kind, _, a = step
+    if kind not in HASH_CALLS or a["host"]:
+        return False
+    if kind == "permute":
+        return a["out"] is not None and Model._partial(a["out"], [a["a"]])
+    return _cuts(a["out"], a["a"] if kind == "sponge" else a["leaves"])
+
 
 class Refused(Exception):
     """what a backend raises where a call fails: code is ERR_* or REFUSED"""
@@ -403,11 +496,14 @@ class ModelBackend:
 
 def sizes(steps):
     """-> [(index, kind, field, scalars per row)] of the steps that call a library and have a size: the length of a row of the largest operand; for
-    a sparse product the entries of its matrix (its work).  What "large" (>= LARGE) and "small" (<= SMALL) are measured on."""
-    out, nnz = [], {}
+    a sparse product the entries of its matrix (its work); for a Poseidon step its lanes: the states of a permute, the rows of a sponge, the nodes
+    of a tree's first level.  What "large" (>= LARGE) and "small" (<= SMALL) are measured on."""
+    out, nnz, width = [], {}, {}
     for i, (kind, f, a) in enumerate(steps):
         if kind == "matrix":
             nnz[f, a["slot"]] = len(a["col_idx"])
+        if kind == "poseidon":
+            width[f, a["slot"]] = a["t"]
         if a.get("overlap") or kind not in LIBRARY:
             continue
         if kind in ("map", "inverse"):
@@ -424,6 +520,12 @@ def sizes(steps):
             n = nnz[f, a["slot"]]
         elif kind == "table":
             n = a["t"][1]
+        elif kind == "permute":
+            n = a["a"][1] // width[f, a["slot"]]
+        elif kind == "sponge":
+            n = a["batch"]
+        elif kind == "tree":
+            n = a["leaves"][1] // max(width[f, a["slot"]] - 1, 1)  # (arity 1: a chain over one leaf)
         else:
             continue
         out.append((i, kind, f, n))
@@ -432,10 +534,10 @@ def sizes(steps):
 
 # ---- the generator ---------------------------------------------------------------------------------------------------------------------------------
 _WEIGHT = {"map": 10, "inverse": 5, "scan": 8, "fft": 8, "eval": 4, "divide": 5, "dot": 4, "combine": 4, "powers": 4, "mle_fold": 5, "mle_eval": 4, "eq": 3,
-           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "format": 5, "hook": 7, "close": 3,
+           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "poseidon": 5, "permute": 9, "sponge": 8, "tree": 6, "format": 5, "hook": 7, "close": 3,
            "stream": 3, "overlap": 3}
 _LEN_WEIGHT = {1: 6, 2: 6, 63: 6, 64: 6, 65: 6, 255: 3, 256: 3, 257: 3, 1023: 1.6, 1024: 1.6, 1025: 1.6, 2051: 0.9, 4097: 0.6}
-_PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "matvec", "gate", "table", "mult")
+_PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "matvec", "gate", "table", "mult", "permute", "sponge", "tree")
 _OVERLAPS = ("map", "inverse", "scan", "divide", "combine", "mle_fold", "matvec")
 
 
@@ -446,6 +548,8 @@ class _Gen:
         self.mont = [False] * len(fields)
         self.mats = [{} for _ in fields]  # slot -> (rows, cols, transpose, row_ptr, col_idx)
         self.tabs = [{} for _ in fields]  # slot -> (n, form, the range it was made of)
+        self.hashes = [{} for _ in fields]  # slot -> (t, rounds)
+        self.host_before = False  # was the last call of libmsm_frhash a host-form one
         self.side = False
         self.steps = []
         self.prev_f, self.follow = None, None  # follow: (field, kind) of a large step that a small one of the same entry point is to follow
@@ -790,6 +894,96 @@ class _Gen:
         self.emit("mult", f, slot=slot, v=v, batch=batch, n=n, out=out, indices=self.rnd.random() < 0.6, counts=self.rnd.random() < 0.5)
         return n
 
+    # ---- libmsm_frhash: a handle (poseidon) and the three calls on it.  The work of a call -- permutations x rounds x t^2 -- stays within HASH_WORK.
+    def g_poseidon(self, f, small):
+        if len(self.hashes[f]) == 3:
+            self.g_close(f, small, "hash")
+        slot = self.rnd.choice([s for s in range(3) if s not in self.hashes[f]])
+        edge = HASH_BOUNDARY[self.fields[f]]
+        t = self.rnd.choices(HASH_WIDTHS, [4 if w in edge else 2 if w <= 4 else 1 for w in HASH_WIDTHS])[0]  # (t <= 4: the widths that a large call can have)
+        rf, rp = self.rnd.choice(((2, 0), (2, 0), (2, 1), (2, 1), (2, 3), (4, 2), (8, 0)))
+        if self.rnd.random() < 0.06:  # as long as the standard shapes: its calls have few lanes, by their work
+            rf, rp = 8, self.rnd.randrange(56, 67)
+        r = self.r[f]
+        self.hashes[f][slot] = (t, rf + rp)
+        self.emit("poseidon", f, slot=slot, t=t, full_rounds=rf, partial_rounds=rp, seed=self.rnd.randrange(1 << 30),
+                  capacity=self.rnd.choice((0, (3 << 64) % r, (1 << (t - 1)) - 1, r - 1, self.rnd.randrange(r))), capacity_at=self.rnd.choice((0, t - 1, self.rnd.randrange(t))),
+                  out_at=self.rnd.choice((0, 1 % t, self.rnd.randrange(t))))
+        return None
+
+    def hash_handle(self, f, small):
+        """-> (slot, t, the permutations one call may run): a live handle, made first where there is none"""
+        if not self.hashes[f] or (len(self.hashes[f]) < 3 and self.rnd.random() < 0.15):
+            self.g_poseidon(f, small)
+        slot = self.rnd.choice(sorted(self.hashes[f]))
+        t, rounds = self.hashes[f][slot]
+        return slot, t, max(HASH_WORK // (rounds * t * t), 1)
+
+    def lanes(self, small, cap):
+        pool = [n for n in LENGTHS if n <= cap and (n <= SMALL or not small)]
+        return self.rnd.choices(pool, [_LEN_WEIGHT[n] for n in pool])[0]
+
+    def hash_host(self, small):
+        """is the call a host-form one: a small call behind a large host-form one mostly is too"""
+        host = self.rnd.random() < (0.8 if small and self.host_before else 0.3)
+        self.host_before = host
+        return host
+
+    def g_permute(self, f, small):
+        slot, t, most = self.hash_handle(f, small)
+        n = self.lanes(small, min(most, BANK // t))
+        a, host, out = self.place(n * t), self.hash_host(small), None
+        c = self.rnd.random()
+        if not host and c < 0.5:
+            out = self.place(n * t, [a])
+        elif not host and c < 0.56 and n * t >= 2:  # cuts the input: refused by the Python layer
+            out = self.shifted(a)
+        if out is None or not _cuts(out, a):
+            self.maybe_plant(f, "permute", self.spots(a, self.rnd))
+        self.emit("permute", f, slot=slot, a=a, out=out, host=host)
+        return n
+
+    def g_sponge(self, f, small):
+        slot, t, most = self.hash_handle(f, small)
+        length = max(self.rnd.choice((1, t - 2, t - 1, t, 2 * (t - 1), 2 * (t - 1) + 1)), 1)  # the last block: empty, short or full
+        stride = length + self.rnd.choice((0, 0, 1, 3))
+        batch = self.lanes(small, min(max(most // -(-length // (t - 1)), 1), BANK // stride))
+        a, host, out = self.place(batch * stride), self.hash_host(small), None
+        if not host:
+            out = self.place(batch, [a])
+            if self.rnd.random() < 0.06:  # cuts the input, be it the padding behind the last row: refused by the Python layer
+                out = [a[0] + 2 * self.rnd.randrange(a[1] - batch + 1), batch]
+        if host or not _cuts(out, a):
+            rows = sorted({0, batch - 1, self.rnd.randrange(batch)})
+            before = len(self.steps)
+            self.maybe_plant(f, "sponge", self.spots(a, self.rnd, rows, stride, length))
+            if len(self.steps) == before and self.plant_ok and batch > 1 and stride > length and self.rnd.random() < 0.3:
+                # a value that is not below r in the padding behind the first row (far from every output's neighbourhood): not read, so not refused
+                self.emit("plant", f, at=a[0] + 2 * self.rnd.randrange(length, stride), value=self.rnd.choice((self.r[f], (1 << 256) - 1)), quiet=True)
+        self.emit("sponge", f, slot=slot, a=a, batch=batch, length=length, out=out, host=host)
+        return batch
+
+    def g_tree(self, f, small):
+        slot, t, most = self.hash_handle(f, small)
+        arity = t - 1
+        if arity == 1:  # a chain over one leaf
+            n, levels, first = 1, self.rnd.choice((1, 2, 3, 64, self.rnd.randrange(1, 65))), 1
+            count = levels
+        else:
+            depths = [k for k in range(1, 13) if arity ** k <= BANK and (arity ** k - 1) // (arity - 1) <= most and (arity ** (k - 1) <= SMALL or not small)] or [1]
+            k = self.rnd.choice(depths + depths[-1:])  # (the deepest there is twice: a large first level is rare enough)
+            n, levels, first = arity ** k, None, arity ** (k - 1)
+            count = (n - 1) // (arity - 1)
+        leaves, host, out = self.place(n), self.hash_host(small), None
+        if not host:
+            out = self.place(count, [leaves])
+            if arity > 1 and self.rnd.random() < 0.06:  # cuts the leaves: refused by the Python layer
+                out = [leaves[0] + 2 * self.rnd.randrange(n - count + 1), count]
+        if host or not _cuts(out, leaves):
+            self.maybe_plant(f, "tree", self.spots(leaves, self.rnd))
+        self.emit("tree", f, slot=slot, leaves=leaves, levels=levels, out=out, host=host)
+        return first
+
     def g_format(self, f, small):
         self.mont[f] = not self.mont[f] if self.rnd.random() < 0.8 else self.mont[f]
         self.emit("format", f, mont=self.mont[f])
@@ -801,10 +995,11 @@ class _Gen:
             self.emit("hook", 0, name=name, value=value)
 
     def g_close(self, f, small, what=None):
-        live = [(w, s) for w, d in (("mat", self.mats[f]), ("tab", self.tabs[f])) for s in sorted(d) if what in (None, w)]
+        kept = {"mat": self.mats, "tab": self.tabs, "hash": self.hashes}
+        live = [(w, s) for w, d in kept.items() for s in sorted(d[f]) if what in (None, w)]
         if live:
             w, s = self.rnd.choice(live)
-            del (self.mats if w == "mat" else self.tabs)[f][s]
+            del kept[w][f][s]
             self.emit("close", f, what=w, slot=s)
 
     def g_stream(self, f, small):

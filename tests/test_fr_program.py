@@ -10,21 +10,22 @@ import os
 import pytest
 
 from tests import fr_program as P
-from tests import frlook_model
-from tests.test_gpu_fr_fuzz import COMMITTED
+from tests import frhash_model, frlook_model, frvec_model
+from tests.test_gpu_fr_fuzz import COMMITTED, SECOND
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("fuzz_fr", os.path.join(ROOT, "tools", "fuzz_fr.py"))
 fuzz_fr = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(fuzz_fr)
 
-VECTOR_KEYS = ("a", "b", "c", "out", "x", "v", "t", "scale")
+VECTOR_KEYS = ("a", "b", "c", "out", "x", "v", "t", "scale", "leaves")
 
 
 @pytest.fixture(scope="module")
 def programs():
     """every committed program: [(fields, seed, case, steps)], generated once"""
-    return [(fields.split(","), seed, case, P.program(seed, case, fields.split(","))) for fields, (seed, cases) in COMMITTED.items() for case in range(cases)]
+    return [(fields.split(","), seed, case, P.program(seed, case, fields.split(","))) for fields, (seed, cases) in list(COMMITTED.items()) + list(SECOND.items())
+            for case in range(cases)]
 
 
 def test_field_constants_agree_with_the_oracles():
@@ -120,6 +121,80 @@ def test_two_fields_take_turns(programs):
             switches += sum(x != y for x, y in zip(turns, turns[1:]))
             pairs += len(turns) - 1
     assert pairs > 500 and 2 * switches > pairs, (switches, pairs)
+
+
+def hash_calls(steps):
+    """the calls of libmsm_frhash of a program, in order: dicts of the step's index and kind, its field index, the handle (its `poseidon` step's
+    index) and width, the field's form and the stream at the call, and whether it is a host-form call, cuts its input (refused by the Python
+    layer: the library is not called) or follows a planted value (refused by the library)"""
+    mont, side, made, out = {}, False, {}, []
+    for i, (kind, f, a) in enumerate(steps):
+        if kind == "format":
+            mont[f] = a["mont"]
+        elif kind == "stream":
+            side = a["side"]
+        elif kind == "poseidon":
+            made[f, a["slot"]] = (i, a["t"])
+        elif kind in P.HASH_CALLS:
+            handle, t = made[f, a["slot"]]
+            out.append({"index": i, "kind": kind, "f": f, "handle": handle, "t": t, "mont": bool(mont.get(f)), "side": side, "host": a["host"],
+                        "cut": P.hash_cut(steps[i]), "planted": steps[i - 1][0] == "plant" and not steps[i - 1][2].get("quiet")})
+    return out
+
+
+def test_hashing_reaches_each_fields_tidy_boundary(programs):
+    """the widest state that goes into the S-box untidied and the narrowest that is tidied first, per field, in calls that compute"""
+    used = {}
+    for fields, _, _, steps in programs:
+        for c in hash_calls(steps):
+            if c["kind"] in ("permute", "sponge") and not c["cut"] and not c["planted"]:
+                used[fields[c["f"]], c["t"]] = used.get((fields[c["f"]], c["t"]), 0) + 1
+    for field, widths in P.HASH_BOUNDARY.items():
+        assert all(used.get((field, t), 0) >= 3 for t in widths), (field, used)
+    assert {t for _, t in used} == set(P.HASH_WIDTHS)
+
+
+def test_hash_handles_meet_both_forms_both_streams_and_one_another(programs):
+    """a handle's constants go to the device inside its FIRST call, whichever form and stream that has; the form is a flag of every later call;
+    the handles of one device share the library's state"""
+    first_form, first_side, forms, after_another, unused_closed = {False: 0, True: 0}, {False: 0, True: 0}, {}, 0, 0
+    for n, (_, _, _, steps) in enumerate(programs):
+        calls = [c for c in hash_calls(steps) if not c["cut"]]  # (a cut never reaches the library)
+        for c in calls:
+            key = (n, c["handle"])
+            if key not in forms:
+                first_form[c["mont"]] += 1
+                first_side[c["side"]] += 1
+            forms.setdefault(key, set()).add(c["mont"])
+        for before, c in zip(calls, calls[1:]):
+            after_another += c["index"] == before["index"] + 1 and (before["f"], before["handle"]) != (c["f"], c["handle"]) and before["t"] != c["t"]
+        made = {}
+        for i, (kind, f, a) in enumerate(steps):
+            if kind == "poseidon":
+                made[f, a["slot"]] = i
+            elif kind == "close" and a["what"] == "hash":
+                unused_closed += (n, made[f, a["slot"]]) not in forms
+    assert min(first_form.values()) >= 5 and min(first_side.values()) >= 5, (first_form, first_side)
+    assert sum(len(v) == 2 for v in forms.values()) >= 5
+    assert after_another >= 5, after_another  # the very next step, on another handle of another width
+    assert unused_closed >= 1  # a handle that never went to the device is closed too
+
+
+def test_host_form_hashing_sees_large_then_small_and_refusals_stay_rare(programs):
+    """the staging buffer of the host forms only grows: a small host-form call right behind a large one.  And no more than a fifth of the calls
+    are refused -- by a planted value or a cut --, so that the refusals do not hide the paths that compute."""
+    pairs = refused = total = 0
+    for _, _, _, steps in programs:
+        sized = [s for s in P.sizes(steps) if s[1] in P.HASH_CALLS and steps[s[0]][2]["host"]]
+        pairs += sum(n >= P.LARGE and m <= P.SMALL and kind == kind2 for (_, kind, _, n), (_, kind2, _, m) in zip(sized, sized[1:]))  # (no host-form call between)
+        calls = hash_calls(steps)
+        total += len(calls)
+        refused += sum(c["cut"] or c["planted"] for c in calls)
+    quiet = [nxt for _, _, _, steps in programs for s, nxt in zip(steps, steps[1:]) if s[0] == "plant" and s[2].get("quiet")]
+    assert all(s[0] == "sponge" for s in quiet) and sum(s[2]["host"] for s in quiet) >= 5 and sum(not s[2]["host"] for s in quiet) >= 5  # the padding is not read
+    assert pairs >= 1, pairs
+    assert total > 500 and 5 * refused <= total, (refused, total)
+    assert 20 * refused >= total  # (but they are there)
 
 
 def test_the_loop_passes_a_backend_that_is_the_model(capsys):
@@ -294,8 +369,146 @@ class OneByteTooMany(Faulty):
         return host
 
 
+class HashFault(Faulty):
+    """a fault in libmsm_frhash: answer(kind, f, a, p, right) -> the wrong plain values of a call that computes, or None where the fault does
+    not show; they go where the right ones went (the output range, or the host bytes)"""
+
+    def answer(self, kind, f, a, p, right):
+        return None
+
+    def decode(self, f, data):
+        """bytes in the field's current form -> plain values"""
+        stored = frvec_model.from_bytes(data)
+        return frvec_model.mont(stored, self.m.r[f], back=True) if self.m.mont[f] else stored
+
+    def faulty(self, kind, f, a):
+        host = self.plain_call(kind, f, a)  # (a refused call raises here: nothing was computed)
+        if kind not in P.HASH_CALLS:
+            return host
+        dst = a["leaves" if kind == "tree" else "a"] if a["out"] is None else a["out"]
+        right = host if a["host"] else self.m.raw(f, dst)
+        wrong = self.answer(kind, f, a, self.m.hashes[f][a["slot"]], right)
+        if wrong is None or self.m.enc(f, wrong) == right:
+            return host
+        self.fired()
+        if a["host"]:
+            return self.m.enc(f, wrong)
+        self.m.put(f, dst[0], self.m.enc(f, wrong))
+        return host
+
+
+class HandleAnswersForTheOneBefore(HashFault):
+    """a handle that answers with the constants of the handle created before it (here: with constants of its own shape from that one's seed)"""
+    fields_to_run = "bn254,grumpkin"
+
+    def fresh(self):
+        self.seed_before, self.stale = {}, {}
+
+    def faulty(self, kind, f, a):
+        if kind == "poseidon":
+            if f in self.seed_before:
+                self.stale[f, a["slot"]] = self.seed_before[f]
+            else:
+                self.stale.pop((f, a["slot"]), None)
+            self.seed_before[f] = a["seed"]
+        return super().faulty(kind, f, a)
+
+    def answer(self, kind, f, a, p, right):
+        if (f, a["slot"]) not in self.stale or (kind == "permute" and a["out"] is None and not a["host"]):  # (in place the input is gone: it shows in every other call)
+            return None
+        rc, mds = P.poseidon_constants(self.stale[f, a["slot"]], p.t, p.full_rounds, p.partial_rounds, p.r)
+        other = frhash_model.Poseidon(p.r, p.t, p.full_rounds, p.partial_rounds, rc, mds, p.capacity, p.capacity_at, p.out_at)
+        v = self.m.plain(f, a["leaves" if kind == "tree" else "a"])
+        if kind == "permute":
+            return [x for i in range(0, len(v), p.t) for x in other.permute(v[i:i + p.t])]
+        if kind == "sponge":
+            stride = len(v) // a["batch"]
+            return [other.hash(v[k * stride:k * stride + a["length"]]) for k in range(a["batch"])]
+        return other.merkle_chain(v[0], a["levels"]) if p.t == 2 else [x for level in other.merkle(v) for x in level]
+
+
+class SpongeReadsThePadding(HashFault):
+    """a sponge that reads one scalar of the padding behind `length` as data when the last block is short"""
+    fields_to_run = "pallas"
+
+    def answer(self, kind, f, a, p, right):
+        stride = a["a"][1] // a["batch"] if kind == "sponge" else 0
+        if kind != "sponge" or a["length"] % (p.t - 1) == 0 or stride == a["length"]:
+            return None
+        v = self.m.plain(f, a["a"])
+        return [p.hash(v[k * stride:k * stride + a["length"] + 1]) for k in range(a["batch"])]
+
+
+class SpongeTakesTheOtherFormsConstants(HashFault):
+    """a sponge that converts with the constants of the a * 2^256 form whatever the call's flag says: canonical data hashed as if they were not"""
+    fields_to_run = "bn254,bls12_381"
+
+    def answer(self, kind, f, a, p, right):
+        if kind != "sponge" or self.m.mont[f]:
+            return None
+        v, stride = frvec_model.mont(self.m.stored(f, a["a"]), p.r, back=True), a["a"][1] // a["batch"]
+        return frvec_model.mont([p.hash(v[k * stride:k * stride + a["length"]]) for k in range(a["batch"])], p.r)
+
+
+class SecondLevelFromTheLeaves(HashFault):
+    """a tree whose second level is hashed from the leaves instead of from the first level"""
+    fields_to_run = "grumpkin"
+
+    def answer(self, kind, f, a, p, right):
+        arity = p.t - 1
+        if kind != "tree" or arity == 1 or a["leaves"][1] < arity * arity:
+            return None
+        v = self.m.plain(f, a["leaves"])
+        levels = [[p.hash(v[arity * j:arity * j + arity]) for j in range(len(v) // arity)]]
+        levels.append(levels[0][:len(levels[0]) // arity])  # (the hashes of the first leaves once more)
+        while len(levels[-1]) > 1:
+            levels.append([p.hash(levels[-1][arity * j:arity * j + arity]) for j in range(len(levels[-1]) // arity)])
+        return [x for level in levels for x in level]
+
+
+class HostOutputFromTheStaleSpot(HashFault):
+    """a host-form call whose output comes from where the previous, larger call's output lay in the staging area (the input at its start, the
+    output behind it; a permutation in place)"""
+    fields_to_run = "vesta"
+
+    def fresh(self):
+        self.staging, self.out_at = bytearray(), 0
+
+    def faulty(self, kind, f, a):
+        self.operand = self.m.raw(f, a["leaves" if kind == "tree" else "a"]) if kind in P.HASH_CALLS and a["host"] else None  # (before an in-place call changes it)
+        return super().faulty(kind, f, a)
+
+    def answer(self, kind, f, a, p, right):
+        if not a["host"]:
+            return None
+        if kind == "sponge":  # (of the last row only what is read)
+            self.operand = self.operand[:len(self.operand) - 32 * (a["a"][1] // a["batch"] - a["length"])]
+        at = 0 if kind == "permute" else len(self.operand)
+        need = at + len(right)
+        self.staging.extend(bytes(max(need - len(self.staging), 0)))
+        self.staging[:len(self.operand)] = self.operand
+        self.staging[at:need] = right
+        before, self.out_at = self.out_at, at
+        if before <= at:
+            return None
+        return self.decode(f, bytes(self.staging[before:before + len(right)]).ljust(len(right), b"\0"))  # (canonical scalars: enc() gives these bytes again)
+
+
+class FirstTidiedWidthGoesWrong(HashFault):
+    """a permutation at the field's first tidied width computed with one S-box input unreduced: some wrong but canonical value at exactly that
+    width (here: the state's first element gives way to its second)"""
+    fields_to_run = "bls12_381"
+
+    def answer(self, kind, f, a, p, right):
+        if kind != "permute" or p.t != P.HASH_BOUNDARY[self.m.fields[f]][1]:
+            return None
+        plain = self.decode(f, right)
+        return [plain[1]] + plain[1:]
+
+
 @pytest.mark.parametrize("fault", [ScanTileBoundary, ScratchKeepsTheTail, NttReusesTheTable, TableAnswersForAnother, ErrorWordNotCleared, SecondHalfFromFurtherOn,
-                                   MontComputedAsCanonical, OneByteTooMany], ids=lambda c: c.__name__)
+                                   MontComputedAsCanonical, OneByteTooMany, HandleAnswersForTheOneBefore, SpongeReadsThePadding, SpongeTakesTheOtherFormsConstants, SecondLevelFromTheLeaves,
+                                   HostOutputFromTheStaleSpot, FirstTidiedWidthGoesWrong], ids=lambda c: c.__name__)
 def test_a_planted_fault_is_caught_at_its_step_and_replays(fault):
     fields = fault.fields_to_run.split(",")
     seed, cases = COMMITTED[fault.fields_to_run]

@@ -1,7 +1,8 @@
 """libmsm_frhash.so's Poseidon on the CPU: the pure-Python model (tests/frhash_model.py) against known answers and against the generator of
 msm_webgpu_amd.api, and a stand-alone program (tests/host_harness/frhash_harness.cpp) that runs the plan of csrc/frhash_plan.h and, lane by
 lane in serial order, the functions the kernels call (csrc/frhash_kernels.h), compiled with g++ -DFQ_CHECK so that every limb and value bound
-is asserted, against the model: permutations, sponges and trees, the five fields, both data forms, t in {2, 3, 5, 9, 12}.  Host logic only."""
+is asserted, against the model: permutations, sponges and trees, the five fields, both data forms, t in {2, 3, 5, 9, 12} and, per field, the
+widest state that goes into the S-box untidied, the narrowest that is tidied first (4 and 5, 7 and 8, or 9 and 10) and t = 10.  Host logic only."""
 import os
 import subprocess
 
@@ -13,6 +14,9 @@ from tests.util import rng
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("bn254", "grumpkin", "pallas", "vesta", "bls12_381")
 WIDTHS = (2, 3, 5, 9, 12)
+# frh_permute tidies the S-box input iff (t + 4)^2 > FQ_HEADROOM (70 for BLS12-381, 127 for Pallas and Vesta, 169 for BN254 and Grumpkin, where
+# t = 9 meets the bound with equality): the last width that is not tidied and the first that is
+EDGE = {"bls12_381": (4, 5), "pallas": (7, 8), "vesta": (7, 8), "bn254": (9, 10), "grumpkin": (9, 10)}
 R_BN254 = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
@@ -131,9 +135,35 @@ def harness(request, tmp_path_factory):
     return request.param, _build(tmp, request.param), tmp
 
 
+def edge_widths(field):
+    """the field's two widths at the tidy boundary and the even width 10, as far as WIDTHS does not hold them"""
+    return sorted(set(EDGE[field] + (10,)) - set(WIDTHS))
+
+
+def test_the_tidy_boundary_is_where_the_constants_put_it():
+    import re
+
+    for field, (last, first) in EDGE.items():
+        text = open(os.path.join(ROOT, "msm-webgpu_amd", "csrc", "fr_%s_constants.h" % field)).read()
+        headroom = int(re.search(r"constexpr int FQ_HEADROOM = (\d+);", text).group(1))
+        assert headroom == (1 << 261) // _r(field) and first == last + 1 and (last + 4) ** 2 <= headroom < (first + 4) ** 2, (field, headroom)
+    assert (EDGE["bn254"][0] + 4) ** 2 == (1 << 261) // _r("bn254")  # met with equality
+    assert [edge_widths(f) for f in FIELDS] == [[10], [10], [7, 8, 10], [7, 8, 10], [4, 10]]
+
+
 @pytest.mark.parametrize("mont", [False, True], ids=["canonical", "mont256"])
 @pytest.mark.parametrize("t", WIDTHS)
 def test_permutations_against_the_model(harness, t, mont):
+    _permutations(harness, t, mont)
+
+
+@pytest.mark.parametrize("mont", [False, True], ids=["canonical", "mont256"])
+def test_permutations_at_the_tidy_boundary(harness, mont):
+    for t in edge_widths(harness[0]):
+        _permutations(harness, t, mont)
+
+
+def _permutations(harness, t, mont):
     field, exe, tmp = harness
     r, rnd = _r(field), rng(400 + t)
     p = M.standard(r, t)
@@ -148,6 +178,16 @@ def test_permutations_against_the_model(harness, t, mont):
 @pytest.mark.parametrize("t", WIDTHS)
 def test_the_worst_case_of_the_bounds(harness, t):
     """constants, matrix and state all r - 1: every lazy sum is as large as it gets; then no partial rounds, and two full rounds alone"""
+    _worst_case(harness, t)
+
+
+def test_the_worst_case_at_the_tidy_boundary(harness):
+    """the same where the S-box input is as large as it may be without being tidied -- (t + 4)^2 = 64 of 70, 121 of 127, 169 of 169 -- and one wider"""
+    for t in sorted(set(EDGE[harness[0]] + (10,))):
+        _worst_case(harness, t)
+
+
+def _worst_case(harness, t):
     field, exe, tmp = harness
     r = _r(field)
     for rf, rp in ((8, M.DEFAULT_PARTIAL[t]), (8, 0), (2, 0), (16, 128)):
@@ -163,6 +203,15 @@ def test_the_worst_case_of_the_bounds(harness, t):
 
 @pytest.mark.parametrize("t", WIDTHS)
 def test_sponges_against_the_model(harness, t):
+    _sponges(harness, t)
+
+
+def test_sponges_at_the_tidy_boundary(harness):
+    for t in edge_widths(harness[0]):
+        _sponges(harness, t)
+
+
+def _sponges(harness, t):
     field, exe, tmp = harness
     r, rnd = _r(field), rng(500 + t)
     conventions = ((0, 0, 0), ((3 << 64) % r, t - 1, 0), ((1 << (t - 1)) - 1, 0, 1 % t))

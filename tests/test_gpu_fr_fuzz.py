@@ -1,12 +1,19 @@
-"""Randomised differential test of the seven scalar-field libraries as chained programs on shared state: tools/fuzz_fr.py runs the programs of
+"""Randomised differential test of the eight scalar-field libraries as chained programs on shared state: tools/fuzz_fr.py runs the programs of
 tests/fr_program.py on the device and compares every range a step wrote, every host value it returned and at last the whole arena with the model.
 
 Case counts.  The time of a test is the Python model's, not the device's.  The model side alone (tools/fuzz_fr.py's loop against
 fr_program.ModelBackend, i.e. the model run twice) was measured on a machine without a GPU for every committed seed, and the count of each
-test chosen so that it stays at or below about 3 s there:
-    bn254 (seed 20261101) 30 cases 2.3 s; pallas (20261102) 30: 2.9 s; vesta (20261103) 28: 2.9 s (29: 3.4 s); bls12_381 (20261104) 15: 2.7 s
-    (16: 3.0 s); grumpkin (20261105) 40: 1.7 s; bn254,bls12_381 (20261106) 30: 2.7 s; pallas,vesta (20261107) 25: 2.8 s (30: 4.2 s);
-    bn254,grumpkin (20261108) 40: 2.9 s.  The slowest single case took 1.6 s (its model steps at 4097 scalars).
+test chosen so that it stays at or below about 3 s there.  Measured again with libmsm_frhash's steps among the programs, three runs each, the
+median first (the machine's own noise is a fifth of a figure):
+    bn254 (seed 20261101) 30 cases 2.7 s (2.4 .. 2.8); pallas (20261102) 30: 2.7 s (2.6 .. 3.1); vesta (20261103) 28: 2.4 s (2.1 .. 3.0);
+    bls12_381 (20261104) 15: 1.2 s; grumpkin (20261105) 40: 2.8 s (2.4 .. 2.9).
+The three entries over two fields went past the limit at their old counts -- bn254,bls12_381 (20261106) 30: 3.1 .. 4.0 s; pallas,vesta
+(20261107) 25: 3.2 .. 3.5 s; bn254,grumpkin (20261108) 40: 3.1 .. 3.5 s -- and not for the Poseidon steps, whose model is 0.3 to 0.7 s of each and
+is bounded by fr_program.HASH_WORK: the slowest steps are the model's inverses and folds at 4097 scalars.  A tighter bound does not bring them
+back, so each runs as two tests with two seeds and no fewer cases in all:
+    bn254,bls12_381 (20261106) 20: 2.5 s (2.1 .. 3.1) and (20261110) 12: 1.8 s (1.7 .. 2.0); pallas,vesta (20261107) 20: 2.3 s (2.0 .. 2.6) and
+    (20261109) 12: 0.9 s; bn254,grumpkin (20261108) 28: 2.2 s (1.9 .. 3.0) and (20261111) 14: 1.6 s (1.4 .. 1.6).
+The slowest single case took 0.7 s.
 Nobody has measured the device side of these counts on its own: the device work is milliseconds, and a test's time is the model's on whatever
 CPU the GPU machine has."""
 import os
@@ -25,14 +32,16 @@ COMMITTED = {
     "vesta": (20261103, 28),
     "bls12_381": (20261104, 15),
     "grumpkin": (20261105, 40),
-    "bn254,bls12_381": (20261106, 30),
-    "pallas,vesta": (20261107, 25),
-    "bn254,grumpkin": (20261108, 40),
+    "bn254,bls12_381": (20261106, 20),
+    "pallas,vesta": (20261107, 20),
+    "bn254,grumpkin": (20261108, 28),
 }
+# an entry whose model time went past the limit with one seed runs as two tests, the second with a seed of its own; together no fewer cases than before
+SECOND = {"pallas,vesta": (20261109, 12), "bn254,bls12_381": (20261110, 12), "bn254,grumpkin": (20261111, 14)}
 
 
-def _fuzz(capsys, fields):
-    seed, cases = COMMITTED[fields]
+def _fuzz(capsys, fields, committed=COMMITTED):
+    seed, cases = committed[fields]
     argv = sys.argv
     sys.argv = ["fuzz_fr.py", str(cases), str(seed), fields]
     try:
@@ -51,3 +60,8 @@ def test_fuzz_programs_over_one_field(built, capsys, field):
 def test_fuzz_programs_over_two_fields(built, capsys, fields):
     """the two fields share every library's per-device state: a step on one follows a step on the other more often than not"""
     _fuzz(capsys, fields)
+
+
+@pytest.mark.parametrize("fields", sorted(SECOND))
+def test_fuzz_programs_of_a_second_seed(built, capsys, fields):
+    _fuzz(capsys, fields, SECOND)

@@ -1,9 +1,10 @@
 """Poseidon on the device (include/msm_frhash.h; MsmContext.poseidon, scalars_permute, scalars_hash, merkle_tree) against the pure-Python model
-(tests/frhash_model.py), byte for byte: batches of 1, 63, 64, 65 and 257 permutations at t = 2, 3, 5, 9 and 12 on BN254 and BLS12-381 and at
-t = 3 on the other three fields, both data forms, in place and out of place, and again with four lanes to a workgroup; sponges of every length
-at which the last block is empty, short or full, with a stride whose padding is not below r and must not be read, under the three capacity
-conventions; trees of arity 2, 4, 8, 11 and 1, every node compared, with and without the short tile; the known answer; the rejection of a
-value >= r at the first, a middle and the last position with a correct call right behind it; the same bytes on a second run."""
+(tests/frhash_model.py), byte for byte: batches of 1, 63, 64, 65 and 257 permutations at t = 2, 3, 5, 9 and 12 on BN254 and BLS12-381, at
+t = 3 on the other three fields and at one width of their tidy boundary each, both data forms, in place and out of place, and again with four
+lanes to a workgroup; every field's two widths on either side of the width from which the S-box input is tidied, at either alignment; sponges
+of every length at which the last block is empty, short or full, with a stride whose padding is not below r and must not be read, under the
+three capacity conventions; trees of arity 2, 4, 8, 11 and 1, every node compared, with and without the short tile; the known answer; the
+rejection of a value >= r at the first, a middle and the last position with a correct call right behind it; the same bytes on a second run."""
 import pytest
 import torch
 
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ERR_NONCANONICAL = -4
 WIDTHS = (2, 3, 5, 9, 12)
 COUNTS = (1, 63, 64, 65, 257)
-CASES = [(c, t) for c in ("bn254", "bls12_381") for t in WIDTHS] + [(c, 3) for c in ("grumpkin", "pallas", "vesta")]
+CASES = [(c, t) for c in ("bn254", "bls12_381") for t in WIDTHS] + [(c, 3) for c in ("grumpkin", "pallas", "vesta")] + [("grumpkin", 9), ("pallas", 7), ("vesta", 8)]
 
 
 @pytest.fixture(scope="module")
@@ -97,6 +98,66 @@ def test_permutations_of_every_count_and_form(contexts, curve, t):
             api.frhash_test_tile(0)
             assert tuple(ctx.scalars_permute(h, dev(form(flat(states[:3]), r, mont))).shape) == (3, t, 32)
             assert ctx.scalars_permute(h, M.to_bytes(form(flat(states[:5]), r, mont))) == M.to_bytes(form(flat(images[:5]), r, mont))  # the host form
+
+
+# ---- each field's tidy boundary -------------------------------------------------------------------------------------------------------------------
+# frh_permute tidies the S-box input iff (t + 4)^2 > FQ_HEADROOM (70, 127, 127, 169, 169): the last width that is not tidied, the first that is
+EDGE = {"bls12_381": (4, 5), "pallas": (7, 8), "vesta": (7, 8), "bn254": (9, 10), "grumpkin": (9, 10)}
+EDGES = [(c, t) for c, widths in EDGE.items() for t in widths]
+
+
+def shifted(data, shift, around=0):
+    """the bytes on the device, `shift` (0 or 16) bytes into a 32-byte-aligned tensor, with `around` bytes of 0xFF on either side: (the whole, the view)"""
+    whole = torch.full((shift + 2 * around + len(data),), 0xFF, dtype=torch.uint8, device="cuda")
+    assert whole.data_ptr() % 32 == 0
+    view = whole[shift + around:shift + around + len(data)]
+    view.copy_(torch.frombuffer(bytearray(data), dtype=torch.uint8))
+    return whole, view
+
+
+@pytest.mark.parametrize("curve,t", EDGES, ids=["%s-t%d" % c for c in EDGES])
+def test_the_widths_on_either_side_of_the_tidy_boundary(contexts, curve, t):
+    """The device multiplies through csrc/fq29_asm.h, which the host program's FQ_CHECK run does not: the widest state whose S-box input is squared
+    as it is, (t + 4)^2 of FQ_HEADROOM (for BN254 and Grumpkin at t = 9 all of it), and the next one, on the device.  State 0 is all r - 1, state
+    1 all 0; the standard parameters, and constants and matrix all r - 1 with rounds (2, 1); 1 and 65 states; both forms; in place, and out of
+    place into 0xFF with the 32 bytes on either side compared; operands at 0 and at 16 mod 32; 64 and four lanes to a workgroup.  The sponges
+    take 2 (t - 1) + 1 elements, under halo2's convention on canonical data and neptune's on a * 2^256.  The model's time is the test's: 65
+    permutations and twice 17 sponges of three blocks with the standard rounds, 65 of each with three rounds, and the standard parameters
+    themselves -- 1.3 s at t = 10 on a CPU without a GPU, 0.4 s of it the parameters."""
+    r, rnd = api.SCALAR_FIELDS[curve], rng(1400 + t)
+    length = 2 * (t - 1) + 1
+    states = [[r - 1] * t, [0] * t] + [[rnd.randrange(r) for _ in range(t)] for _ in range(63)]
+    rows = [[r - 1] * length, [0] * length] + [[rnd.randrange(r) for _ in range(length)] for _ in range(63)]
+    rc, mds = M.parameters(r, t)
+    shapes = ((8, M.DEFAULT_PARTIAL[t], rc, mds, 17), (2, 1, [r - 1] * (3 * t), [[r - 1] * t] * t, 65))
+    for rf, rp, rc, mds, n_rows in shapes:
+        images = None
+        for mont in (False, True):
+            convention = dict(capacity=(1 << (t - 1)) - 1, capacity_at=0, out_at=1) if mont else dict(capacity=(length << 64) % r, capacity_at=t - 1, out_at=0)
+            p = M.Poseidon(r, t, rf, rp, rc, mds, **convention)
+            images = images or [p.permute(s) for s in states]
+            hashes = [p.hash(row) for row in rows[:n_rows]]
+            ctx = contexts(curve, mont)
+            with ctx.poseidon(t, rf, rp, round_constants=list(rc), mds=[list(row) for row in mds], **convention) as h:
+                for tile in (0, 4):
+                    api.frhash_test_tile(tile)
+                    for n in (1, 65):
+                        for shift in (0, 16):
+                            where = (curve, t, rf, rp, mont, tile, n, shift)
+                            want = M.to_bytes(form(flat(images[:n]), r, mont))
+                            _, src = shifted(M.to_bytes(form(flat(states[:n]), r, mont)), shift)
+                            whole, out = shifted(bytes(len(want)), shift, around=32)
+                            assert ctx.scalars_permute(h, src, out=out).data_ptr() == out.data_ptr() and src.data_ptr() % 32 == shift
+                            assert raw(whole) == b"\xff" * (shift + 32) + want + b"\xff" * 32, where
+                            assert raw(src) == M.to_bytes(form(flat(states[:n]), r, mont)), where
+                            ctx.scalars_permute(h, src, out=src)
+                            assert raw(src) == want, where + ("in place",)
+                            k = min(n, n_rows)
+                            _, a = shifted(M.to_bytes(form(flat(rows[:k]), r, mont)), shift)
+                            whole, out = shifted(bytes(32 * k), shift, around=32)
+                            ctx.scalars_hash(h, a, length, batch=k, out=out)
+                            assert raw(whole) == b"\xff" * (shift + 32) + M.to_bytes(form(hashes[:k], r, mont)) + b"\xff" * 32, where + ("sponge",)
+                api.frhash_test_tile(0)
 
 
 def test_the_hash_is_of_the_values(contexts):

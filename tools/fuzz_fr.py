@@ -1,8 +1,10 @@
-"""Randomised differential test of the seven scalar-field libraries as CHAINED programs on shared state (tests/fr_program.py): random steps over
+"""Randomised differential test of the eight scalar-field libraries as CHAINED programs on shared state (tests/fr_program.py): random steps over
 one or two fields in one arena per field -- every entry point of the scalars_* section of api.py, in place or into another range, at starts of 0 and
 16 mod 32, after a larger call, after another field's call, after a refused call, under both scalar forms, with several test hooks set at once,
-with matrices and lookup tables kept alive across all of it.  After EVERY step each range the step wrote and each host value it returned is
-compared byte for byte with the model; at the end of a program the whole arena is.
+with matrices, lookup tables and Poseidon handles kept alive across all of it (a handle's constants go to the device inside its first call, on
+whichever stream and under whichever form that call has; a Poseidon call is a device-form one on ranges of the arena or a host-form one on
+their bytes).  After EVERY step each range the step wrote and each host value it returned is compared byte for byte with the model; at the end
+of a program the whole arena is.
 Usage: python tools/fuzz_fr.py [cases] [seed] [field[,field]] [--case K]   (fields: bn254 pallas vesta bls12_381 grumpkin; --case K replays one case)
 FUZZ_FR_KINDS=a,b,... restricts the step kinds that are drawn (tests/fr_program.py: KINDS)."""
 import os
@@ -112,7 +114,7 @@ class DeviceBackend:
         self.own = torch.cuda.ExternalStream(api.lib().msm_hip_stream(self.ctx[0]._h), device="cuda:0")  # the first context's own stream
         self.side = torch.cuda.Stream(0)
         self.cur = self.default
-        self.mats, self.tabs = [{} for _ in fields], [{} for _ in fields]
+        self.mats, self.tabs, self.hashes = [{} for _ in fields], [{} for _ in fields], [{} for _ in fields]
 
     def t(self, f, rng):
         return None if rng is None else self.arena[f][16 * rng[0]:16 * rng[0] + 32 * rng[1]]
@@ -134,7 +136,7 @@ class DeviceBackend:
         """between programs: no hook, no handle, the canonical form, the default stream"""
         for name in P.HOOKS:
             getattr(self.api, name)(0)
-        for d in self.mats + self.tabs:
+        for d in self.mats + self.tabs + self.hashes:
             for h in d.values():
                 h.close()
             d.clear()
@@ -147,6 +149,11 @@ class DeviceBackend:
         self.torch.cuda.synchronize()
         for c in self.ctx:
             c.close()
+        self.api.frhash_release()
+
+    def host_bytes(self, f, rng):
+        """the bytes of a range, for a host-form call"""
+        return self.t(f, rng).cpu().numpy().tobytes()
 
     def _operand(self, f, v):
         return v if v is None or isinstance(v, int) else self.t(f, v)
@@ -238,6 +245,29 @@ class DeviceBackend:
         return tuple(words) + (tuple(res[-1]),)
 
     @_translated
+    def op_poseidon(self, f, slot, t, full_rounds, partial_rounds, seed, capacity, capacity_at, out_at):
+        rc, mds = P.poseidon_constants(seed, t, full_rounds, partial_rounds, P.FIELD_R[self.fields[f]])
+        self.hashes[f][slot] = self.ctx[f].poseidon(t, full_rounds, partial_rounds, round_constants=rc, mds=mds, capacity=capacity, capacity_at=capacity_at, out_at=out_at)
+
+    @_translated
+    def op_permute(self, f, slot, a, out, host):
+        if host:
+            return self.ctx[f].scalars_permute(self.hashes[f][slot], self.host_bytes(f, a))
+        self.ctx[f].scalars_permute(self.hashes[f][slot], self.t(f, a), out=self.t(f, a if out is None else out))
+
+    @_translated
+    def op_sponge(self, f, slot, a, batch, length, out, host):
+        if host:
+            return self.ctx[f].scalars_hash(self.hashes[f][slot], self.host_bytes(f, a), length, batch=batch)
+        self.ctx[f].scalars_hash(self.hashes[f][slot], self.t(f, a), length, batch=batch, out=self.t(f, out))
+
+    @_translated
+    def op_tree(self, f, slot, leaves, levels, out, host):
+        if host:
+            return self.ctx[f].merkle_tree(self.hashes[f][slot], self.host_bytes(f, leaves), levels=levels)
+        self.ctx[f].merkle_tree(self.hashes[f][slot], self.t(f, leaves), out=self.t(f, out), levels=levels)
+
+    @_translated
     def op_format(self, f, mont):
         self.ctx[f].set_scalar_format(mont256=mont)
 
@@ -247,12 +277,12 @@ class DeviceBackend:
 
     @_translated
     def op_close(self, f, what, slot):
-        (self.mats if what == "mat" else self.tabs)[f].pop(slot).close()
+        {"mat": self.mats, "tab": self.tabs, "hash": self.hashes}[what][f].pop(slot).close()
 
     def op_stream(self, f, side):
         self._switch(self.side if side else self.own)
 
-    def op_plant(self, f, at, value):
+    def op_plant(self, f, at, value, quiet=False):
         self.write(f, at, value.to_bytes(32, "little"))
 
 
