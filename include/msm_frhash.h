@@ -14,6 +14,22 @@
  * them, so `alpha` is carried and 5 is the one value accepted.  The library is PARAMETER-AGNOSTIC: constants and matrix are the caller's
  * (msm_webgpu_amd.api.poseidon_parameters generates the Poseidon paper's); nothing is built in.
  *
+ * Poseidon2 (Grassi, Khovratovich, Schofnegger 2023) is the second permutation, chosen with MSM_FRHASH_POSEIDON2 when the handle is created and
+ * served by every call below unchanged: sponge, tree, both data forms, the five fields, the check against r.  Width t in {2, 3, 4, 8, 12} and no
+ * other, R_F even and R_P within the limits above, S-box x^5, round constants rc[R_F t + R_P] in the order of their use -- t for each of the
+ * first R_F / 2 external rounds, then one for each internal round, then t for each of the last R_F / 2 --, and a vector mu[t]:
+ *     s = M_E s                                                                      (the initial linear layer)
+ *     R_F / 2 times:  s[i] += rc[..] for all i;  s[i] = s[i]^5 for all i;  s = M_E s
+ *     R_P times:      s[0] += rc[..];  s[0] = s[0]^5;  s[i] = mu[i] s[i] + sum_j s[j]  (the sum taken before any s[i] changes)
+ *     R_F / 2 times:  as the first R_F / 2
+ * M_E: for t = 2 and t = 3, out[i] = s[i] + sum_j s[j], that is circ(2, 1) and circ(2, 1, 1).  For t = 4 it is
+ * M4 = [[5, 7, 1, 3], [4, 6, 1, 1], [1, 3, 5, 7], [1, 1, 4, 6]].  For t = 8 and t = 12, M4 is applied to every block of four and then the sum,
+ * over all blocks, of the elements at position i mod 4 is added to element i: circ(2 M4, M4, ..).  The internal layer is M_I = J + diag(mu), J
+ * the all-ones matrix.  NOTE WHAT mu IS: the internal matrix's diagonal MINUS ONE -- what HorizenLabs' parameter files call
+ * mat_internal_diag_m_1 and Barretenberg internal_matrix_diagonal; the matrix's true diagonal is mu[i] + 1.  Handing over the true diagonal
+ * computes another permutation and no check can tell.  Constants are the caller's here too: no published set is built in, and none is generated.
+ * Barretenberg's sponge is the convention (L * 2^64, t - 1, 0) below.  The feed-forward compression P(x) + x is not offered.
+ *
  * Data.  A scalar is 32 little-endian bytes: a canonical integer below r, or -- MSM_FRHASH_MONT256 -- a * 2^256 mod r; results are in the form
  * of the input and canonical.  THE HASH IS OF THE VALUES: a canonical vector and its a * 2^256 mod r image hash to each other's images.
  * Round constants, matrix and `capacity` are canonical integers below r in BOTH forms.  Every element a lane reads is compared with r by
@@ -35,7 +51,7 @@
  * BLS12-381 (4 and 6).  No root of unity is needed, so Grumpkin's scalar field is offered.
  *
  * What the host checks before a device is asked for (MSM_HIP_ERR_INVALID_ARG): the curve; 2 <= t <= MSM_FRHASH_MAX_WIDTH, full_rounds even
- * with 2 <= full_rounds <= MSM_FRHASH_MAX_FULL_ROUNDS, partial_rounds <= MSM_FRHASH_MAX_PARTIAL_ROUNDS, alpha == 5; the flags; the handle;
+ * with 2 <= full_rounds <= MSM_FRHASH_MAX_FULL_ROUNDS, partial_rounds <= MSM_FRHASH_MAX_PARTIAL_ROUNDS, alpha == 5, under MSM_FRHASH_POSEIDON2 t in {2, 3, 4, 8, 12}; the flags; the handle;
  * the ranges given with each call; capacity_at and out_at below t; device pointers 16-byte aligned; the outputs apart from the inputs as
  * each call states.  A round constant, a matrix entry or a `capacity` that is not below r: MSM_HIP_ERR_NONCANONICAL, also before any device.
  *
@@ -46,8 +62,8 @@
  * current device as it found it.  Calls are serialised by the library.  The host forms stage their vectors through device memory.  The
  * library reads no environment setting.
  *
- * How it runs (csrc/frhash_kernels.h): one lane per permutation, its state in a slab of LDS of its own, 64 lanes
- * to a workgroup; a tree is one launch per level.  No kernel waits for another workgroup.
+ * How it runs (csrc/frhash_kernels.h): one lane per permutation, its state in a slab of LDS of its own (Poseidon2:
+ * one copy of it, both linear layers in place), 64 lanes to a workgroup; a tree is one launch per level.  No kernel waits for another workgroup.
  */
 #ifndef MSM_FRHASH_H
 #define MSM_FRHASH_H
@@ -59,6 +75,7 @@ extern "C" {
 #endif
 
 #define MSM_FRHASH_MONT256 2u              /* the data are a * 2^256 mod r; checked against r like canonical data */
+#define MSM_FRHASH_POSEIDON2 16u           /* msm_frhash_create alone: the handle is a Poseidon2 permutation (see above) */
 #define MSM_FRHASH_MAX_WIDTH 12            /* the largest t */
 #define MSM_FRHASH_MAX_FULL_ROUNDS 16      /* the largest R_F */
 #define MSM_FRHASH_MAX_PARTIAL_ROUNDS 128  /* the largest R_P */
@@ -71,7 +88,9 @@ int msm_frhash_abi_version(void); /* 1 */
 
 /* A handle for one permutation over one field.  round_constants: (full_rounds + partial_rounds) * t canonical scalars; mds: t * t canonical
  * scalars, row-major; both HOST memory, read before the call returns.  `device` is where the calls will run and is not touched here.
- * flags: 0 or MSM_FRHASH_MONT256, without effect (the tables are canonical integers in both forms, and a call names its own form). */
+ * flags: 0 or MSM_FRHASH_MONT256, without effect (the tables are canonical integers in both forms, and a call names its own form), and
+ * MSM_FRHASH_POSEIDON2: t is one of 2, 3, 4, 8, 12 (another: MSM_HIP_ERR_INVALID_ARG), round_constants holds full_rounds * t + partial_rounds
+ * scalars in the order of their use, and mds holds the t scalars of mu -- the internal matrix's diagonal minus one. */
 int msm_frhash_create(int curve, int device, uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, uint32_t alpha, const uint8_t* round_constants,
                       const uint8_t* mds, uint32_t flags, msm_frhash** out);
 /* what the handle holds (any pointer may be NULL) */

@@ -468,7 +468,7 @@ class FrLookup:
 
 
 def frhash_lib():
-    """Load libmsm_frhash.so (in-tree; include/msm_frhash.h): Poseidon over the scalar field -- batch permutations, sponges, Merkle trees.  Raises
+    """Load libmsm_frhash.so (in-tree; include/msm_frhash.h): Poseidon and Poseidon2 over the scalar field -- batch permutations, sponges, Merkle trees.  Raises
     if it has not been built (msm-webgpu_amd/build.py builds it beside the other eight)."""
     if "frhash" in _fr_libs:
         return _fr_libs["frhash"]
@@ -563,13 +563,13 @@ def _poseidon_parameters(r, t, full_rounds, partial_rounds):
 
 
 class FrHash:
-    """A Poseidon permutation over a scalar field (msm_frhash_create, include/msm_frhash.h): MsmContext.poseidon makes it,
-    MsmContext.scalars_permute, scalars_hash, merkle_tree and merkle_path use it.  t, full_rounds, partial_rounds: its shape; arity = t - 1;
-    capacity, capacity_at, out_at: the sponge's convention, remembered for the calls.  close() frees it; so does collecting it or leaving a
-    `with` block."""
+    """A Poseidon or Poseidon2 permutation over a scalar field (msm_frhash_create, include/msm_frhash.h): MsmContext.poseidon or
+    MsmContext.poseidon2 makes it, MsmContext.scalars_permute, scalars_hash, merkle_tree and merkle_path use it.  kind: "poseidon" or
+    "poseidon2"; t, full_rounds, partial_rounds: its shape; arity = t - 1; capacity, capacity_at, out_at: the sponge's convention, remembered
+    for the calls.  close() frees it; so does collecting it or leaving a `with` block."""
 
-    def __init__(self, handle, curve, device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at):
-        self._h, self.curve, self.device = handle, curve, device
+    def __init__(self, handle, curve, device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at, kind="poseidon"):
+        self._h, self.curve, self.device, self.kind = handle, curve, device, kind
         self.t, self.full_rounds, self.partial_rounds, self.arity = t, full_rounds, partial_rounds, t - 1
         self.capacity, self.capacity_at, self.out_at = capacity, capacity_at, out_at
 
@@ -1993,9 +1993,42 @@ class MsmContext:
                                               C.cast(C.c_char_p(m_b), C.c_void_p), 0, C.byref(h)), "msm_frhash_create")
         return FrHash(h, self.curve, self.device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at)
 
+    FRHASH_POSEIDON2 = 16  # MSM_FRHASH_POSEIDON2
+    POSEIDON2_WIDTHS = (2, 3, 4, 8, 12)
+
+    def poseidon2(self, t, full_rounds, partial_rounds, round_constants, diagonal, capacity=0, capacity_at=0, out_at=0):
+        """A Poseidon2 permutation of width t in {2, 3, 4, 8, 12} over this context's scalar field -> FrHash with kind == "poseidon2"
+        (msm_frhash_create under MSM_FRHASH_POSEIDON2; include/msm_frhash.h has the definition), which scalars_permute, scalars_hash,
+        merkle_tree and merkle_path take like any other.  round_constants: full_rounds * t + partial_rounds integers in the order of their
+        use (t per external round, one per internal round, t per external round).  diagonal: the t integers mu of the internal layer
+        s[i] = mu[i] * s[i] + sum(s) -- the internal matrix's diagonal MINUS ONE, what the published parameter files call
+        mat_internal_diag_m_1 or internal_matrix_diagonal.  The constants are the caller's: there is no default and no generator.
+        capacity, capacity_at, out_at: as for poseidon; Barretenberg's sponge is (L * 2^64, t - 1, 0).  No device is touched."""
+        r = self._frmle_field("poseidon2")
+        t, full_rounds, partial_rounds = int(t), int(full_rounds), int(partial_rounds)
+        if t not in self.POSEIDON2_WIDTHS or full_rounds % 2 or not 2 <= full_rounds <= self.FRHASH_MAX_FULL_ROUNDS:
+            raise ValueError("a Poseidon2 permutation has t in {2, 3, 4, 8, 12} and an even 2 <= full_rounds <= 16")
+        if not 0 <= partial_rounds <= self.FRHASH_MAX_PARTIAL_ROUNDS:
+            raise ValueError("a permutation has 0 .. 128 partial rounds")
+        round_constants, diagonal = [int(c) for c in round_constants], [int(c) for c in diagonal]
+        if len(round_constants) != full_rounds * t + partial_rounds or len(diagonal) != t:
+            raise ValueError("round_constants holds full_rounds * t + partial_rounds integers and diagonal t")
+        if any(not 0 <= c < r for c in round_constants) or any(not 0 <= c < r for c in diagonal):
+            raise ValueError("round constants and the diagonal must lie in [0, r)")
+        capacity_at, out_at = int(capacity_at), int(out_at)
+        if not 0 <= capacity_at < t or not 0 <= out_at < t:
+            raise ValueError("capacity_at and out_at must lie in [0, t)")
+        capacity = int.from_bytes(self._frpoly_const(capacity, r, "capacity"), "little")
+        rc_b = b"".join(c.to_bytes(32, "little") for c in round_constants)
+        mu_b = b"".join(c.to_bytes(32, "little") for c in diagonal)
+        h = C.c_void_p()
+        _check(frhash_lib().msm_frhash_create(self.curve_id, self.device, t, full_rounds, partial_rounds, 5, C.cast(C.c_char_p(rc_b), C.c_void_p),
+                                              C.cast(C.c_char_p(mu_b), C.c_void_p), self.FRHASH_POSEIDON2, C.byref(h)), "msm_frhash_create")
+        return FrHash(h, self.curve, self.device, t, full_rounds, partial_rounds, capacity, capacity_at, out_at, kind="poseidon2")
+
     def _frhash_handle(self, h):
         if not isinstance(h, FrHash) or not h._h:
-            raise TypeError("h must be an open FrHash (poseidon)")
+            raise TypeError("h must be an open FrHash (poseidon, poseidon2)")
         if SCALAR_FIELDS[h.curve] != SCALAR_FIELDS.get(self.curve) or h.device != self.device:
             raise ValueError("the permutation belongs to the scalar field of %s on device %d" % (h.curve, h.device))
         self._frmle_field("hashing")

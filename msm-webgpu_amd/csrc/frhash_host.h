@@ -29,6 +29,7 @@ struct msm_frhash {
   const FrhashOps* ops = nullptr;
   int device = 0;
   uint32_t t = 0, full_rounds = 0, partial_rounds = 0;
+  uint32_t kind = 0;                    // FRHASH_KIND_*: Poseidon, or Poseidon2 (MSM_FRHASH_POSEIDON2)
   std::vector<uint32_t> h_table;        // what csrc/frhash_plan.h made of the constants
   mutable uint32_t* d_table = nullptr;  // the same on the device, from the first call on
 };
@@ -113,10 +114,11 @@ inline int create_impl(int curve, int device, uint32_t t, uint32_t full_rounds, 
   *out = nullptr;
   if (!ops || device < 0 || !rc || !mds || !shape_ok(t, full_rounds, partial_rounds, alpha, flags)) return MSM_HIP_ERR_INVALID_ARG;
   const Field f(ops->r32);
-  if (!all_below_r(f, rc, (size_t)(full_rounds + partial_rounds) * t) || !all_below_r(f, mds, (size_t)t * t)) return MSM_HIP_ERR_NONCANONICAL;
+  const uint32_t kind = kind_of(flags);
+  if (!all_below_r(f, rc, constants_of(kind, t, full_rounds, partial_rounds)) || !all_below_r(f, mds, matrix_of(kind, t))) return MSM_HIP_ERR_NONCANONICAL;
   msm_frhash* h = new msm_frhash();
-  h->magic = MAGIC, h->ops = ops, h->device = device, h->t = t, h->full_rounds = full_rounds, h->partial_rounds = partial_rounds;
-  plan_table(f, t, full_rounds, partial_rounds, rc, mds, h->h_table);
+  h->magic = MAGIC, h->ops = ops, h->device = device, h->t = t, h->full_rounds = full_rounds, h->partial_rounds = partial_rounds, h->kind = kind;
+  plan_table(f, t, full_rounds, partial_rounds, rc, mds, h->h_table, kind);
   *out = h;
   return MSM_HIP_OK;
 }
@@ -131,7 +133,7 @@ inline int permute_impl(const msm_frhash* h, void* stream, void* out, const void
   Call call(h, stream, host);
   if (call.rc) return call.rc;
   const hipStream_t st = call.st;
-  const FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, n, flags, call.tile);
+  const FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, n, flags, call.tile, h->kind);
   uint32_t* dout = static_cast<uint32_t*>(out);
   const uint32_t* din = static_cast<const uint32_t*>(state);
   if (host) {  // staging: the states, permuted in place
@@ -152,7 +154,7 @@ inline int hash_impl(const msm_frhash* h, void* stream, void* out, const void* a
   if (!host && (misaligned(out) || misaligned(a))) return MSM_HIP_ERR_INVALID_ARG;  // (16-byte vector accesses)
   const size_t span = (rows - 1) * stride + len;
   if (!apart(out, rows * 32, a, span * 32)) return MSM_HIP_ERR_INVALID_ARG;
-  FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, rows, flags, 0);
+  FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, rows, flags, 0, h->kind);
   g.len = (uint32_t)len, g.stride = (uint32_t)stride, g.capacity_at = capacity_at, g.out_at = out_at;
   if (!plan_capacity(Field(h->ops->r32), capacity, g)) return MSM_HIP_ERR_NONCANONICAL;
   int rc = have_device(h->device);
@@ -184,7 +186,7 @@ inline int merkle_impl(const msm_frhash* h, void* stream, void* nodes, const voi
   if (!host && (misaligned(nodes) || misaligned(leaves))) return MSM_HIP_ERR_INVALID_ARG;  // (16-byte vector accesses)
   const size_t below = leaf_count(h->t, n_leaves), above = node_count(levels), arity = h->t - 1;
   if (!apart(nodes, above * 32, leaves, below * 32)) return MSM_HIP_ERR_INVALID_ARG;
-  FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, 1, flags, 0);
+  FrhashArgs g = plan_args(h->t, h->full_rounds, h->partial_rounds, 1, flags, 0, h->kind);
   g.len = g.stride = (uint32_t)arity, g.capacity_at = capacity_at, g.out_at = out_at;
   if (!plan_capacity(Field(h->ops->r32), capacity, g)) return MSM_HIP_ERR_NONCANONICAL;
   int rc = have_device(h->device);

@@ -18,7 +18,8 @@ using host_fr::Field;
 using host_fr::Fr;
 
 constexpr size_t MAX_ELEMENTS = (size_t)MSM_FRHASH_MAX_ELEMENTS;
-constexpr uint32_t KNOWN_FLAGS = MSM_FRHASH_MONT256;
+constexpr uint32_t KNOWN_FLAGS = MSM_FRHASH_MONT256;                            // of a call
+constexpr uint32_t CREATE_FLAGS = MSM_FRHASH_MONT256 | MSM_FRHASH_POSEIDON2;  // of msm_frhash_create
 
 inline Fr pow2(const Field& f, int k) {  // 2^k mod r
   Fr x = {{1, 0, 0, 0}};
@@ -34,16 +35,29 @@ inline bool all_below_r(const Field& f, const uint8_t* c, size_t count) {
 // c R mod r, R = 2^261, for a canonical c: the kernel's form of a constant
 inline void to_kernel(const Field& f, const uint8_t c[32], uint32_t w[8]) { host_fr::store_words(f.mul(f.to_mont(host_fr::load32(c)), pow2(f, 261)), w); }
 
+// the kind of handle the flags of msm_frhash_create ask for (FRHASH_KIND_*)
+inline uint32_t kind_of(uint32_t flags) { return (flags & MSM_FRHASH_POSEIDON2) ? FRHASH_KIND_POSEIDON2 : FRHASH_KIND_POSEIDON; }
+inline bool poseidon2_width(uint32_t t) { return t == 2 || t == 3 || t == 4 || t == 8 || t == 12; }  // the widths Poseidon2 defines
+// the shape of a handle; flags: those of msm_frhash_create
 inline bool shape_ok(uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, uint32_t alpha, uint32_t flags) {
   return t >= 2 && t <= MSM_FRHASH_MAX_WIDTH && full_rounds >= 2 && full_rounds <= MSM_FRHASH_MAX_FULL_ROUNDS && full_rounds % 2 == 0 &&
-         partial_rounds <= MSM_FRHASH_MAX_PARTIAL_ROUNDS && alpha == 5 && !(flags & ~KNOWN_FLAGS);
+         partial_rounds <= MSM_FRHASH_MAX_PARTIAL_ROUNDS && alpha == 5 && !(flags & ~CREATE_FLAGS) && (kind_of(flags) != FRHASH_KIND_POSEIDON2 || poseidon2_width(t));
 }
-inline size_t table_words(uint32_t t, uint32_t full_rounds, uint32_t partial_rounds) { return FRHASH_TAB_RC + (size_t)8 * ((full_rounds + partial_rounds) * t + t * t); }
+// how many scalars `round_constants` and `mds` hold: Poseidon t a round and the t x t matrix; Poseidon2 t an external round, one an internal
+// round, and the t of mu
+inline size_t constants_of(uint32_t kind, uint32_t t, uint32_t full_rounds, uint32_t partial_rounds) {
+  return kind == FRHASH_KIND_POSEIDON2 ? (size_t)full_rounds * t + partial_rounds : (size_t)(full_rounds + partial_rounds) * t;
+}
+inline size_t matrix_of(uint32_t kind, uint32_t t) { return kind == FRHASH_KIND_POSEIDON2 ? t : (size_t)t * t; }
+inline size_t table_words(uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, uint32_t kind = FRHASH_KIND_POSEIDON) {
+  return FRHASH_TAB_RC + (size_t)8 * (constants_of(kind, t, full_rounds, partial_rounds) + matrix_of(kind, t));
+}
 
-// the table: R^2 / F and F for both data forms, then the round constants and the matrix as c R (constants that passed all_below_r)
-inline void plan_table(const Field& f, uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, const uint8_t* rc, const uint8_t* mds, std::vector<uint32_t>& words) {
-  const size_t n_rc = (size_t)(full_rounds + partial_rounds) * t, n_m = (size_t)t * t;
-  words.assign(table_words(t, full_rounds, partial_rounds), 0);
+// the table: R^2 / F and F for both data forms, then the round constants and the matrix (Poseidon2: mu) as c R (constants that passed all_below_r)
+inline void plan_table(const Field& f, uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, const uint8_t* rc, const uint8_t* mds, std::vector<uint32_t>& words,
+                       uint32_t kind = FRHASH_KIND_POSEIDON) {
+  const size_t n_rc = constants_of(kind, t, full_rounds, partial_rounds), n_m = matrix_of(kind, t);
+  words.assign(table_words(t, full_rounds, partial_rounds, kind), 0);
   host_fr::store_words(pow2(f, 2 * 261), words.data() + FRHASH_TAB_IN);
   host_fr::store_words(pow2(f, 0), words.data() + FRHASH_TAB_OUT);
   host_fr::store_words(pow2(f, 2 * 261 - 256), words.data() + FRHASH_TAB_MONT + FRHASH_TAB_IN);
@@ -52,12 +66,13 @@ inline void plan_table(const Field& f, uint32_t t, uint32_t full_rounds, uint32_
   for (size_t i = 0; i < n_m; i++) to_kernel(f, mds + 32 * i, words.data() + FRHASH_TAB_RC + 8 * (n_rc + i));
 }
 
-inline FrhashArgs plan_args(uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, size_t n, uint32_t flags, uint32_t tile) {
+inline FrhashArgs plan_args(uint32_t t, uint32_t full_rounds, uint32_t partial_rounds, size_t n, uint32_t flags, uint32_t tile, uint32_t kind = FRHASH_KIND_POSEIDON) {
   FrhashArgs g;
   memset(&g, 0, sizeof g);
   g.t = t, g.full_rounds = full_rounds, g.partial_rounds = partial_rounds, g.n = (uint32_t)n;
   g.form = (flags & MSM_FRHASH_MONT256) ? FRHASH_TAB_MONT : 0;
   g.tile = tile ? tile : FRHASH_THREADS;
+  g.kind = kind;
   return g;
 }
 inline unsigned blocks_of(const FrhashArgs& g) { return (unsigned)((g.n + g.tile - 1) / g.tile); }

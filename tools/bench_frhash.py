@@ -14,12 +14,20 @@ them the code under test:
 
 A tree is reported against (n - 1) / (A - 1) permutations at the batch rate; a sponge against its permutations at the batch rate.
 
+Poseidon2 (MsmContext.poseidon2; --poseidon2-widths, empty: none) is timed against the EXISTING Poseidon kernel of the same t, R_F = 8 and the
+same R_P, on the same states, the two ALTERNATED in one process; beside the measured ratio stand the ratio of the two product counts (what to
+expect where the multiplier bounds both) and each kernel's fraction of the ceiling.  Its products, a pair under one reduction counted as 2:
+t + R_F (t S + L) + L + R_P (S + 2 t), S = 3 or 4 products an S-box, L = 0, t or t + 4 products a layer (csrc/frhash_kernels.h).  Its constants
+are drawn from a seeded generator: the time does not depend on them.
+
 Protocol: device data, every shape warmed up, then `--calls` calls timed back to back (each call returns when its stream has completed), the
 call and its chain ALTERNATED `--rounds` times; min .. max over the rounds beside every mean.
 
-usage: tools/bench_frhash.py [--log-n 20] [--widths 3,5,9,12] [--calls 10] [--chain-calls 1] [--rounds 3] [--ubench build/ubench_fqmul] [--no-chain]"""
+usage: tools/bench_frhash.py [--log-n 20] [--widths 3,5,9,12] [--poseidon2-widths 3,4,8,12] [--calls 10] [--chain-calls 1] [--rounds 3]
+                             [--ubench build/ubench_fqmul] [--no-chain]"""
 import argparse
 import os
+import random
 import re
 import statistics
 import subprocess
@@ -50,6 +58,52 @@ def spread(v):
 
 def products(t, rf, rp):
     return rf * (3 * t + t * t) + rp * (3 + t * t)
+
+
+def poseidon2_rules(r, t):
+    """(frh2_tidy_sums(t), frh2_bound(t), frh2_tidy_sbox(t)) of csrc/frhash_kernels.h over the field of order r, restated;
+    tests/test_frhash2_host.py compares them with the kernel's own for every field and width"""
+    headroom = (1 << 261) // r
+    tidy_sums = t >= 8 and ((t // 2 + 3) ** 2 > headroom or t * (t // 2 + 2) + 2 > headroom)
+    bound = 2 * t + 2 if t < 4 else 2 if t == 4 else 4 if tidy_sums else t // 2 + 2
+    return tidy_sums, bound, (bound + 1) ** 2 > headroom
+
+
+def products2(r, t, rf, rp):
+    """the products of one Poseidon2 permutation as csrc/frhash_kernels.h issues them over the field of order r, a pair of fq_mul2 counted as 2"""
+    tidy_sums, _, tidy_sbox = poseidon2_rules(r, t)
+    sbox = 4 if tidy_sbox else 3
+    layer = 0 if t < 4 else t + 4 if tidy_sums else t
+    return t + rf * (t * sbox + layer) + layer + rp * (sbox + 2 * t)
+
+
+def bench_poseidon2(c, curve, t, n, a, ns_per_product):
+    """Poseidon2 against the existing Poseidon kernel: the same t, R_F, R_P and states, alternated"""
+    rf, rp = 8, api.POSEIDON_PARTIAL_ROUNDS[t]
+    r = api.SCALAR_FIELDS[curve]
+    rnd = random.Random(74 + t)
+    label = "%-9s poseidon2 t = %-2d R_P = %d n = 2^%d" % (curve, t, rp, n.bit_length() - 1)
+    states = c.sample_scalars(n * t, 71).view(n, t, 32)
+    out_old, out_new = torch.empty_like(states), torch.empty_like(states)
+    old = c.poseidon(t, rf, rp)
+    new = c.poseidon2(t, rf, rp, [rnd.randrange(r) for _ in range(rf * t + rp)], [rnd.randrange(r) for _ in range(t)])
+    run_old = lambda: c.scalars_permute(old, states, out=out_old)  # noqa: E731
+    run_new = lambda: c.scalars_permute(new, states, out=out_new)  # noqa: E731
+    run_old(), run_new()
+    t_old, t_new = [], []
+    for _ in range(a.rounds):
+        t_new.append(timed(run_new, a.calls))
+        t_old.append(timed(run_old, a.calls))
+    p_old, p_new = products(t, rf, rp), products2(r, t, rf, rp)
+    faster = max(t_new) < min(t_old)
+    line = "%s %s = %.2f ns per permutation  against poseidon %s = %.4f x  %s  products %d against %d = %.4f x" % (
+        label, spread(t_new), statistics.mean(t_new) / n * 1e9, spread(t_old), statistics.mean(t_new) / statistics.mean(t_old),
+        "FASTER beyond the spread of both" if faster else "NOT FASTER", p_new, p_old, p_new / p_old)
+    if ns_per_product:
+        line += "  fraction of the ceiling %.2f (poseidon %.2f)" % (p_new * n * ns_per_product * 1e-9 / statistics.mean(t_new), p_old * n * ns_per_product * 1e-9 / statistics.mean(t_old))
+    print(line, flush=True)
+    old.close()
+    new.close()
 
 
 def ubench(path):
@@ -116,6 +170,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--widths", default="3,5,9,12")
+    ap.add_argument("--poseidon2-widths", default="3,4,8,12")
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--chain-calls", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=3)
@@ -157,9 +212,15 @@ def main():
         print("bn254     merkle  arity %d  %d leaves, %d levels: %s  against %d permutations at the batch rate %.3f ms = %.2f x" % (
             t - 1, leaves, levels, spread(tm), count, count * rate[t] * 1e3, statistics.mean(tm) / (count * rate[t])), flush=True)
         h.close()
+    widths2 = [int(s) for s in a.poseidon2_widths.split(",") if s]
+    for t in widths2:
+        bench_poseidon2(c, "bn254", t, n, a, ns_per_product)
+        torch.cuda.empty_cache()
     c.close()
     c = m.MsmContext(0, curve="bls12_381")
     bench_permute(c, "bls12_381", 3, n, a, ns_per_product)
+    for t in widths2[-1:]:  # the widest: the one width at which this field tidies the position sums
+        bench_poseidon2(c, "bls12_381", t, n, a, ns_per_product)
     c.close()
     api.frhash_release()
     api.frgate_release()
