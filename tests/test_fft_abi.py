@@ -114,6 +114,8 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
         with pytest.raises(ValueError):
             _bare_context(n_bases).lagrange_bases()
     ctx = _bare_context(8)
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        ctx.bases_fft(w, 3)
     with pytest.raises(ValueError):  # omega as bytes: 32 of them
         ctx.bases_fft(bytes(31), 3)
     with pytest.raises(OverflowError):  # ... as an integer: below 2^256

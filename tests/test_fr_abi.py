@@ -90,9 +90,14 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
     def no_call():
         raise AssertionError("the library was called")
 
+    from msm_webgpu_amd import scalars  # (where the wrappers look the loaders up)
+
     monkeypatch.setattr(api, "lib", no_call)
-    monkeypatch.setattr(api, "fr_lib", no_call)
+    monkeypatch.setattr(scalars, "lib", no_call)
+    monkeypatch.setattr(scalars, "fr_lib", no_call)
     r = api.SCALAR_FIELDS["bn254"]
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        _bare_context().scalars_fft(bytes(32 * 8))
     with pytest.raises(ValueError):  # Grumpkin: r - 1 = 2 * odd
         _bare_context("grumpkin").scalars_fft(bytes(64))
     ctx = _bare_context()

@@ -213,7 +213,9 @@ def test_the_python_mirror(built, monkeypatch):
     def no_call():
         raise AssertionError("the library was called")
 
-    monkeypatch.setattr(api, "frmat_lib", no_call)
+    from msm_webgpu_amd import scalars  # (where the wrappers look the loaders up)
+
+    monkeypatch.setattr(scalars, "frmat_lib", no_call)  # (the good call at the end shows that the trap sits in the path)
     for bad in (lambda: ctx.scalars_matrix(0, 5, [0], [], []),
                 lambda: ctx.scalars_matrix(3, (1 << 26) + 1, ptr, idx, val),
                 lambda: ctx.scalars_matrix(3, 5, ptr[:-1], idx, val),  # row_ptr: its length, its ends, a step down

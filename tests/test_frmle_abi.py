@@ -168,11 +168,16 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
     def no_call():
         raise AssertionError("the library was called")
 
+    from msm_webgpu_amd import scalars  # (where the wrappers look the loaders up)
+
+    monkeypatch.setattr(api, "lib", no_call)
     for name in ("lib", "fr_lib", "frvec_lib", "frpoly_lib", "frmle_lib"):
-        monkeypatch.setattr(api, name, no_call)
+        monkeypatch.setattr(scalars, name, no_call)
     r = api.SCALAR_FIELDS["bn254"]
     v = bytes(32 * 8)
     T = [(1, (0, 1))]
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        _bare_context().scalars_mle_fold(v, 1)
 
     def every_method(ctx):
         return [lambda: ctx.scalars_mle_fold(v, 1), lambda: ctx.scalars_mle_eval(v, [1, 2, 3]), lambda: ctx.scalars_eq([1, 2]), lambda: ctx.scalars_sumcheck_round(v, T, batch=2)]

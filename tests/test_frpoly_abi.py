@@ -139,10 +139,15 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
     def no_call():
         raise AssertionError("the library was called")
 
+    from msm_webgpu_amd import scalars  # (where the wrappers look the loaders up)
+
+    monkeypatch.setattr(api, "lib", no_call)
     for name in ("lib", "fr_lib", "frvec_lib", "frpoly_lib"):
-        monkeypatch.setattr(api, name, no_call)
+        monkeypatch.setattr(scalars, name, no_call)
     r = api.SCALAR_FIELDS["bn254"]
     v = bytes(32 * 4)
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        _bare_context().scalars_eval(v, 1)
 
     def every_method(ctx):
         return [lambda: ctx.scalars_eval(v, 1), lambda: ctx.scalars_divide(v, 1), lambda: ctx.scalars_dot(v, v), lambda: ctx.scalars_combine(v, [1, 2]),

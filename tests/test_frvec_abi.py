@@ -160,11 +160,16 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
     def no_call():
         raise AssertionError("the library was called")
 
+    from msm_webgpu_amd import scalars  # (where the wrappers look the loaders up)
+
     monkeypatch.setattr(api, "lib", no_call)
-    monkeypatch.setattr(api, "fr_lib", no_call)
-    monkeypatch.setattr(api, "frvec_lib", no_call)
+    monkeypatch.setattr(scalars, "lib", no_call)
+    monkeypatch.setattr(scalars, "fr_lib", no_call)
+    monkeypatch.setattr(scalars, "frvec_lib", no_call)
     r = api.SCALAR_FIELDS["bn254"]
     v = bytes(32 * 4)
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        _bare_context().scalars_add(v, v)
 
     def every_method(ctx):
         return [lambda: ctx.scalars_add(v, v), lambda: ctx.scalars_sub(v, 1), lambda: ctx.scalars_mul(v, v), lambda: ctx.scalars_mul_add(v, v, 1),

@@ -4,7 +4,7 @@ scalars_multiplicities gives; a column with one foreign value raises with its in
 as 4-byte scalars.
 
 logup runs on BN254, BLS12-381 and Grumpkin.  On Grumpkin, whose scalar field the vector library has no unit for, MsmContext.logup takes the
-same columns from scalars_gate and scalars_mle_eval (api.py: _logup_without_frvec); the test asks the same bytes of it."""
+same columns from scalars_gate and scalars_mle_eval (scalars.py: _logup_without_frvec); the test asks the same bytes of it."""
 import pytest
 import torch
 

@@ -80,6 +80,8 @@ def test_bad_arguments_raise_before_any_library_call(built, monkeypatch):
 
     monkeypatch.setattr(api, "lib", no_call)
     ctx = _bare_context(8)
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        ctx.mul_each(bytes(32))
     for call in (lambda s, **kw: ctx.mul_each(s, **kw), lambda s, **kw: ctx.mul_base(0, s, **kw)):
         with pytest.raises(ValueError):  # not a whole number of 32-byte scalars
             call(bytes(33))

@@ -74,6 +74,8 @@ def test_host_index_check_raises_before_any_library_call(built, monkeypatch, bad
 
     ctx = _bare_context(1000)
     monkeypatch.setattr(api, "lib", no_call)
+    with pytest.raises(AssertionError, match="the library was called"):  # (the trap sits in the path: a well-formed call reaches it)
+        ctx.msm_sparse(np.array([0, 999], dtype=np.int64), bytes(64))
     with pytest.raises(ValueError):
         ctx.msm_sparse(np.array(bad, dtype=np.int64), bytes(32 * len(bad)))
     with pytest.raises(ValueError):  # (int32 too)

@@ -1,5 +1,5 @@
 """Randomised differential test of the eight scalar-field libraries as CHAINED programs on shared state (tests/fr_program.py): random steps over
-one or two fields in one arena per field -- every entry point of the scalars_* section of api.py, in place or into another range, at starts of 0 and
+one or two fields in one arena per field -- every entry point of the scalars_* methods of scalars.py, in place or into another range, at starts of 0 and
 16 mod 32, after a larger call, after another field's call, after a refused call, under both scalar forms, with several test hooks set at once,
 with matrices, lookup tables and Poseidon handles kept alive across all of it (a handle's constants go to the device inside its first call, on
 whichever stream and under whichever form that call has; a Poseidon call is a device-form one on ranges of the arena or a host-form one on
