@@ -1,4 +1,5 @@
-"""Build libmsm_hip.so and the scalar-field libraries (FR_LIBRARIES: libmsm_fr.so ... libmsm_frhash.so) in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+"""Build libmsm_hip.so, the scalar-field libraries (FR_LIBRARIES: libmsm_fr.so ... libmsm_frhash.so) and the field-neutral ones (AUX_LIBRARIES:
+libmsm_frcol.so) in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import collections
 import os
 import subprocess
@@ -36,16 +37,22 @@ FR_LIBRARIES = collections.OrderedDict((lib.name, lib) for lib in [
     _fr_library("frlook", field_math=False),  # lookup arguments: it matches keys and computes nothing, so of the field's files the constants alone
     _fr_library("frhash"),  # Poseidon: batch permutations, sponges and Merkle trees
 ])
+# Libraries that move scalars as stored and so are ONE translation unit for all fields, without a field's constants or arithmetic: rows of the same
+# shape in a table of their own (DESIGN.md sections 4.25, 4.26), built, stamped and gated exactly like the rows of FR_LIBRARIES.
+AUX_LIBRARIES = collections.OrderedDict((lib.name, lib) for lib in [
+    FrLibrary("frcol", os.path.join(HERE, "libmsm_frcol.so"), ["frcol.hip"], ["frcol.hip", "frcol_kernels.h", "frcol_host.h", "frcol_plan.h", "fr_host_common.h"],
+              [os.path.join(HERE, "..", "include", "msm_frcol.h"), HEADER]),  # lookup columns from counts: run expansion, halo2's permuted pair, gather
+])
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
 def library_of(units):
-    """The scalar-field library whose units contain `units`; None for libmsm_hip.so's units (and for none at all)."""
-    return next((lib for lib in FR_LIBRARIES.values() if units and set(units) <= set(lib.units)), None)
+    """The row of FR_LIBRARIES or AUX_LIBRARIES whose units contain `units`; None for libmsm_hip.so's units (and for none at all)."""
+    return next((lib for lib in list(FR_LIBRARIES.values()) + list(AUX_LIBRARIES.values()) if units and set(units) <= set(lib.units)), None)
 
 
 def device_asm_files(lib=None):
-    """The device assembly of every translation unit of a library (lib: a row of FR_LIBRARIES; None: libmsm_hip.so), as build() leaves it behind."""
+    """The device assembly of every translation unit of a library (lib: a row of FR_LIBRARIES or AUX_LIBRARIES; None: libmsm_hip.so), as build() leaves it behind."""
     return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in (lib.units if lib else TRANSLATION_UNITS)]
 
 
@@ -139,10 +146,10 @@ def compile_flags():
 
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
-    from the scalar-field units, every library of FR_LIBRARIES (msm-webgpu_amd/libmsm_fr.so ... msm-webgpu_amd/libmsm_frhash.so).  Each library
-    is rebuilt only when its own sources or the flags changed."""
+    from the scalar-field units, every library of FR_LIBRARIES (msm-webgpu_amd/libmsm_fr.so ... msm-webgpu_amd/libmsm_frhash.so) and of
+    AUX_LIBRARIES (msm-webgpu_amd/libmsm_frcol.so).  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip = force or needs_build()
-    todo = [lib for lib in FR_LIBRARIES.values() if (force and not os.environ.get("MSM_HIP_SO")) or needs_build(lib)]
+    todo = [lib for lib in list(FR_LIBRARIES.values()) + list(AUX_LIBRARIES.values()) if (force and not os.environ.get("MSM_HIP_SO")) or needs_build(lib)]
     if not do_hip and not todo:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
