@@ -109,6 +109,20 @@ def _out(like, out, n, name="out"):
     return out
 
 
+def _apart(outputs, inputs):
+    """every output (name, tensor) apart from every input and from the other outputs, as the library demands: ValueError naming the two
+    operands otherwise -- before the C call, whose MSM_HIP_ERR_INVALID_ARG does not say which check failed"""
+    span = lambda v: (v.data_ptr(), v.data_ptr() + v.numel() * v.element_size())
+    for k, (name, o) in enumerate(outputs):
+        for other, v in outputs[k + 1:] + list(inputs):
+            (p, p_end), (q, q_end) = span(o), span(v)
+            if p < q_end and q < p_end:
+                raise ValueError("%s overlaps %s: every output lies apart from every input and from the other outputs" % (name, other))
+
+
+_NO_TOTAL = (1 << 64) - 1  # what *total starts at: 2^24 words of 32 bits, each with a bias of 1, add up to less than 2^57
+
+
 def _stream_behind(ctx, *tensors):
     """the context's stream, made to wait for torch's work on the operands"""
     ctx._order_after_torch(*tensors)
@@ -120,7 +134,7 @@ def expand(ctx, t, counts, n_out, bias=0, out=None):
     """out = t[0] w[0] times, then t[1] w[1] times, ... with w[j] = counts[j] + bias (msm_frcol_expand_device): n_out scalars in a new tensor
     or `out`.  t: the table, n_t <= 2^24 scalars; counts: n_t 32-bit words on the device (scalars_multiplicities(counts=True)); bias: 0 -- over a
     column's counts halo2's A' -- or 1 -- with n_out = n + n_t plookup's s.  The w[j] must add up to n_out (<= 2^26): ValueError otherwise,
-    naming the sum, and out is untouched."""
+    naming the sum, and out is untouched.  out lies apart from t and counts: ValueError naming the two otherwise, and nothing is called."""
     _scalar_context(ctx, "expand")
     tt, n_t = _scalars(ctx, t, "t")
     cnt, m = _words(ctx, counts, "counts")
@@ -130,9 +144,10 @@ def expand(ctx, t, counts, n_out, bias=0, out=None):
     if bias not in (0, 1) or not 1 <= n_out <= MAX_ELEMENTS:
         raise ValueError("bias is 0 or 1 and n_out lies in [1, 2^26]")
     out = _out(tt, out, n_out)
-    total = C.c_uint64()
+    _apart([("out", out)], [("t", tt), ("counts", cnt)])
+    total = C.c_uint64(_NO_TOTAL)
     rc = frcol_lib().msm_frcol_expand_device(ctx.device, _stream_behind(ctx, tt, cnt), out.data_ptr(), tt.data_ptr(), cnt.data_ptr(), n_t, bias, n_out, C.byref(total))
-    if rc == ERR_INVALID_ARG and total.value != n_out:
+    if rc == ERR_INVALID_ARG and total.value not in (_NO_TOTAL, n_out):  # (the library wrote the sum: it got as far as forming it)
         raise ValueError("the counts%s add up to %d, not to the %d outputs" % (" + 1" if bias else "", total.value, n_out))
     _check(rc, "msm_frcol_expand_device")
     return out
@@ -141,7 +156,8 @@ def expand(ctx, t, counts, n_out, bias=0, out=None):
 def permuted_pair(ctx, t, counts, out=None):
     """halo2's permuted columns (A', S') of a lookup of n values into the n table values t, from the counts (msm_frcol_pair_device): A' groups the
     looked-up values by table entry; S' holds t[j] where the run of t[j] begins and the table values never looked up elsewhere, ascending by
-    index.  The counts must add up to n = len(t): ValueError otherwise.  out: None or a pair of tensors.  -> (a_perm, s_perm)"""
+    index.  The counts must add up to n = len(t): ValueError otherwise.  out: None or a pair of tensors, apart from t, from counts and from
+    one another (ValueError naming the two that share bytes).  -> (a_perm, s_perm)"""
     _scalar_context(ctx, "permuted_pair")
     tt, n = _scalars(ctx, t, "t")
     cnt, m = _words(ctx, counts, "counts")
@@ -149,10 +165,11 @@ def permuted_pair(ctx, t, counts, out=None):
         raise ValueError("the table holds %d scalars (at most 2^24), counts %d words" % (n, m))
     a_out, s_out = (None, None) if out is None else out
     a_out, s_out = _out(tt, a_out, n, "out[0]"), _out(tt, s_out, n, "out[1]")
-    total, used = C.c_uint64(), C.c_uint64()
+    _apart([("out[0]", a_out), ("out[1]", s_out)], [("t", tt), ("counts", cnt)])
+    total, used = C.c_uint64(_NO_TOTAL), C.c_uint64()
     rc = frcol_lib().msm_frcol_pair_device(ctx.device, _stream_behind(ctx, tt, cnt), a_out.data_ptr(), s_out.data_ptr(), tt.data_ptr(), cnt.data_ptr(), n, C.byref(total),
                                            C.byref(used))
-    if rc == ERR_INVALID_ARG and total.value != n:
+    if rc == ERR_INVALID_ARG and total.value not in (_NO_TOTAL, n):
         raise ValueError("the counts add up to %d, not to the %d rows of the table" % (total.value, n))
     _check(rc, "msm_frcol_pair_device")
     return a_out, s_out
@@ -161,15 +178,17 @@ def permuted_pair(ctx, t, counts, out=None):
 def gather(ctx, a, idx, out=None):
     """out[i] = a[idx[i]] (msm_frcol_gather_device): what a vector lookup does after the count -- it fetches the other columns of the matched
     rows.  idx: a CUDA int32 tensor with -1 for "missing" (scalars_multiplicities(indices=True)) or uint32 with 0xFFFFFFFF: those elements are
-    32 zero bytes.  Any other index outside a raises ValueError (that element is then zero)."""
+    32 zero bytes.  Any other index outside a raises ValueError (that element is then zero).  out lies apart from a and idx: ValueError
+    naming the two otherwise, with nothing written."""
     _scalar_context(ctx, "gather")
     ta, n_a = _scalars(ctx, a, "a")
     ti, n = _words(ctx, idx.reshape(-1) if isinstance(idx, torch.Tensor) else idx, "idx")
     if n_a > MAX_ELEMENTS or not 1 <= n <= MAX_ELEMENTS:
         raise ValueError("a vector holds 1 .. 2^26 scalars")
     out = _out(ta, out, n)
+    _apart([("out", out)], [("a", ta), ("idx", ti)])
     rc = frcol_lib().msm_frcol_gather_device(ctx.device, _stream_behind(ctx, ta, ti), out.data_ptr(), ta.data_ptr(), n_a, ti.data_ptr(), n)
-    if rc == ERR_INVALID_ARG:
+    if rc == ERR_INVALID_ARG:  # (the operands lay apart and the ranges were checked above: what is left is an index)
         raise ValueError("an index is neither below the %d scalars of a nor -1" % n_a)
     _check(rc, "msm_frcol_gather_device")
     return out

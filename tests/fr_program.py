@@ -1,4 +1,4 @@
-"""Programs over the eight scalar-field libraries (libmsm_fr, frvec, frpoly, frmle, frmat, frgate, frlook, frhash): a generator, and a model interpreter
+"""Programs over the nine scalar-field libraries (libmsm_fr, frvec, frpoly, frmle, frmat, frgate, frlook, frhash, frcol): a generator, and a model interpreter
 that predicts every byte a program leaves on the device.  Needs no GPU, no HIP and no torch: tools/fuzz_fr.py runs the programs on the device and
 compares, tests/test_fr_program.py checks the tester itself.
 
@@ -15,12 +15,23 @@ libmsm_frhash's steps: "poseidon" makes a handle in a slot from a seed (its cons
 table goes there inside its first call, on whichever stream and under whichever form that call has; "permute", "sponge" and "tree" call it on
 ranges of the arena or, with host set, on the bytes of those ranges, in which case the result is the step's host value and no range is
 written.  An output that cuts the input is refused by the Python layer (REFUSED), not by the library.  A "plant" step with quiet set puts a value
-that is not below r where the next step does NOT read (the padding between a sponge's rows): that step must not be refused, and heals it."""
+that is not below r where the next step does NOT read (the padding between a sponge's rows): that step must not be refused, and heals it.
+"poseidon2" makes a Poseidon2 handle (frhash2_model.Poseidon2; its constants: poseidon2_constants) in the same three slots; the three calls take
+it unchanged.
+
+libmsm_frcol's steps: "expand", "pair" and "gather" (msm_webgpu_amd.columns) move scalars AS STORED, whatever the field's form, by 32-bit WORD
+VECTORS, of which every field keeps up to three in slots -- lists in the model, int32 or uint32 tensors on the device.  A slot is filled by a
+"mult" step that names it (cslot: its counts, islot: its indices; the backend keeps the very tensor the call returned) or by a "words" step,
+which uploads a vector the generator drew and calls no library.  Counts that do not add up to the outputs and an index that is neither inside
+`a` nor MISSING are refused by the Python layer (REFUSED) after the library looked: the output range is then among the step's writes -- unchanged
+for a wrong sum, with that element zero for a bad index.  An output that cuts an input or the other output is refused before the C call like a
+hash step's cut (column_cut), and like it is not flagged "overlap".  NO VALUE >= r IS PLANTED before a column step: the library does not
+compare with r, so the value would be copied into the arena and the NEXT step refused for the wrong reason."""
 import functools
 import hashlib
 import random
 
-from tests import frgate_model, frhash_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
+from tests import frcol_model, frgate_model, frhash2_model, frhash_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
 
 FIELD_R = {
     "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
@@ -40,20 +51,34 @@ LENGTHS = (1, 2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2051, 4097)
 # tree over 2048 leaves, rounds (2, 0): 36846 units), and at most 0.09 s above it; at t = 2 the largest step the lengths below allow is 1025 lanes
 # of 8 rounds, 32800 units: 0.12 s.
 HASH_WORK = 37000
+# Poseidon2 (frhash2_model.Poseidon2.permute) has no matrix product: an external round costs t S-boxes and a few additions, an internal one an S-box
+# and t products.  Its unit of work is permutations x (3 R_F t + R_P (t + 3)).  (Per permutations x (R_F t + R_P) x t the cost is no constant: 0.23 us
+# at t = 12, (4, 2) and 1.64 at t = 2, (8, 56).)  Measured on the same kind of CPU, BN254 (BLS12-381 within 5 %), microseconds per unit: t = 2,
+# rounds (2, 0): 0.86; t = 2, (2, 3): 0.74; t = 3, (2, 0): 0.79; t = 3, (2, 1): 0.75; t = 3, (4, 2): 0.75; t = 4, (4, 2): 0.73; t = 4, (2, 3): 0.74;
+# t = 8, (2, 1): 0.89; t = 8, (4, 2): 0.86; t = 8, (8, 0): 0.88; t = 12, (2, 1): 0.85; t = 12, (2, 3): 0.79; t = 12, (4, 2): 0.79; t = 2, (8, 56): 0.72;
+# t = 3, (8, 57): 0.70; t = 4, (8, 56): 0.68; t = 8, (8, 60): 0.68; t = 12, (8, 60): 0.67.  112000 units are 0.1 s at the dearest of these and 0.075 s
+# at the cheapest.
+HASH2_WORK = 112000
 LARGE, SMALL = 1023, 65  # a "large" step has an operand of at least LARGE scalars to a row, a "small" one at most SMALL
 ERR_INVALID_ARG, ERR_NONCANONICAL, REFUSED = -2, -4, "refused"  # MSM_HIP_ERR_*; REFUSED: the Python layer raises ValueError before the C call
 HOOKS = {"fr_test_pass_bits": (0, 1, 2, 3, 5), "frvec_test_tile": (0, 2, 3, 8, 64), "frpoly_test_tile": (0, 2, 3, 8, 64), "frmle_test_tile": (0, 2, 8, 64),
-         "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8), "frhash_test_tile": (0, 1, 3, 4, 64)}
+         "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8), "frhash_test_tile": (0, 1, 3, 4, 64), "frcol_test_tile": (0, 2, 3, 8, 64)}
 LIBRARY = {"map": "frvec", "inverse": "frvec", "scan": "frvec", "fft": "fr", "eval": "frpoly", "divide": "frpoly", "dot": "frpoly", "combine": "frpoly",
            "powers": "frpoly", "mle_fold": "frmle", "mle_eval": "frmle", "eq": "frmle", "round": "frmle", "matrix": "frmat", "matvec": "frmat", "gate": "frgate",
-           "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook", "poseidon": "frhash", "permute": "frhash", "sponge": "frhash", "tree": "frhash"}
-LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook", "frhash")
-GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult", "poseidon", "permute", "sponge", "tree")  # the libraries that serve its scalar field
-HASH_CALLS = ("permute", "sponge", "tree")  # the steps that call libmsm_frhash ("poseidon" touches no device)
+           "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook", "poseidon": "frhash", "poseidon2": "frhash", "permute": "frhash", "sponge": "frhash", "tree": "frhash", "expand": "frcol", "pair": "frcol", "gather": "frcol"}
+LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook", "frhash", "frcol")
+GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult", "poseidon", "poseidon2", "permute", "sponge", "tree", "expand", "pair",
+                  "gather")  # the libraries that serve its scalar field
+HASH_CALLS = ("permute", "sponge", "tree")  # the steps that call libmsm_frhash ("poseidon" and "poseidon2" touch no device)
+HASH_MAKERS = ("poseidon", "poseidon2")  # the steps that make a handle: its kind
+COLUMN_CALLS = ("expand", "pair", "gather")  # the steps that call libmsm_frcol
 HASH_WIDTHS = (2, 3, 4, 5, 7, 8, 9, 10, 12)
+HASH2_WIDTHS = frhash2_model.WIDTHS
+MISSING = frcol_model.MISSING
+WORD_SLOTS = 3
 # the widest state whose S-box input the kernel leaves untidied, and the first it tidies: (t + 4)^2 against the field's FQ_HEADROOM (csrc/frhash_kernels.h)
 HASH_BOUNDARY = {"bls12_381": (4, 5), "pallas": (7, 8), "vesta": (7, 8), "bn254": (9, 10), "grumpkin": (9, 10)}
-KINDS = tuple(LIBRARY) + ("format", "hook", "close", "stream", "plant", "overlap")
+KINDS = tuple(LIBRARY) + ("words", "format", "hook", "close", "stream", "plant", "overlap")
 
 
 def label(step):
@@ -100,7 +125,8 @@ class Model:
         self.mont = [False] * len(self.fields)
         self.mats = [{} for _ in self.fields]
         self.tabs = [{} for _ in self.fields]
-        self.hashes = [{} for _ in self.fields]  # slot -> frhash_model.Poseidon
+        self.hashes = [{} for _ in self.fields]  # slot -> frhash_model.Poseidon or frhash2_model.Poseidon2
+        self.words = [{} for _ in self.fields]  # slot -> a list of 32-bit words
         self.planted = [{} for _ in self.fields]  # off16 -> the 32 bytes a planted value replaced
         self.quiet = [{} for _ in self.fields]  # the same for a value planted where the next step does NOT read: it must not be refused
         self.hooks = {h: 0 for h in HOOKS}
@@ -363,7 +389,8 @@ class Model:
             return [], len(set(self.tabs[f][slot][0]))
         return self._run(f, [(t[0], n)], [], compute)  # (ERR_NONCANONICAL: no handle is made)
 
-    def op_mult(self, f, slot, v, batch, n, out, indices, counts):
+    def op_mult(self, f, slot, v, batch, n, out, indices, counts, cslot=None, islot=None):
+        assert (cslot is None or counts) and (islot is None or indices) and (cslot is None or cslot != islot)
         keys, form = self.tabs[f][slot]
         stride = v[1] // batch
         assert out[1] == len(keys) and stride * batch == v[1] and 1 <= n <= stride and not _cuts(out, v)
@@ -373,6 +400,9 @@ class Model:
 
         def compute():
             cnt, idx, missing, first, _ = frlook_model.lookup(keys, [stored[k * stride:(k + 1) * stride] for k in range(batch)], n)
+            for wslot, words in ((cslot, cnt), (islot, idx)):  # the word vectors the call returned stay in the slots it names
+                if wslot is not None:
+                    self.words[f][wslot] = list(words)
             host = ((idx,) if indices else ()) + ((cnt,) if counts else ()) + ((missing, first if missing else None),)
             return [(out[0], self.enc(f, cnt))], host
         return self._run(f, [(v[0] + 2 * k * stride, n) for k in range(batch)], [out], compute)
@@ -383,6 +413,12 @@ class Model:
         rc, mds = poseidon_constants(seed, t, full_rounds, partial_rounds, self.r[f])
         self.hashes[f][slot] = frhash_model.Poseidon(self.r[f], t, full_rounds, partial_rounds, rc, mds, capacity, capacity_at, out_at)
         return self._fail(None)  # (no device is touched: the table goes there with the handle's first call)
+
+    def op_poseidon2(self, f, slot, t, full_rounds, partial_rounds, seed, capacity, capacity_at, out_at):
+        assert slot not in self.hashes[f] and len(self.hashes[f]) < 3 and t in HASH2_WIDTHS
+        rc, mu = poseidon2_constants(seed, t, full_rounds, partial_rounds, self.r[f])
+        self.hashes[f][slot] = frhash2_model.Poseidon2(self.r[f], t, full_rounds, partial_rounds, rc, mu, capacity, capacity_at, out_at)
+        return self._fail(None)
 
     def _hashed(self, f, reads, out, host, values):
         """a call of libmsm_frhash: values() -> the plain results, which go to `out`, or come back as host bytes in the data's form where `host` is set"""
@@ -427,6 +463,67 @@ class Model:
             assert host or len(nodes) == out[1]
             return nodes
         return self._hashed(f, [leaves], out, host, values)
+
+
+    # ---- libmsm_frcol: scalars AS STORED, whatever the field's form ---------------------------------------------------------------------------------
+    def op_words(self, f, slot, values):
+        assert 0 <= slot < WORD_SLOTS and values and all(0 <= w < 1 << 32 for w in values)
+        self.words[f][slot] = list(values)
+        return self._fail(None)
+
+    def _moved(self, f, puts, refused=False):
+        """a column call that copies: puts [(range, stored values)] -- nothing is compared with r; refused: the Python layer raises all the same"""
+        out = self._run(f, [], [rng for rng, _ in puts], lambda: ([(rng[0], frvec_model.to_bytes(vals)) for rng, vals in puts], None))
+        return dict(out, error=REFUSED) if refused else out
+
+    def op_expand(self, f, t, counts, bias, out):
+        cnt = self.words[f][counts]
+        assert len(cnt) == t[1] and bias in (0, 1) and 1 <= out[1] <= BANK
+        if column_cut(("expand", f, {"t": t, "out": out})):
+            return self._fail(REFUSED)
+        if frcol_model.total(cnt, bias) != out[1]:  # (the sum in 64 bits: one that is n_out only in 32 bits is refused too)
+            return self._moved(f, [(out, self.stored(f, out))], True)
+        return self._moved(f, [(out, frcol_model.expand(self.stored(f, t), cnt, bias))])
+
+    def op_pair(self, f, t, counts, out, s_out):
+        cnt = self.words[f][counts]
+        assert len(cnt) == t[1] == out[1] == s_out[1]
+        if column_cut(("pair", f, {"t": t, "out": out, "s_out": s_out})):
+            return self._fail(REFUSED)
+        if frcol_model.total(cnt) != t[1]:
+            return self._moved(f, [(out, self.stored(f, out)), (s_out, self.stored(f, s_out))], True)
+        a_perm, s_perm, _ = frcol_model.pair(self.stored(f, t), cnt)
+        return self._moved(f, [(out, a_perm), (s_out, s_perm)])
+
+    def op_gather(self, f, a, idx, out):
+        words = self.words[f][idx]
+        assert len(words) == out[1]
+        if column_cut(("gather", f, {"a": a, "out": out})):
+            return self._fail(REFUSED)
+        vals, ok = frcol_model.gather(self.stored(f, a), words)
+        return self._moved(f, [(out, vals)], not ok)  # (a bad index: that element zero, the others as usual, and ValueError)
+
+
+def column_cut(step):
+    """is this a call of libmsm_frcol whose output shares bytes with an input or with the other output -- a same start included: the Python
+    layer refuses it (REFUSED) before the C call, with nothing written"""
+    kind, _, a = step
+    if kind == "expand":
+        return _cuts(a["out"], a["t"])
+    if kind == "pair":
+        return _cuts(a["out"], a["t"]) or _cuts(a["s_out"], a["t"]) or _cuts(a["out"], a["s_out"])
+    return kind == "gather" and _cuts(a["out"], a["a"])
+
+
+def poseidon2_constants(seed, t, full_rounds, partial_rounds, r):
+    """-> (round constants, mu) of a Poseidon2 handle from its integer seed; 0, 1 and r - 1 are among the round constants (there are at least
+    four) and among mu (at t = 2, which has room for two, 1 and r - 1)"""
+    n = full_rounds * t + partial_rounds
+    vals = expand(seed, n + t, r)
+    for k, special in enumerate((0, 1, r - 1)):
+        vals[(seed + k) % n] = special
+        vals[n + ((seed >> 8) + k) % t] = special
+    return vals[:n], vals[n:]
 
 
 def poseidon_constants(seed, t, full_rounds, partial_rounds, r):
@@ -497,14 +594,15 @@ class ModelBackend:
 def sizes(steps):
     """-> [(index, kind, field, scalars per row)] of the steps that call a library and have a size: the length of a row of the largest operand; for
     a sparse product the entries of its matrix (its work); for a Poseidon step its lanes: the states of a permute, the rows of a sponge, the nodes
-    of a tree's first level.  What "large" (>= LARGE) and "small" (<= SMALL) are measured on."""
+    of a tree's first level; for a column step its outputs (of a pair: to a column), and none where its output cuts an operand: the library is
+    not called.  What "large" (>= LARGE) and "small" (<= SMALL) are measured on."""
     out, nnz, width = [], {}, {}
     for i, (kind, f, a) in enumerate(steps):
         if kind == "matrix":
             nnz[f, a["slot"]] = len(a["col_idx"])
-        if kind == "poseidon":
+        if kind in HASH_MAKERS:
             width[f, a["slot"]] = a["t"]
-        if a.get("overlap") or kind not in LIBRARY:
+        if a.get("overlap") or kind not in LIBRARY or column_cut((kind, f, a)):
             continue
         if kind in ("map", "inverse"):
             n = a["a"][1]
@@ -512,7 +610,7 @@ def sizes(steps):
             n = a["a"][1] // a["batch"]
         elif kind == "fft":
             n = 1 << a["log_n"]
-        elif kind in ("combine", "eq"):
+        elif kind in ("combine", "eq", "expand", "pair", "gather"):
             n = a["out"][1]
         elif kind in ("powers", "mle_fold", "mle_eval", "round", "gate", "mult"):
             n = a["n"]
@@ -534,11 +632,12 @@ def sizes(steps):
 
 # ---- the generator ---------------------------------------------------------------------------------------------------------------------------------
 _WEIGHT = {"map": 10, "inverse": 5, "scan": 8, "fft": 8, "eval": 4, "divide": 5, "dot": 4, "combine": 4, "powers": 4, "mle_fold": 5, "mle_eval": 4, "eq": 3,
-           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "poseidon": 5, "permute": 9, "sponge": 8, "tree": 6, "format": 5, "hook": 7, "close": 3,
-           "stream": 3, "overlap": 3}
+           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "poseidon": 4, "poseidon2": 4, "permute": 10, "sponge": 9, "tree": 7,
+           "expand": 7, "pair": 6, "gather": 6, "words": 4, "format": 5, "hook": 8, "close": 3, "stream": 3, "overlap": 4}
 _LEN_WEIGHT = {1: 6, 2: 6, 63: 6, 64: 6, 65: 6, 255: 3, 256: 3, 257: 3, 1023: 1.6, 1024: 1.6, 1025: 1.6, 2051: 0.9, 4097: 0.6}
 _PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "matvec", "gate", "table", "mult", "permute", "sponge", "tree")
-_OVERLAPS = ("map", "inverse", "scan", "divide", "combine", "mle_fold", "matvec")
+_OVERLAPS = ("map", "inverse", "scan", "divide", "combine", "mle_fold", "matvec", "expand", "pair", "gather")  # (the last three: cuts, refused by the Python layer)
+_BAD_WORDS = 0.07  # how often a word vector drawn for a column call is one that must be refused
 
 
 class _Gen:
@@ -548,8 +647,10 @@ class _Gen:
         self.mont = [False] * len(fields)
         self.mats = [{} for _ in fields]  # slot -> (rows, cols, transpose, row_ptr, col_idx)
         self.tabs = [{} for _ in fields]  # slot -> (n, form, the range it was made of)
-        self.hashes = [{} for _ in fields]  # slot -> (t, rounds)
+        self.hashes = [{} for _ in fields]  # slot -> (t, the work of one permutation, the handle's kind)
+        self.words = [{} for _ in fields]  # slot -> {"what": "counts" / "idx", "n": its length, "total": the sum of the counts, "bound": the least n_a of an idx}
         self.host_before = False  # was the last call of libmsm_frhash a host-form one
+        self.last_hash, self.force_slot, self.no_plant = None, None, False  # the handle of the last hash call; the handle the next one is to take
         self.side = False
         self.steps = []
         self.prev_f, self.follow = None, None  # follow: (field, kind) of a large step that a small one of the same entry point is to follow
@@ -603,7 +704,7 @@ class _Gen:
 
     def maybe_plant(self, f, kind, spots):
         """before a step that reads the scalars `spots` (off16 each): sometimes plant a value >= r in one of them"""
-        if self.plant_ok and kind in _PLANTABLE and spots and self.rnd.random() < 0.09:
+        if self.plant_ok and not self.no_plant and kind in _PLANTABLE and spots and self.rnd.random() < 0.09:
             r = self.r[f]
             self.emit("plant", f, at=self.rnd.choice(spots), value=self.rnd.choice((r, r + 1, (1 << 256) - 1, r + self.rnd.randrange(1 << 200))))
 
@@ -889,35 +990,211 @@ class _Gen:
         else:
             v = self.place(batch * stride)
         out = self.place(t_n, [v, [v[0] + 2 * v[1] - 2, 1]])
+        before = len(self.steps)
         if form == self.mont[f]:
             self.maybe_plant(f, "mult", self.spots(v, self.rnd, range(batch), stride, n))
-        self.emit("mult", f, slot=slot, v=v, batch=batch, n=n, out=out, indices=self.rnd.random() < 0.6, counts=self.rnd.random() < 0.5)
+        indices, islot = self.rnd.random() < 0.6, None
+        if indices and form == self.mont[f] and len(self.steps) == before and self.rnd.random() < 0.5:  # the call computes: its indices stay, -1 where a value is missing
+            islot = self.rnd.randrange(WORD_SLOTS)
+            self.words[f][islot] = {"what": "idx", "n": batch * n, "bound": t_n}
+        self.emit("mult", f, slot=slot, v=v, batch=batch, n=n, out=out, indices=indices, counts=self.rnd.random() < 0.5, cslot=None, islot=islot)
         return n
 
-    # ---- libmsm_frhash: a handle (poseidon) and the three calls on it.  The work of a call -- permutations x rounds x t^2 -- stays within HASH_WORK.
+    def chain(self, f, n_t, batch, n, want):
+        """a table over n_t scalars and at once, under the same form and with nothing written between, the count of its source's first batch
+        rows of n scalars -- every value is found, so the counts add up to batch * n -- which keeps its counts or indices (`want`) in a word
+        slot: what libmsm_frcol is there to be chained behind.  -> (the table's source, the slot)"""
+        assert batch * n <= n_t
+        if len(self.tabs[f]) == 3:
+            self.g_close(f, False, "tab")
+        slot = self.rnd.choice([s for s in range(3) if s not in self.tabs[f]])
+        t = self.place(n_t)
+        if self.fields[f] != "grumpkin" and self.rnd.random() < 0.3:  # repeated values: every match goes to the lowest index, the other counts are 0
+            self.emit("powers", f, g=self.rnd.choice((1, self.r[f] - 1)), n=n_t, scale=self.scalar(f), out=list(t))
+        self.tabs[f][slot] = (n_t, self.mont[f], list(t))
+        self.emit("table", f, slot=slot, t=list(t), n=n_t)
+        wslot = self.rnd.randrange(WORD_SLOTS)
+        other = (wslot + 1 + self.rnd.randrange(WORD_SLOTS - 1)) % WORD_SLOTS if self.rnd.random() < 0.3 else None  # the other vector too
+        cslot, islot = (wslot, other) if want == "counts" else (other, wslot)
+        for s, rec in ((cslot, {"what": "counts", "n": n_t, "total": batch * n}), (islot, {"what": "idx", "n": batch * n, "bound": n_t})):
+            if s is not None:
+                self.words[f][s] = rec
+        self.emit("mult", f, slot=slot, v=[t[0], batch * n], batch=batch, n=n, out=self.place(n_t, [t]), indices=islot is not None, counts=cslot is not None, cslot=cslot,
+                  islot=islot)
+        return t, wslot
+
+    # ---- libmsm_frcol: word vectors (words, or a count's that a chain left) and the three calls that take them.  `overlap`: an output that cuts an operand.
+    def g_words(self, f, small):
+        """a vector for a later column call to find: counts or indices"""
+        if self.rnd.random() < 0.55:
+            n_t = self.length(small, 2051)
+            self.draw_counts(f, n_t, self.length(small, BANK - n_t))
+        else:
+            self.draw_indices(f, self.length(small), self.length(small))
+
+    def draw_counts(self, f, n_t, total, zeros=None):
+        """a `words` step of n_t counts that add up to `total` -- or, rarely, do not: off by one -> the slot.  zeros: must some counts be 0?"""
+        names = [c for c in frcol_model.COUNT_SETS if zeros is None or (c != "all ones") == zeros]
+        values = frcol_model.counts(self.rnd.choice(names), n_t, total, self.rnd)
+        if self.rnd.random() < _BAD_WORDS:
+            at = self.rnd.choice([j for j, c in enumerate(values) if c] or [0])
+            values[at] += 1 if self.rnd.random() < 0.5 or not values[at] else -1
+        return self.put_words(f, values, {"what": "counts", "n": n_t, "total": total})
+
+    def draw_indices(self, f, n_a, n):
+        """a `words` step of n indices into n_a scalars, MISSING among them -- or, rarely, one that is n_a or more -> the slot"""
+        values = [MISSING if self.rnd.random() < 0.2 else self.rnd.randrange(n_a) for _ in range(n)]
+        if self.rnd.random() < _BAD_WORDS:
+            values[self.rnd.randrange(n)] = self.rnd.choice((n_a, n_a, n_a + 1, MISSING - 1))
+        return self.put_words(f, values, {"what": "idx", "n": n, "bound": n_a})
+
+    def put_words(self, f, values, rec):
+        slot = self.rnd.randrange(WORD_SLOTS)
+        self.words[f][slot] = rec
+        self.emit("words", f, slot=slot, values=values)
+        return slot
+
+    def live_words(self, f, what, small, fits=lambda w: True):
+        return [s for s, w in sorted(self.words[f].items()) if w["what"] == what and fits(w) and (not small or w["n"] <= SMALL)]
+
+    def column_out(self, n, avoid, cut):
+        """an output of n scalars apart from the ranges `avoid` -- or, where `cut` names one of them, across it: from its start or from inside it"""
+        if cut is None:
+            return self.place(n, avoid)
+        if cut[1] > 1 and self.rnd.random() < 0.7:
+            return self.shifted(cut, n, 0)
+        half, bank = self.bank_of(cut)
+        base = half * (2 * HALF + 1) + 2 * bank * BANK
+        if (cut[0] - base) // 2 + n > BANK:  # (no room behind it in its bank: it moves to the bank's start, as in shifted)
+            cut[0] = base
+        return [cut[0], n]
+
+    def g_expand(self, f, small, overlap=False):
+        c, bias = self.rnd.random(), self.rnd.randrange(2)
+        live = self.live_words(f, "counts", small, lambda w: 1 <= w["total"] + bias * w["n"] <= (SMALL if small else BANK))
+        t = None
+        if c < 0.04 and not small:  # four counts of 2^31: with the bias their sum is n_out in 32 bits, and 2^33 + 4 in fact
+            n_t, bias, total = 4, 1, 0
+            slot = self.put_words(f, [0x80000000] * 4, {"what": "counts", "n": 4, "total": 0})
+        elif live and c < 0.35:  # a vector that is there: a count's that an earlier chain left, as the call left it, or an earlier step's
+            slot = self.rnd.choice(live)
+            n_t, total = self.words[f][slot]["n"], self.words[f][slot]["total"]
+        elif c < 0.65 and not overlap:
+            n_t = self.rnd.choice((1, 2, 21, 32)) if small else self.length(False, 1025)  # (a lookup table: as long as g_table's)
+            n = self.rnd.choice([k for k in (1, 2, 21, 32) + LENGTHS if k <= n_t])
+            batch = self.rnd.choice([b for b in (1, 1, 2, 3, 5) if b * n <= n_t])
+            total = batch * n
+            t, slot = self.chain(f, n_t, batch, n, "counts")
+            t = list(t) if self.rnd.random() < 0.5 else None  # the table's own source, or any other range
+        else:
+            n_out = self.length(small)
+            bias = bias if n_out > 1 else 0
+            n_t = self.rnd.choice([k for k in LENGTHS if k < n_out]) if bias else self.length(small or self.rnd.random() < 0.3, 2051)
+            total = n_out - bias * n_t
+            slot = self.draw_counts(f, n_t, total)
+        t = self.place(n_t) if t is None else t
+        out = self.column_out(total + bias * n_t, [t], t if overlap else None)
+        self.emit("expand", f, t=t, counts=slot, bias=bias, out=out)
+        return None if overlap else out[1]
+
+    def g_pair(self, f, small, overlap=False):
+        c = self.rnd.random()
+        live = self.live_words(f, "counts", small, lambda w: w["total"] == w["n"])
+        t = None
+        if c < 0.03 and not small:
+            n = 4
+            slot = self.put_words(f, [0x80000000] * 4, {"what": "counts", "n": 4, "total": 0})
+        elif live and c < 0.25:
+            slot = self.rnd.choice(live)
+            n = self.words[f][slot]["n"]
+        elif c < 0.65 and not overlap:  # a count of the table's own source, whole: batch rows of n / batch
+            n = self.length(small, 1025)
+            batch = self.rnd.choice([b for b in (1, 1, 2, 3, 5) if n % b == 0])
+            t, slot = self.chain(f, n, batch, n // batch, "counts")
+        else:
+            n = self.length(small)
+            slot = self.draw_counts(f, n, n, zeros=self.rnd.random() < 0.7)
+        t = self.place(n) if t is None else list(t)
+        cut = self.rnd.randrange(3) if overlap else None  # A' across t, S' across t, S' across A'
+        out = self.column_out(n, [t], t if cut == 0 else None)
+        s_out = self.column_out(n, [t, out], None if cut in (None, 0) else t if cut == 1 else out)
+        self.emit("pair", f, t=t, counts=slot, out=out, s_out=s_out)
+        return None if overlap else n
+
+    def g_gather(self, f, small, overlap=False):
+        c = self.rnd.random()
+        live = self.live_words(f, "idx", small)
+        if live and c < 0.4:  # indices that are there: a count's, with -1 for a value it did not find, or an earlier step's
+            slot = self.rnd.choice(live)
+        elif c < 0.6 and not overlap:
+            n_t = self.rnd.choice((1, 2, 21, 32)) if small else self.length(False, 1025)  # (a lookup table: as long as g_table's)
+            n = self.rnd.choice([k for k in (1, 2, 21, 32) + LENGTHS if k <= n_t])
+            _, slot = self.chain(f, n_t, self.rnd.choice([b for b in (1, 1, 2, 3, 5) if b * n <= n_t]), n, "idx")
+        else:
+            slot = self.draw_indices(f, self.length(small and self.rnd.random() < 0.5), self.length(small))
+        w = self.words[f][slot]
+        a = self.place(min(w["bound"] + self.rnd.choice((0, 0, 3)), BANK))
+        out = self.column_out(w["n"], [a], a if overlap else None)
+        self.emit("gather", f, a=a, idx=slot, out=out)
+        return None if overlap else w["n"]
+
+    # ---- libmsm_frhash: a handle of either kind (poseidon, poseidon2) and the three calls on it.  The work of a call stays within HASH_WORK or HASH2_WORK.
     def g_poseidon(self, f, small):
         if len(self.hashes[f]) == 3:
             self.g_close(f, small, "hash")
         slot = self.rnd.choice([s for s in range(3) if s not in self.hashes[f]])
         edge = HASH_BOUNDARY[self.fields[f]]
         t = self.rnd.choices(HASH_WIDTHS, [4 if w in edge else 2 if w <= 4 else 1 for w in HASH_WIDTHS])[0]  # (t <= 4: the widths that a large call can have)
+        t = self.width_of_the_other_kind(f, "poseidon2", t)
+        rf, rp = self.rounds()
+        self.hashes[f][slot] = (t, (rf + rp) * t * t, "poseidon")
+        self.emit("poseidon", f, slot=slot, t=t, full_rounds=rf, partial_rounds=rp, seed=self.rnd.randrange(1 << 30), **self.convention(f, t))
+        return None
+
+    def g_poseidon2(self, f, small):
+        if len(self.hashes[f]) == 3:
+            self.g_close(f, small, "hash")
+        slot = self.rnd.choice([s for s in range(3) if s not in self.hashes[f]])
+        t = self.rnd.choice(HASH2_WIDTHS)
+        t = self.width_of_the_other_kind(f, "poseidon", t, HASH2_WIDTHS)
+        rf, rp = self.rounds()
+        self.hashes[f][slot] = (t, 3 * rf * t + rp * (t + 3), "poseidon2")
+        self.emit("poseidon2", f, slot=slot, t=t, full_rounds=rf, partial_rounds=rp, seed=self.rnd.randrange(1 << 30), **self.convention(f, t))
+        return None
+
+    def rounds(self):
         rf, rp = self.rnd.choice(((2, 0), (2, 0), (2, 1), (2, 1), (2, 3), (4, 2), (8, 0)))
         if self.rnd.random() < 0.06:  # as long as the standard shapes: its calls have few lanes, by their work
             rf, rp = 8, self.rnd.randrange(56, 67)
+        return rf, rp
+
+    def convention(self, f, t):
+        """a sponge's capacity convention: circomlib's (0, 0, 0), halo2's (L 2^64, t - 1, 0), neptune's (2^arity - 1, 0, 1), and others"""
         r = self.r[f]
-        self.hashes[f][slot] = (t, rf + rp)
-        self.emit("poseidon", f, slot=slot, t=t, full_rounds=rf, partial_rounds=rp, seed=self.rnd.randrange(1 << 30),
-                  capacity=self.rnd.choice((0, (3 << 64) % r, (1 << (t - 1)) - 1, r - 1, self.rnd.randrange(r))), capacity_at=self.rnd.choice((0, t - 1, self.rnd.randrange(t))),
-                  out_at=self.rnd.choice((0, 1 % t, self.rnd.randrange(t))))
-        return None
+        return {"capacity": self.rnd.choice((0, (3 << 64) % r, (1 << (t - 1)) - 1, r - 1, self.rnd.randrange(r))), "capacity_at": self.rnd.choice((0, t - 1, self.rnd.randrange(t))),
+                "out_at": self.rnd.choice((0, 1 % t, self.rnd.randrange(t)))}
+
+    def width_of_the_other_kind(self, f, kind, t, widths=HASH_WIDTHS):
+        """t, or sometimes the width of a live handle of the other kind: both kinds alive at one width"""
+        there = sorted({h[0] for h in self.hashes[f].values() if h[2] == kind and h[0] in widths})
+        return self.rnd.choice(there) if there and self.rnd.random() < 0.5 else t
 
     def hash_handle(self, f, small):
         """-> (slot, t, the permutations one call may run): a live handle, made first where there is none"""
-        if not self.hashes[f] or (len(self.hashes[f]) < 3 and self.rnd.random() < 0.15):
-            self.g_poseidon(f, small)
-        slot = self.rnd.choice(sorted(self.hashes[f]))
-        t, rounds = self.hashes[f][slot]
-        return slot, t, max(HASH_WORK // (rounds * t * t), 1)
+        if self.force_slot is not None:
+            slot = self.force_slot
+        else:
+            if not self.hashes[f] or (len(self.hashes[f]) < 3 and self.rnd.random() < 0.15):
+                (self.g_poseidon if self.rnd.random() < 0.5 else self.g_poseidon2)(f, small)
+            slot = self.rnd.choice(sorted(self.hashes[f]))
+        t, unit, kind = self.hashes[f][slot]
+        self.last_hash = (f, slot)
+        return slot, t, max((HASH_WORK if kind == "poseidon" else HASH2_WORK) // unit, 1)
+
+    def twin(self, f, slot):
+        """the live handles of the other kind at the width of handle `slot`"""
+        t, _, kind = self.hashes[f][slot]
+        return [s for s, h in sorted(self.hashes[f].items()) if h[0] == t and h[2] != kind]
 
     def lanes(self, small, cap):
         pool = [n for n in LENGTHS if n <= cap and (n <= SMALL or not small)]
@@ -957,7 +1234,7 @@ class _Gen:
             rows = sorted({0, batch - 1, self.rnd.randrange(batch)})
             before = len(self.steps)
             self.maybe_plant(f, "sponge", self.spots(a, self.rnd, rows, stride, length))
-            if len(self.steps) == before and self.plant_ok and batch > 1 and stride > length and self.rnd.random() < 0.3:
+            if len(self.steps) == before and self.plant_ok and not self.no_plant and batch > 1 and stride > length and self.rnd.random() < 0.3:
                 # a value that is not below r in the padding behind the first row (far from every output's neighbourhood): not read, so not refused
                 self.emit("plant", f, at=a[0] + 2 * self.rnd.randrange(length, stride), value=self.rnd.choice((self.r[f], (1 << 256) - 1)), quiet=True)
         self.emit("sponge", f, slot=slot, a=a, batch=batch, length=length, out=out, host=host)
@@ -1023,13 +1300,23 @@ class _Gen:
                 small = True
             else:
                 f = self.rnd.randrange(len(self.fields))
-                if self.prev_f is not None and len(self.fields) > 1 and self.rnd.random() < 0.6:  # the other field's turn
+                if self.prev_f is not None and len(self.fields) > 1 and self.rnd.random() < 0.8:  # the other field's turn (a draw may be several steps on one field)
                     f = 1 - self.prev_f
                 pool = [k for k in self.kinds if self.serves(f, k)]
                 kind = self.rnd.choices(pool, [_WEIGHT[k] for k in pool])[0]
                 small = False
-            self.follow = None
+            self.follow, self.last_hash = None, None
             per_row = getattr(self, "g_" + kind)(f, small)
+            if kind in HASH_CALLS and self.last_hash and self.twin(*self.last_hash) and self.rnd.random() < 0.5:
+                # the same call at once on a live handle of the OTHER kind at the same width (the two kinds share a table's head and the lane
+                # functions' template): nothing in between, so no planted value
+                self.force_slot, self.no_plant = self.rnd.choice(self.twin(*self.last_hash)), True
+                getattr(self, "g_" + kind)(f, small)
+                self.force_slot, self.no_plant = None, False
+            elif kind in COLUMN_CALLS and not small and per_row is not None and per_row > SMALL and self.rnd.random() < 0.4:
+                # libmsm_frcol's nodes, rel, used and z only grow and are per device, not per field: a small call of the same entry point right
+                # behind one that is larger, not only behind a "large" one
+                getattr(self, "g_" + kind)(f, True)
             self.prev_f = f
             if per_row is not None and per_row >= LARGE and not small:
                 self.follow = (f, kind)

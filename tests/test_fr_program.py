@@ -10,7 +10,7 @@ import os
 import pytest
 
 from tests import fr_program as P
-from tests import frhash_model, frlook_model, frvec_model
+from tests import frhash2_model, frhash_model, frlook_model, frvec_model
 from tests.test_gpu_fr_fuzz import COMMITTED, SECOND
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +18,7 @@ _spec = importlib.util.spec_from_file_location("fuzz_fr", os.path.join(ROOT, "to
 fuzz_fr = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(fuzz_fr)
 
-VECTOR_KEYS = ("a", "b", "c", "out", "x", "v", "t", "scale", "leaves")
+VECTOR_KEYS = ("a", "b", "c", "out", "s_out", "x", "v", "t", "scale", "leaves")
 
 
 @pytest.fixture(scope="module")
@@ -95,7 +95,7 @@ def test_every_library_sees_large_then_small_and_a_planted_value(programs):
                 assert nxt[0] in P.LIBRARY and nxt[1] == s[1]  # (the very next step reads it)
                 planted.add(P.LIBRARY[nxt[0]])
     assert pairs == set(P.LIBRARIES), pairs
-    assert planted == set(P.LIBRARIES), planted
+    assert planted == set(P.LIBRARIES) - {"frcol"}, planted  # (libmsm_frcol does not compare with r: a planted value would be copied into the arena)
 
 
 def test_transforms_change_the_root_at_one_length(programs):
@@ -124,20 +124,21 @@ def test_two_fields_take_turns(programs):
 
 
 def hash_calls(steps):
-    """the calls of libmsm_frhash of a program, in order: dicts of the step's index and kind, its field index, the handle (its `poseidon` step's
-    index) and width, the field's form and the stream at the call, and whether it is a host-form call, cuts its input (refused by the Python
-    layer: the library is not called) or follows a planted value (refused by the library)"""
+    """the calls of libmsm_frhash of a program, in order: dicts of the step's index and kind, its field index, the handle (its `poseidon` or
+    `poseidon2` step's index), its width and its kind (`made`: that step's kind), the field's form and the stream at the call, and whether it
+    is a host-form call, cuts its input (refused by the Python layer: the library is not called) or follows a planted value (refused by the
+    library)"""
     mont, side, made, out = {}, False, {}, []
     for i, (kind, f, a) in enumerate(steps):
         if kind == "format":
             mont[f] = a["mont"]
         elif kind == "stream":
             side = a["side"]
-        elif kind == "poseidon":
-            made[f, a["slot"]] = (i, a["t"])
+        elif kind in P.HASH_MAKERS:
+            made[f, a["slot"]] = (i, a["t"], kind)
         elif kind in P.HASH_CALLS:
-            handle, t = made[f, a["slot"]]
-            out.append({"index": i, "kind": kind, "f": f, "handle": handle, "t": t, "mont": bool(mont.get(f)), "side": side, "host": a["host"],
+            handle, t, maker = made[f, a["slot"]]
+            out.append({"index": i, "kind": kind, "f": f, "handle": handle, "t": t, "made": maker, "mont": bool(mont.get(f)), "side": side, "host": a["host"],
                         "cut": P.hash_cut(steps[i]), "planted": steps[i - 1][0] == "plant" and not steps[i - 1][2].get("quiet")})
     return out
 
@@ -147,11 +148,45 @@ def test_hashing_reaches_each_fields_tidy_boundary(programs):
     used = {}
     for fields, _, _, steps in programs:
         for c in hash_calls(steps):
-            if c["kind"] in ("permute", "sponge") and not c["cut"] and not c["planted"]:
+            if c["made"] == "poseidon" and c["kind"] in ("permute", "sponge") and not c["cut"] and not c["planted"]:  # (Poseidon2 tidies by rules of its own)
                 used[fields[c["f"]], c["t"]] = used.get((fields[c["f"]], c["t"]), 0) + 1
     for field, widths in P.HASH_BOUNDARY.items():
         assert all(used.get((field, t), 0) >= 3 for t in widths), (field, used)
     assert {t for _, t in used} == set(P.HASH_WIDTHS)
+
+
+def test_poseidon2_runs_at_every_width_of_every_field(programs):
+    """calls that compute, on every field at every Poseidon2 width: on BLS12-381 t = 3 tidies the S-box input and t = 12 the sums, and no other
+    field does either"""
+    used = {}
+    for fields, _, _, steps in programs:
+        for c in hash_calls(steps):
+            if c["made"] == "poseidon2" and not c["cut"] and not c["planted"]:
+                used[fields[c["f"]], c["t"]] = used.get((fields[c["f"]], c["t"]), 0) + 1
+    assert all(used.get((field, t), 0) >= 3 for field in P.FIELD_R for t in P.HASH2_WIDTHS), used
+
+
+def test_the_two_kinds_of_handle_alternate_at_one_width(programs):
+    """a call that computes on a handle of one kind, and in the very next step one on a handle of the other kind at the same width on the same
+    field: both ways round"""
+    to = {"poseidon": 0, "poseidon2": 0}
+    for _, _, _, steps in programs:
+        calls = [c for c in hash_calls(steps) if not c["cut"] and not c["planted"]]
+        for before, c in zip(calls, calls[1:]):
+            if c["index"] == before["index"] + 1 and c["f"] == before["f"] and c["t"] == before["t"] and c["made"] != before["made"]:
+                to[c["made"]] += 1
+    assert min(to.values()) >= 5, to
+
+
+def test_a_poseidon2_handle_first_goes_to_the_device_under_either_form_on_either_stream(programs):
+    first_form, first_side, seen = {False: 0, True: 0}, {False: 0, True: 0}, set()
+    for n, (_, _, _, steps) in enumerate(programs):
+        for c in hash_calls(steps):
+            if c["made"] == "poseidon2" and not c["cut"] and (n, c["handle"]) not in seen:  # (a cut never reaches the library)
+                seen.add((n, c["handle"]))
+                first_form[c["mont"]] += 1
+                first_side[c["side"]] += 1
+    assert min(first_form.values()) >= 5 and min(first_side.values()) >= 5, (first_form, first_side)
 
 
 def test_hash_handles_meet_both_forms_both_streams_and_one_another(programs):
@@ -170,7 +205,7 @@ def test_hash_handles_meet_both_forms_both_streams_and_one_another(programs):
             after_another += c["index"] == before["index"] + 1 and (before["f"], before["handle"]) != (c["f"], c["handle"]) and before["t"] != c["t"]
         made = {}
         for i, (kind, f, a) in enumerate(steps):
-            if kind == "poseidon":
+            if kind in P.HASH_MAKERS:
                 made[f, a["slot"]] = i
             elif kind == "close" and a["what"] == "hash":
                 unused_closed += (n, made[f, a["slot"]]) not in forms
@@ -195,6 +230,77 @@ def test_host_form_hashing_sees_large_then_small_and_refusals_stay_rare(programs
     assert pairs >= 1, pairs
     assert total > 500 and 5 * refused <= total, (refused, total)
     assert 20 * refused >= total  # (but they are there)
+
+
+def column_calls(steps):
+    """the calls of libmsm_frcol of a program, in order: dicts of the step's index and kind, its field index, the field's form and the hooks
+    that are set at the call, what filled its word slot ("mult": the very tensor a lookup call returned; "words": an uploaded vector), the
+    length of its table, its operands, and how it ends -- None: it computes; "cut": an output shares bytes with an operand; "sum": the counts
+    do not add up to the outputs; "index": an index is neither inside `a` nor MISSING.  Worked out from the steps alone: a `mult` step names
+    a slot only where it computes, its indices lie below its table's length, and where it keeps its counts every value it looks up is in
+    the table (fr_program._Gen.chain), so that they add up to batch * n."""
+    mont, hooks, slots, out = {}, {}, {}, []
+    for i, (kind, f, a) in enumerate(steps):
+        if kind == "format":
+            mont[f] = a["mont"]
+        elif kind == "hook":
+            hooks[a["name"]] = a["value"]
+        elif kind == "words":
+            slots[f, a["slot"]] = {"from": "words", "total": sum(a["values"]), "n": len(a["values"]), "least": max([w + 1 for w in a["values"] if w != P.MISSING] or [0])}
+        elif kind == "mult":
+            if a["cslot"] is not None:
+                slots[f, a["cslot"]] = {"from": "mult", "total": a["batch"] * a["n"], "n": a["out"][1]}
+            if a["islot"] is not None:
+                slots[f, a["islot"]] = {"from": "mult", "n": a["batch"] * a["n"], "least": a["out"][1]}  # (the least n_a that holds every index)
+        elif kind in P.COLUMN_CALLS:
+            w = slots[f, a["idx" if kind == "gather" else "counts"]]
+            if P.column_cut(steps[i]):
+                end = "cut"
+            elif kind == "gather":
+                end = "index" if w["least"] > a["a"][1] else None
+            else:
+                end = "sum" if w["total"] + a.get("bias", 0) * w["n"] != a["out"][1] else None
+            out.append({"index": i, "kind": kind, "f": f, "mont": bool(mont.get(f)), "hooks": {h for h, v in hooks.items() if v}, "from": w["from"], "n_t": a["a" if kind == "gather" else "t"][1],
+                        "operands": [a[k] for k in ("t", "a", "out", "s_out") if k in a], "end": end})
+    return out
+
+
+def test_column_calls_take_what_a_lookup_left_at_either_alignment_under_either_form(programs):
+    calls = [(fields[c["f"]], c) for fields, _, _, steps in programs for c in column_calls(steps)]
+    computing = [(field, c) for field, c in calls if c["end"] is None]
+    assert min(sum(c["from"] == "mult" and c["kind"] == kind for _, c in computing) for kind in P.COLUMN_CALLS) >= 5  # the chain the library exists for
+    assert sum(rng[0] % 2 for _, c in computing for rng in c["operands"]) >= 5  # 32 bytes as two 16-byte accesses: 16 mod 32 is legal
+    assert {(c["kind"], c["mont"]) for _, c in computing} == {(kind, form) for kind in P.COLUMN_CALLS for form in (False, True)}
+    assert {c["kind"] for field, c in computing if field == "grumpkin"} == set(P.COLUMN_CALLS)
+    assert sum("frcol_test_tile" in c["hooks"] and len(c["hooks"]) > 1 for _, c in computing) >= 5
+    assert sum("frcol_test_tile" in c["hooks"] and "frlook_test_hash_bits" in c["hooks"] and c["from"] == "mult" for _, c in computing) >= 1
+    assert any(c["kind"] == "expand" and c["n_t"] >= 1025 and "frcol_test_tile" not in c["hooks"] for _, c in computing)  # two tiles of the design's 1024
+
+
+def test_column_refusals_stay_rare_but_present(programs):
+    """a wrong sum, a bad index and a cut: together no more than a fifth of the column calls, so that they do not hide the paths that compute,
+    and no fewer than a twentieth; and every vector that must be refused is among them"""
+    calls = [c for _, _, _, steps in programs for c in column_calls(steps)]
+    ends = [c["end"] for c in calls]
+    refused = sum(e is not None for e in ends)
+    assert len(calls) > 300 and 5 * refused <= len(calls) and 20 * refused >= len(calls), (refused, len(calls))
+    assert min(ends.count(e) for e in ("cut", "sum", "index")) >= 3, {e: ends.count(e) for e in set(ends)}
+    assert {(c["kind"], c["end"]) for c in calls if c["end"]} >= {("expand", "cut"), ("pair", "cut"), ("gather", "cut"), ("expand", "sum"), ("pair", "sum"), ("gather", "index")}
+    wrapped = off_by_one = at_n_a = 0
+    for _, _, _, steps in programs:
+        words = {}
+        for kind, f, a in steps:
+            if kind == "words":
+                words[f, a["slot"]] = a["values"]
+            elif kind == "mult":
+                words.pop((f, a["cslot"]), None), words.pop((f, a["islot"]), None)
+            elif kind in ("expand", "pair") and (f, a["counts"]) in words and not P.column_cut((kind, f, a)):
+                off = sum(words[f, a["counts"]]) + a.get("bias", 0) * a["t"][1] - a["out"][1]
+                wrapped += off != 0 and off % (1 << 32) == 0  # a sum that is right in 32 bits
+                off_by_one += off in (1, -1)
+            elif kind == "gather" and (f, a["idx"]) in words and not P.column_cut((kind, f, a)):
+                at_n_a += a["a"][1] in words[f, a["idx"]]
+    assert wrapped >= 1 and off_by_one >= 3 and at_n_a >= 1, (wrapped, off_by_one, at_n_a)
 
 
 def test_the_loop_passes_a_backend_that_is_the_model(capsys):
@@ -348,12 +454,13 @@ class MontComputedAsCanonical(Faulty):
     def faulty(self, kind, f, a):
         if not (kind == "inverse" or kind == "map" and a["op"] == "mul") or not self.m.mont[f] or self.m.planted[f] or a.get("out") and P.Model._partial(a["out"], [a["a"]]):
             return self.plain_call(kind, f, a)
-        self.m.mont[f] = False
-        try:
-            host = self.plain_call(kind, f, a)
-        finally:
-            self.m.mont[f] = True
-        self.fired()
+        there = copy.deepcopy(self.m)
+        there.mont[f] = False
+        getattr(there, "op_" + kind)(f, **a)
+        host, dst = self.plain_call(kind, f, a), a["out"] or a["a"]
+        if there.raw(f, dst) != self.m.raw(f, dst):  # (a product with 0 is 0 in either form: the fault shows where the bytes differ)
+            self.m.put(f, dst[0], there.raw(f, dst))
+            self.fired()
         return host
 
 
@@ -411,6 +518,8 @@ class HandleAnswersForTheOneBefore(HashFault):
             else:
                 self.stale.pop((f, a["slot"]), None)
             self.seed_before[f] = a["seed"]
+        elif kind == "poseidon2":  # (a handle of the other kind in that slot: it answers for itself)
+            self.stale.pop((f, a["slot"]), None)
         return super().faulty(kind, f, a)
 
     def answer(self, kind, f, a, p, right):
@@ -506,9 +615,138 @@ class FirstTidiedWidthGoesWrong(HashFault):
         return [plain[1]] + plain[1:]
 
 
+def hashed_with(other, m, kind, f, a):
+    """the plain values of a call of libmsm_frhash as the permutation `other` gives them"""
+    v = m.plain(f, a["leaves" if kind == "tree" else "a"])
+    if kind == "permute":
+        return [x for i in range(0, len(v), other.t) for x in other.permute(v[i:i + other.t])]
+    if kind == "sponge":
+        stride = len(v) // a["batch"]
+        return [other.hash(v[k * stride:k * stride + a["length"]]) for k in range(a["batch"])]
+    return other.merkle_chain(v[0], a["levels"]) if other.t == 2 else [x for level in other.merkle(v) for x in level]
+
+
+class SumTakenLate(frhash2_model.Poseidon2):
+    def internal(self, s):
+        out = list(s)
+        for i in range(self.t):  # (the sum of the state as it stands: behind element 0 it holds what has already changed)
+            out[i] = (self.mu[i] * out[i] + sum(out)) % self.r
+        return out
+
+
+class InternalSumTakenLate(HashFault):
+    """a Poseidon2 internal round whose sum is taken after s[0]'s neighbours changed: every element but the first takes a sum that holds the
+    new values of those before it"""
+    fields_to_run = "bls12_381"
+
+    def answer(self, kind, f, a, p, right):
+        if not isinstance(p, frhash2_model.Poseidon2) or not p.partial_rounds or (kind == "permute" and a["out"] is None and not a["host"]):  # (in place the input is gone)
+            return None
+        return hashed_with(SumTakenLate(p.r, p.t, p.full_rounds, p.partial_rounds, p.rc, p.mu, p.capacity, p.capacity_at, p.out_at), self.m, kind, f, a)
+
+
+class AnsweredWithTheOtherKindsCode(HashFault):
+    """a Poseidon2 handle answered with the code of the other kind: its table read as Poseidon's -- the round constants as far as they go and
+    round again, the internal layer's matrix J + diag(mu) as the MDS matrix"""
+    fields_to_run = "pallas,vesta"
+
+    def answer(self, kind, f, a, p, right):
+        if not isinstance(p, frhash2_model.Poseidon2) or (kind == "permute" and a["out"] is None and not a["host"]):
+            return None
+        need = (p.full_rounds + p.partial_rounds) * p.t
+        rc = (p.rc * (need // len(p.rc) + 1))[:need]
+        mds = [[1 + (p.mu[i] if i == j else 0) for j in range(p.t)] for i in range(p.t)]
+        return hashed_with(frhash_model.Poseidon(p.r, p.t, p.full_rounds, p.partial_rounds, rc, mds, p.capacity, p.capacity_at, p.out_at), self.m, kind, f, a)
+
+
+class ColumnFault(Faulty):
+    """a fault in libmsm_frcol: spoil(kind, f, a, before) changes what a call that computed left in the arena and calls fired() where that
+    shows; before: the bytes of its outputs as they were"""
+
+    def spoil(self, kind, f, a, before):
+        pass
+
+    def faulty(self, kind, f, a):
+        if kind not in P.COLUMN_CALLS:
+            return self.plain_call(kind, f, a)
+        before = {k: self.m.raw(f, a[k]) for k in ("out", "s_out") if k in a}
+        host = self.plain_call(kind, f, a)  # (a refused call raises here)
+        self.spoil(kind, f, a, before)
+        return host
+
+    def replace(self, f, rng, at, count, stored):
+        """`count` scalars from element `at` of the range on become the stored value; -> did a byte change"""
+        data = frvec_model.to_bytes([stored] * count)
+        changed = self.m.raw(f, (rng[0] + 2 * at, count)) != data
+        self.m.put(f, rng[0] + 2 * at, data)
+        return changed
+
+
+class RunOnATileBoundaryCopiesThePreviousEntry(ColumnFault):
+    """an expand whose run that starts on a tile boundary copies the previous entry: the last of the tile before"""
+    fields_to_run = "grumpkin"
+
+    def spoil(self, kind, f, a, before):
+        if kind != "expand":
+            return
+        tile, t, off = self.m.hooks["frcol_test_tile"] or 1024, self.m.stored(f, a["t"]), 0
+        for j, c in enumerate(self.m.words[f][a["counts"]]):
+            if j and j % tile == 0 and c + a["bias"] and self.replace(f, a["out"], off, c + a["bias"], t[j - 1]):
+                self.fired()
+            off += c + a["bias"]
+
+
+class FillersFromThePreviousCallsZ(ColumnFault):
+    """a pair whose fillers come from the z of the previous, larger call: the entries that call never looked up, as far as they lie inside
+    this table"""
+    fields_to_run = "vesta"
+
+    def fresh(self):
+        self.z, self.n = [], 0
+
+    def spoil(self, kind, f, a, before):
+        if kind != "pair":
+            return
+        t, counts = self.m.stored(f, a["t"]), self.m.words[f][a["counts"]]
+        if self.n > len(t):
+            k = used = 0
+            for c in counts:
+                for d in range(c):
+                    rank = k - used - 1
+                    if d and rank < len(self.z) and self.z[rank] < len(t) and self.replace(f, a["s_out"], k, 1, t[self.z[rank]]):
+                        self.fired()
+                    k += 1
+                used += c > 0
+        self.z, self.n = [j for j, c in enumerate(counts) if c == 0], len(t)
+
+
+class MissingElementLeftAsItWas(ColumnFault):
+    """a gather that leaves a MISSING element as it was and does not zero it"""
+    fields_to_run = "vesta"
+
+    def spoil(self, kind, f, a, before):
+        if kind != "gather":
+            return
+        for i, at in enumerate(self.m.words[f][a["idx"]]):
+            if at == P.MISSING and any(before["out"][32 * i:32 * i + 32]):
+                self.m.put(f, a["out"][0] + 2 * i, before["out"][32 * i:32 * i + 32])
+                self.fired()
+
+
+class OneScalarPastTheOutput(ColumnFault):
+    """a column call that writes one scalar past its output: the output's last once more"""
+    fields_to_run = "pallas"
+
+    def spoil(self, kind, f, a, before):
+        out = a["s_out" if kind == "pair" else "out"]
+        if 16 * (out[0] + 2 * out[1]) + 32 <= len(self.m.arena[f]) and self.replace(f, out, out[1], 1, self.m.stored(f, (out[0] + 2 * out[1] - 2, 1))[0]):
+            self.fired()
+
+
 @pytest.mark.parametrize("fault", [ScanTileBoundary, ScratchKeepsTheTail, NttReusesTheTable, TableAnswersForAnother, ErrorWordNotCleared, SecondHalfFromFurtherOn,
                                    MontComputedAsCanonical, OneByteTooMany, HandleAnswersForTheOneBefore, SpongeReadsThePadding, SpongeTakesTheOtherFormsConstants, SecondLevelFromTheLeaves,
-                                   HostOutputFromTheStaleSpot, FirstTidiedWidthGoesWrong], ids=lambda c: c.__name__)
+                                   HostOutputFromTheStaleSpot, FirstTidiedWidthGoesWrong, InternalSumTakenLate, AnsweredWithTheOtherKindsCode, RunOnATileBoundaryCopiesThePreviousEntry,
+                                   FillersFromThePreviousCallsZ, MissingElementLeftAsItWas, OneScalarPastTheOutput], ids=lambda c: c.__name__)
 def test_a_planted_fault_is_caught_at_its_step_and_replays(fault):
     fields = fault.fields_to_run.split(",")
     seed, cases = COMMITTED[fault.fields_to_run]

@@ -83,6 +83,74 @@ def test_sorted_by_table_is_plookups_vector(field):
         col.sorted_by_table(ctx, _dev(stored(t)), _dev(stored(f[:-1] + [(t[0] + 1) % r if (t[0] + 1) % r not in t else 0])))
 
 
+# ---- an output that shares bytes with an input or with the other output: refused by name, before the C call, with nothing written --------------------
+# (call, the operand that is the output, the operand it cuts, how: the output starts `shift` scalars behind the other's start)
+CUTS = [(call, out, other, shift) for call, out, other in (("expand", "out", "t"), ("pair", "out[0]", "t"), ("pair", "out[1]", "t"), ("pair", "out[0]", "out[1]"),
+                                                            ("gather", "out", "a")) for shift in (0, 1, -3)]
+
+
+@pytest.fixture(scope="module")
+def plain_context(built):
+    import msm_webgpu_amd as m
+    from msm_webgpu_amd import columns
+
+    c = m.MsmContext(0, "bn254")
+    yield c, columns
+    c.close()
+
+
+@pytest.mark.parametrize("call,out,other,shift", CUTS, ids=lambda v: str(v).replace(" ", ""))
+def test_an_output_that_cuts_an_operand_is_refused_by_name(plain_context, call, out, other, shift):
+    """n_t = 4.  The library refuses an overlap before it forms the sum of the counts: the message names the two operands and speaks neither
+    of a sum nor of an index, every byte stays as it was, and a correct call right afterwards is right."""
+    ctx, col = plain_context
+    rnd = rng(124)
+    values = [rnd.randrange(1 << 250) for _ in range(24)]
+    buf = _dev(values)
+    before = _ints(buf)
+    t, apart_a, apart_s = buf[8:12], buf[16:20], buf[20:24]  # the input, and outputs that lie apart from it and from one another
+    cut = buf[8 + shift:12 + shift]  # shares bytes with t: the same start, one scalar on, three scalars before
+    counts = torch.tensor([2, 0, 1, 1], dtype=torch.int32, device="cuda")
+    idx = torch.tensor([3, -1, 0, 3], dtype=torch.int32, device="cuda")
+    with pytest.raises(ValueError) as e:
+        if call == "expand":
+            col.expand(ctx, t, counts, 4, out=cut)
+        elif call == "gather":
+            col.gather(ctx, t, idx, out=cut)
+        elif other == "t":
+            col.permuted_pair(ctx, t, counts, out=(cut, apart_s) if out == "out[0]" else (apart_a, cut))
+        else:  # the two outputs cut one another, both apart from t
+            col.permuted_pair(ctx, t, counts, out=(apart_a, buf[16 + shift:20 + shift]))
+    said = str(e.value)
+    assert "%s overlaps %s" % (out, other) in said and "add up to" not in said and "index" not in said, said
+    assert _ints(buf) == before and counts.tolist() == [2, 0, 1, 1] and idx.tolist() == [3, -1, 0, 3]
+    tv = values[8:12]
+    if call == "expand":
+        assert _ints(col.expand(ctx, t, counts, 4, out=apart_a)) == M.expand(tv, [2, 0, 1, 1])
+    elif call == "gather":
+        assert _ints(col.gather(ctx, t, idx, out=apart_a)) == M.gather(tv, [3, M.MISSING, 0, 3])[0]
+    else:
+        got = col.permuted_pair(ctx, t, counts, out=(apart_a, apart_s))
+        assert (_ints(got[0]), _ints(got[1])) == M.pair(tv, [2, 0, 1, 1])[:2]
+    assert _ints(buf[:16]) == before[:16]  # the correct call wrote its outputs and nothing else
+
+
+def test_a_wrong_sum_and_a_bad_index_keep_their_messages(plain_context):
+    """operands that lie apart: the sum the library reported is named, and so is the index"""
+    ctx, col = plain_context
+    t = _dev([5, 6, 7, 8])
+    counts = torch.tensor([2, 0, 1, 2], dtype=torch.int32, device="cuda")
+    with pytest.raises(ValueError, match="add up to 5, not to the 4 outputs"):
+        col.expand(ctx, t, counts, 4)
+    with pytest.raises(ValueError, match="add up to 5, not to the 4 rows"):
+        col.permuted_pair(ctx, t, counts)
+    wrapped = torch.tensor([-0x80000000] * 4, dtype=torch.int32, device="cuda")  # four counts of 2^31: zero in 32 bits
+    with pytest.raises(ValueError, match="add up to %d" % (1 << 33)):
+        col.expand(ctx, t, wrapped, 4)
+    with pytest.raises(ValueError, match="neither below the 4 scalars"):
+        col.gather(ctx, t, torch.tensor([0, 4], dtype=torch.int32, device="cuda"))
+
+
 def _one(ctx, r):
     return ((1 << 256) % r if ctx.scalar_mont256 else 1).to_bytes(32, "little")
 

@@ -1,9 +1,10 @@
-"""Randomised differential test of the eight scalar-field libraries as CHAINED programs on shared state (tests/fr_program.py): random steps over
+"""Randomised differential test of the nine scalar-field libraries as CHAINED programs on shared state (tests/fr_program.py): random steps over
 one or two fields in one arena per field -- every entry point of the scalars_* methods of scalars.py, in place or into another range, at starts of 0 and
 16 mod 32, after a larger call, after another field's call, after a refused call, under both scalar forms, with several test hooks set at once,
-with matrices, lookup tables and Poseidon handles kept alive across all of it (a handle's constants go to the device inside its first call, on
-whichever stream and under whichever form that call has; a Poseidon call is a device-form one on ranges of the arena or a host-form one on
-their bytes).  After EVERY step each range the step wrote and each host value it returned is compared byte for byte with the model; at the end
+with matrices, lookup tables, Poseidon and Poseidon2 handles kept alive across all of it (a handle's constants go to the device inside its first
+call, on whichever stream and under whichever form that call has; a hashing call is a device-form one on ranges of the arena or a host-form
+one on their bytes), and with the counts and indices that a lookup call returned kept on the device for the column calls of
+msm_webgpu_amd.columns behind it.  After EVERY step each range the step wrote and each host value it returned is compared byte for byte with the model; at the end
 of a program the whole arena is.
 Usage: python tools/fuzz_fr.py [cases] [seed] [field[,field]] [--case K]   (fields: bn254 pallas vesta bls12_381 grumpkin; --case K replays one case)
 FUZZ_FR_KINDS=a,b,... restricts the step kinds that are drawn (tests/fr_program.py: KINDS)."""
@@ -102,8 +103,8 @@ class DeviceBackend:
         import torch
 
         import msm_webgpu_amd as m
-        from msm_webgpu_amd import api
-        self.torch, self.api, self.fields = torch, api, list(fields)
+        from msm_webgpu_amd import api, columns
+        self.torch, self.api, self.columns, self.fields = torch, api, columns, list(fields)
         for name in fields:
             r = P.FIELD_R[name]
             assert api.SCALAR_FIELDS[name] == r and (name == "grumpkin" or all(api.root_of_unity(name, k) == P.root_of_unity(r, k) for k in range(13)))
@@ -115,6 +116,7 @@ class DeviceBackend:
         self.side = torch.cuda.Stream(0)
         self.cur = self.default
         self.mats, self.tabs, self.hashes = [{} for _ in fields], [{} for _ in fields], [{} for _ in fields]
+        self.words = [{} for _ in fields]  # slot -> a CUDA tensor of 32-bit words: the one a lookup call returned, or an uploaded one
 
     def t(self, f, rng):
         return None if rng is None else self.arena[f][16 * rng[0]:16 * rng[0] + 32 * rng[1]]
@@ -135,7 +137,9 @@ class DeviceBackend:
     def reset(self):
         """between programs: no hook, no handle, the canonical form, the default stream"""
         for name in P.HOOKS:
-            getattr(self.api, name)(0)
+            self._hook(name)(0)
+        for d in self.words:
+            d.clear()
         for d in self.mats + self.tabs + self.hashes:
             for h in d.values():
                 h.close()
@@ -144,12 +148,17 @@ class DeviceBackend:
             c.set_scalar_format(mont256=False)
         self._switch(self.default)
 
+    def _hook(self, name):
+        """a test hook by its name: the scalar-field libraries' are the API's, the columns' its own module's"""
+        return getattr(self.api, name, None) or getattr(self.columns, name)
+
     def close(self):
         self.reset()
         self.torch.cuda.synchronize()
         for c in self.ctx:
             c.close()
         self.api.frhash_release()
+        self.columns.frcol_release()
 
     def host_bytes(self, f, rng):
         """the bytes of a range, for a host-form call"""
@@ -239,8 +248,11 @@ class DeviceBackend:
         return self.tabs[f][slot].distinct
 
     @_translated
-    def op_mult(self, f, slot, v, batch, n, out, indices, counts):
+    def op_mult(self, f, slot, v, batch, n, out, indices, counts, cslot=None, islot=None):
         res = self.ctx[f].scalars_multiplicities(self.tabs[f][slot], self.t(f, v), batch, n, out=self.t(f, out), indices=indices, counts=counts, strict=False)
+        for wslot, at in ((islot, 1), (cslot, 2 if indices else 1)):  # the very tensors the call returned, not copies
+            if wslot is not None:
+                self.words[f][wslot] = res[at]
         words = [[int(x) & 0xFFFFFFFF for x in w.cpu().reshape(-1).tolist()] for w in res[1:-1]]  # (idx: -1 where the value is missing)
         return tuple(words) + (tuple(res[-1]),)
 
@@ -248,6 +260,27 @@ class DeviceBackend:
     def op_poseidon(self, f, slot, t, full_rounds, partial_rounds, seed, capacity, capacity_at, out_at):
         rc, mds = P.poseidon_constants(seed, t, full_rounds, partial_rounds, P.FIELD_R[self.fields[f]])
         self.hashes[f][slot] = self.ctx[f].poseidon(t, full_rounds, partial_rounds, round_constants=rc, mds=mds, capacity=capacity, capacity_at=capacity_at, out_at=out_at)
+
+    @_translated
+    def op_poseidon2(self, f, slot, t, full_rounds, partial_rounds, seed, capacity, capacity_at, out_at):
+        rc, mu = P.poseidon2_constants(seed, t, full_rounds, partial_rounds, P.FIELD_R[self.fields[f]])
+        self.hashes[f][slot] = self.ctx[f].poseidon2(t, full_rounds, partial_rounds, round_constants=rc, diagonal=mu, capacity=capacity, capacity_at=capacity_at, out_at=out_at)
+
+    @_translated
+    def op_words(self, f, slot, values):
+        self.words[f][slot] = self.torch.tensor([w - (1 << 32) if w >> 31 else w for w in values], dtype=self.torch.int32, device="cuda:0")
+
+    @_translated
+    def op_expand(self, f, t, counts, bias, out):
+        self.columns.expand(self.ctx[f], self.t(f, t), self.words[f][counts], out[1], bias=bias, out=self.t(f, out))
+
+    @_translated
+    def op_pair(self, f, t, counts, out, s_out):
+        self.columns.permuted_pair(self.ctx[f], self.t(f, t), self.words[f][counts], out=(self.t(f, out), self.t(f, s_out)))
+
+    @_translated
+    def op_gather(self, f, a, idx, out):
+        self.columns.gather(self.ctx[f], self.t(f, a), self.words[f][idx], out=self.t(f, out))
 
     @_translated
     def op_permute(self, f, slot, a, out, host):
@@ -273,7 +306,7 @@ class DeviceBackend:
 
     @_translated
     def op_hook(self, f, name, value):
-        getattr(self.api, name)(value)
+        self._hook(name)(value)
 
     @_translated
     def op_close(self, f, what, slot):
