@@ -33,13 +33,13 @@ namespace msm_frmle {
 using namespace fr_host;
 
 constexpr size_t MAX_ELEMENTS = (size_t)1 << 26;
-constexpr uint32_t KNOWN_FLAGS = MSM_FRMLE_MONT256;
+constexpr uint32_t KNOWN_FLAGS = MSM_FRMLE_MONT256 | MSM_FRMLE_LOW_FIRST;
 
 struct DeviceState {
   hipStream_t stream = nullptr;
   Buffer result;    // word 0: the error word; from word FRMLE_RESULT_HEAD: the values of the call
   Buffer h_result;  // pinned: what the one copy of a call fills
-  Buffer scratch;   // the tile values, level by level
+  Buffer scratch;   // the tile values, level by level; behind them the scratch rows of a low-first in-place bind
   Buffer consts;    // the tables of eq, the terms of a round
   Buffer staging;   // the host forms' table
   std::vector<uint32_t> h_consts;  // what is on its way into consts (it outlives the call that uploads it)
@@ -135,7 +135,8 @@ inline int shape_checks(const FrmleOps* ops, int device, size_t n, size_t min_n,
 struct Levels {
   std::vector<size_t> len, at;
   size_t words = 0;
-  Levels(size_t n, size_t rows, uint32_t tile) : len(plan_levels(n, tile)), at(len.size(), 0) {
+  Levels(size_t n, size_t rows, uint32_t tile) : Levels(plan_levels(n, tile), rows) {}
+  Levels(std::vector<size_t> lens, size_t rows) : len(std::move(lens)), at(len.size(), 0) {
     for (size_t l = 1; l < len.size(); l++) {
       at[l] = words;
       words += rows * len[l] * 8;
@@ -168,9 +169,25 @@ inline int fold_impl(int curve, int device, void* stream, void* out, const void*
     da = dout;
   }
   const size_t half = n / 2;
-  ops->fold((unsigned)((batch * half + FRMLE_THREADS - 1) / FRMLE_THREADS), call.st, dout, da, half, batch, stride, &g, call.err);
+  int launches = 1;
+  if (!(flags & MSM_FRMLE_LOW_FIRST)) {
+    ops->fold((unsigned)((batch * half + FRMLE_THREADS - 1) / FRMLE_THREADS), call.st, dout, da, half, batch, stride, &g, call.err);
+  } else if (dout != da) {  // apart: no slot is both read and written
+    const FrmleFoldArgs low = plan_fold_low(f, c, LowLaunch{0, (uint32_t)half, false}, stride);
+    ops->fold((unsigned)((batch * half + FRMLE_THREADS - 1) / FRMLE_THREADS), call.st, dout, da, half, batch, stride, &low, call.err);
+  } else {
+    const LowSchedule s = plan_low_in_place(n);
+    if ((rc = grow(call.ds->scratch, batch * s.copy * 8))) return rc;
+    launches = (int)s.launches.size();
+    for (const LowLaunch& l : s.launches) {
+      const FrmleFoldArgs low = plan_fold_low(f, c, l, l.to_scratch ? s.copy : stride);
+      ops->fold((unsigned)((batch * l.count + FRMLE_THREADS - 1) / FRMLE_THREADS), call.st, l.to_scratch ? call.ds->scratch.p : dout, da, l.count, batch, stride, &low,
+                call.err);
+    }
+    if (s.copy && !hip_ok(hipMemcpy2DAsync(dout, stride * 32, call.ds->scratch.p, s.copy * 32, s.copy * 32, batch, hipMemcpyDeviceToDevice, call.st))) return MSM_HIP_ERR_HIP;
+  }
   if (host && (rc = stage_out(call, out, half, batch, stride))) return rc;
-  return leave(call, nullptr, 0, 1, 1);
+  return leave(call, nullptr, 0, launches, 1);
 }
 
 inline int eval_impl(int curve, int device, void* stream, const void* a, size_t n, size_t batch, size_t stride, const uint8_t* point, uint32_t flags, uint8_t* values_host,
@@ -190,6 +207,8 @@ inline int eval_impl(int curve, int device, void* stream, const void* a, size_t 
   const uint32_t tile = tile_in_use();
   const Levels lv(n, batch, tile);
   const size_t levels = lv.count();
+  const std::vector<uint8_t> reversed = flags & MSM_FRMLE_LOW_FIRST ? reversed_point(point, k) : std::vector<uint8_t>();
+  if (flags & MSM_FRMLE_LOW_FIRST) point = reversed.data();                                       // (the kernel does not know the order)
   const std::vector<FrmleEvalArgs> g = plan_eval(f, tile, k, point);  // (as many levels: ceil(k / log2(tile)), 1 for k = 0)
   if (g.size() != levels) return MSM_HIP_ERR_INVALID_ARG;
   Call call;
@@ -223,6 +242,8 @@ inline int eq_impl(int curve, int device, void* stream, void* out, size_t n, con
   std::lock_guard<std::mutex> hold(lock());
   Call call;
   if ((rc = enter(device, stream, host, 0, &call))) return rc;
+  const std::vector<uint8_t> reversed = flags & MSM_FRMLE_LOW_FIRST ? reversed_point(point, log2_of(n)) : std::vector<uint8_t>();
+  if (flags & MSM_FRMLE_LOW_FIRST) point = reversed.data();
   const FrmleEqArgs p = plan_eq(f, n, point, c, (flags & MSM_FRMLE_MONT256) != 0, call.ds->h_consts);
   if ((rc = upload_consts(call))) return rc;
   uint32_t* dout = static_cast<uint32_t*>(out);
@@ -257,19 +278,34 @@ inline int round_impl(int curve, int device, void* stream, void* a, size_t n, si
   const size_t half = fold_by ? n / 4 : n / 2;  // the pairs of the tables the round is of
   Call call;
   if ((rc = enter(device, stream, host, FRMLE_POINTS, &call))) return rc;
-  const FrmleRoundArgs g = plan_round(f, tile, plain, num_terms, batch, fold_by, (flags & MSM_FRMLE_MONT256) != 0, call.ds->h_consts);
-  const Levels lv(half, g.points, tile);
+  FrmleRoundArgs g = plan_round(f, tile, plain, num_terms, batch, fold_by, (flags & MSM_FRMLE_MONT256) != 0, call.ds->h_consts);
+  const bool low = (flags & MSM_FRMLE_LOW_FIRST) != 0;
+  // low first with fold_by: the schedule of csrc/frmle_plan.h -- two launches over their own tiles and a copy; otherwise one launch over all pairs
+  LowSchedule s;
+  if (low && fold_by) s = plan_low_fused(n);
+  else s.launches.push_back(LowLaunch{0, (uint32_t)half, false});
+  const uint32_t launch_tile = low && fold_by ? low_fused_tile(tile) : tile;  // (the sums above always run over `tile`)
+  const Levels lv = low && fold_by ? Levels(plan_levels_low_fused(s, half, launch_tile, tile), g.points) : Levels(half, g.points, tile);
   const size_t levels = lv.count();
+  plan_round_launches(g, low, s, launch_tile, lv.words - (levels > 1 ? lv.at[1] : 0), call.ds->h_consts);  // (scratch rows: only where levels > 1)
   if ((rc = upload_consts(call))) return rc;
-  if ((rc = grow(call.ds->scratch, lv.words))) return rc;
+  if ((rc = grow(call.ds->scratch, lv.words + batch * s.copy * 8))) return rc;
   uint32_t* const scratch = call.ds->scratch.p;
+  uint32_t* const rows = scratch + lv.words;  // the scratch rows of the schedule, s.copy elements apart
   uint32_t* da = static_cast<uint32_t*>(a);
   if (host && (rc = stage_in(call, a, span(n, batch, stride), &da))) return rc;
-  ops->round(lv.tiles(0, tile), call.st, da, (uint32_t)half, (uint32_t)stride, call.ds->consts.p, levels > 1 ? scratch + lv.at[1] : call.values, &g, call.err);
+  uint32_t* const partial = levels > 1 ? scratch + lv.at[1] : call.values;
+  uint32_t tile0 = 0;
+  for (size_t k = 0; k < s.launches.size(); k++) {
+    const uint32_t* const consts = call.ds->consts.p + low_block_words(num_terms) * k;
+    ops->round(low_tiles(s.launches[k], launch_tile), call.st, da, (uint32_t)half, (uint32_t)stride, consts, partial + 8 * (size_t)tile0, &g, call.err);
+    tile0 += low_tiles(s.launches[k], launch_tile);
+  }
+  if (s.copy && !hip_ok(hipMemcpy2DAsync(da, stride * 32, rows, s.copy * 32, s.copy * 32, batch, hipMemcpyDeviceToDevice, call.st))) return MSM_HIP_ERR_HIP;
   for (size_t l = 1; l < levels; l++)
     ops->sum((unsigned)(g.points * lv.tiles(l, tile)), call.st, scratch + lv.at[l], l + 1 < levels ? scratch + lv.at[l + 1] : call.values, lv.len[l], lv.tiles(l, tile), tile);
   if (host && fold_by && (rc = stage_out(call, a, n / 2, batch, stride))) return rc;
-  return leave(call, values_host, g.points, (int)levels, (int)levels);
+  return leave(call, values_host, g.points, (int)(levels - 1 + s.launches.size()), (int)levels);
 }
 
 }  // namespace msm_frmle

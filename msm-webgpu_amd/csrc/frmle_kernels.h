@@ -33,6 +33,15 @@
 //                 fq_tidy takes (value x (R mod r) <= FQ_HEADROOM r^2).  Both bounds are static_asserts below; the host program runs the
 //                 patterns that reach them (lo = 0, hi = r - 1 at degree 4) under FQ_CHECK.
 //
+// LOW FIRST (MSM_FRMLE_LOW_FIRST: the first variable is bit 0 of the index, arkworks' order).  Binding pairs 2 i with 2 i + 1, and the SAME lane
+// functions and kernels do it: the mode travels in FrmleFoldArgs / FrmleRoundArgs and only selects addresses -- a pair's two elements are 1 apart
+// instead of `half`, a fused pair's four elements are 4 i .. 4 i + 3 --, uniformly for the launch; the arithmetic and its bounds are those above.
+// A lane then reads 64 contiguous bytes per row (128 in the fused round) as 16-byte loads; a wave's loads together cover whole lines.  eval and eq
+// need no mode: the host reverses the point.  What the mode does change is WHERE a result may be stored: output i of an in-place bind lands on
+// slot i, an input of lane i / 2 (fused: the outputs 2 i, 2 i + 1 of lane i are inputs of lane i / 2), which may run in another workgroup at any
+// time.  No kernel waits for one, so the host never launches such a pair of lanes together (csrc/frmle_plan.h: the schedule); to the lanes here
+// that is a range of outputs (first, count) and an output row stride.
+//
 // frp_load / frp_store / frp_add of csrc/frpoly_kernels.h are restated here (frm_load ..): including that file would instantiate libmsm_frpoly.so's
 // four kernels in every unit of this library.
 //
@@ -60,7 +69,10 @@
 
 // what the host plans (csrc/frmle_plan.h) -- plain data, the same for every field's unit; every constant is 8 words, canonical
 struct FrmleFoldArgs {
-  uint32_t c[8];  // c R
+  uint32_t c[8];        // c R
+  uint32_t low;         // MSM_FRMLE_LOW_FIRST: output i binds the elements 2 i and 2 i + 1; what follows is read under it only
+  uint32_t first;       // the launch computes the outputs first .. first + half - 1 of every row (`half`: the kernel's count of outputs per row)
+  uint32_t out_stride;  // the rows of out are this many elements apart (the scratch rows of the in-place schedule are not `stride` apart)
 };
 struct FrmleEvalArgs {
   uint32_t tile;  // elements per tile in use (the test hook shrinks it), a power of two <= FRMLE_TILE
@@ -78,7 +90,18 @@ struct FrmleRoundArgs {
   uint32_t fold;       // bind the top variable of every row first
   uint32_t batch;      // rows (<= FRMLE_MAX_ROWS): all of them are folded
   uint32_t c[8];       // fold_by R
+  uint32_t low;        // MSM_FRMLE_LOW_FIRST: pair i is the elements 2 i and 2 i + 1, and FRMLE_LOW_WORDS words behind the terms say the rest
 };
+// Low first, what a launch of k_frmle_round needs beyond FrmleRoundArgs sits behind its terms in device memory, at word FRMLE_TERM_WORDS num_terms:
+// the kernel has no scalar register left for more arguments (they would be live from its first instruction to its last), while a word behind
+// `terms` is loaded where it is used.  The lane functions read them low first only; the kernel reads FRMLE_LOW_TILES in both orders.  Offsets:
+#define FRMLE_LOW_WORDS 8
+#define FRMLE_LOW_FIRST_PAIR 0  // the launch's pairs are first .. end - 1; tile k of the launch begins at first + k tile
+#define FRMLE_LOW_END_PAIR 1
+#define FRMLE_LOW_TILES 2       // the tiles of all launches of the round: partial[t * tiles + block], `partial` moved on by the launches before
+#define FRMLE_LOW_TO_SCRATCH 3  // with fold: the folded rows go to the scratch rows (1) or stay in a (0) ...
+#define FRMLE_LOW_OUT_AT 4      // ... which begin this many words behind `partial` (the same allocation) ...
+#define FRMLE_LOW_OUT_STRIDE 5  // ... and are this many elements apart
 
 #if defined(__HIPCC__)
 // what the host code (csrc/frmle_host.h) knows of a field's unit
@@ -168,12 +191,21 @@ FQ_HD fq frm_acc(const fq& a, const fq& b) { return fq_norm(fq_add(a, b)); }
 FQ_HD fq frm_exact(const fq& x) { return fq_canonical(fq_tidy(x)); }  // normal, <= FQ_HEADROOM r  ->  canonical
 
 // ---- 1. fold ------------------------------------------------------------------------------------------------------------------------------------
-// pair i of row `row`: out[row][i] = bind(a[row][i], a[row][i + half])
+// pair i of row `row`: out[row][i] = bind(a[row][i], a[row][i + half]); low first, output o = g.first + i: out[row][o] = bind(a[row][2 o],
+// a[row][2 o + 1]), the rows of out g.out_stride apart.  One uniform branch: the top-first side is the code it was before there was a choice
+// (selects on the 64-bit offsets cost the top-first fold 3 % at 2^20: DESIGN.md section 4.20.1).
 FQ_HD bool frm_fold_pair(const FrmleFoldArgs& g, size_t row, size_t i, size_t half, size_t stride, const uint32_t* a, uint32_t* out) {
   fq lo, hi;
-  bool ok = frm_load(lo, a, row * stride + i);
-  ok &= frm_load(hi, a, row * stride + i + half);
-  frm_store(out, row * stride + i, frm_bind(lo, hi, frm_const(g.c)));
+  if (!g.low) {
+    bool ok = frm_load(lo, a, row * stride + i);
+    ok &= frm_load(hi, a, row * stride + i + half);
+    frm_store(out, row * stride + i, frm_bind(lo, hi, frm_const(g.c)));
+    return ok;
+  }
+  const size_t o = g.first + i, from = row * stride + 2 * o;
+  bool ok = frm_load(lo, a, from);
+  ok &= frm_load(hi, a, from + 1);
+  frm_store(out, row * g.out_stride + o, frm_bind(lo, hi, frm_const(g.c)));
   return ok;
 }
 
@@ -220,27 +252,58 @@ FQ_HD void frm_eq_lane(const FrmleEqArgs& p, size_t lane, size_t n, const uint32
 }
 
 // ---- 4. round -----------------------------------------------------------------------------------------------------------------------------------
-// the fused fold: pair i (< half) of the FOLDED tables, for every row: the elements i, i + half, i + 2 half, i + 3 half of the row as it is, the
-// folded row's i and i + half stored
-FQ_HD bool frm_round_fold_pair(const FrmleRoundArgs& g, uint32_t* a, uint32_t stride, uint32_t i, uint32_t half) {
+// Where a launch's lanes find their pairs, the same for all of them.  Top first, pair i of a table is the elements i and i + half, and the fused
+// fold takes i, i + half, i + 2 half, i + 3 half and stores the folded i and i + half in place.  Low first, pair i is 2 i and 2 i + 1, the fused
+// fold takes 4 i .. 4 i + 3 and stores the folded 2 i and 2 i + 1 in `rows` -- a, or the scratch rows behind `partial` --, and the launch's pairs
+// are those the words behind the terms name (FRMLE_LOW_*).  The two orders differ in these few offsets and in nothing else, and k_frmle_round
+// has very few scalar registers to spare: the offsets are made once per lane, and the order is not looked at again.
+struct FrmRoundWhere {
+  uint32_t shift;  // pair i begins at element i << shift of its row (the fused fold's four at i << 2 shift)
+  uint32_t apart;  // a pair's two elements are this far apart, and so are the fused fold's two results.  The fused fold binds elements
+                   // apart << (1 - shift) apart -- 2 half, or 1 -- and its second bind begins apart << shift behind its first -- half, or 2
+  uint32_t first;  // the launch's pairs are first .. end - 1
+  uint32_t end;
+  uint32_t rows_at;  // the folded rows: 0: a itself; otherwise they begin this many words behind `partial` (never 0: the partials lie between)
+  uint32_t rows_stride;  // ... and are this many elements apart
+};
+FQ_HD FrmRoundWhere frm_round_where(const FrmleRoundArgs& g, uint32_t half, uint32_t stride, const uint32_t* terms) {
+  FrmRoundWhere w;
+  w.rows_at = 0, w.rows_stride = stride;
+  if (g.low) {  // (uniform)
+    const uint32_t* const lw = terms + FRMLE_TERM_WORDS * g.num_terms;
+    w.shift = 1, w.apart = 1, w.first = lw[FRMLE_LOW_FIRST_PAIR], w.end = lw[FRMLE_LOW_END_PAIR];
+    if (g.fold && lw[FRMLE_LOW_TO_SCRATCH]) w.rows_at = lw[FRMLE_LOW_OUT_AT], w.rows_stride = lw[FRMLE_LOW_OUT_STRIDE];
+  } else {
+    w.shift = 0, w.apart = half, w.first = 0, w.end = half;
+  }
+  return w;
+}
+FQ_HD uint32_t* frm_round_rows(const FrmRoundWhere& w, uint32_t* a, uint32_t* partial) { return w.rows_at ? partial + w.rows_at : a; }
+// the fused fold: pair i of the FOLDED tables, for every row
+FQ_HD bool frm_round_fold_pair(const FrmleRoundArgs& g, const FrmRoundWhere& w, uint32_t* a, uint32_t stride, uint32_t i, uint32_t* rows) {
   bool ok = true;
   const fq c = frm_in_vgprs(frm_const(g.c));
+  const uint32_t bound = w.apart << (1 - w.shift), second = w.apart << w.shift;
   for (uint32_t row = 0; row < g.batch; row++) {
-    const uint32_t at = row * stride + i;  // (batch stride <= 2^26: element numbers fit 32 bits)
+    const uint32_t at = row * stride + (i << (2 * w.shift)), to = row * w.rows_stride + (i << w.shift);  // (batch stride <= 2^26: element numbers fit 32 bits)
     fq x0, x1, x2, x3;
     ok &= frm_load(x0, a, at);
-    ok &= frm_load(x1, a, at + half);
-    ok &= frm_load(x2, a, at + 2 * half);
-    ok &= frm_load(x3, a, at + 3 * half);
-    frm_store(a, at, frm_bind(x0, x2, c));
-    frm_store(a, at + half, frm_bind(x1, x3, c));
+    ok &= frm_load(x1, a, at + second);
+    ok &= frm_load(x2, a, at + bound);
+    ok &= frm_load(x3, a, at + second + bound);
+    frm_store(rows, to, frm_bind(x0, x2, c));
+    frm_store(rows, to + w.apart, frm_bind(x1, x3, c));
   }
   return ok;
 }
+FQ_HD bool frm_round_fold_pair(const FrmleRoundArgs& g, uint32_t* a, uint32_t stride, uint32_t i, uint32_t half) {
+  return frm_round_fold_pair(g, frm_round_where(g, half, stride, nullptr), a, stride, i, a);  // (top first: no word behind the terms is read)
+}
 // pair i: every term's product at t = 0 .. points - 1, times the term's constant, added to acc[t] (normal; the lane's bound is at the top)
 template <int POINTS>
-FQ_HD bool frm_round_pair(const FrmleRoundArgs& g, const uint32_t* a, uint32_t stride, uint32_t i, uint32_t half, const uint32_t* terms, fq acc[POINTS]) {
+FQ_HD bool frm_round_pair(const FrmleRoundArgs& g, const FrmRoundWhere& w, const uint32_t* rows, uint32_t i, const uint32_t* terms, fq acc[POINTS]) {
   bool ok = true;
+  const uint32_t from = i << w.shift;
 #pragma unroll 1
   for (uint32_t term = 0; term < g.num_terms; term++) {
     const uint32_t* tw = terms + (size_t)FRMLE_TERM_WORDS * term;
@@ -250,10 +313,10 @@ FQ_HD bool frm_round_pair(const FrmleRoundArgs& g, const uint32_t* a, uint32_t s
 #pragma unroll
     for (int f = 0; f < POINTS - 1; f++) {
       if ((uint32_t)f < degree) {
-        const uint32_t at = tw[9 + f] * stride + i;
+        const uint32_t at = tw[9 + f] * w.rows_stride + from;
         fq hi;
-        ok &= frm_load(val[f], a, at);
-        ok &= frm_load(hi, a, at + half);
+        ok &= frm_load(val[f], rows, at);
+        ok &= frm_load(hi, rows, at + w.apart);
         diff[f] = frm_add(hi, fq_neg_canonical(val[f]));
       }
     }
@@ -274,25 +337,28 @@ FQ_HD bool frm_round_pair(const FrmleRoundArgs& g, const uint32_t* a, uint32_t s
   return ok;
 }
 // the lane's pairs of tile k: in-tile offsets lane, 256 + lane, ..; acc (normal, < 64r) receives their sums.  With fold_by the lane folds and
-// stores all its pairs first and reads its own stores back afterwards: what only the fold needs is dead by then.
+// stores all its pairs first and reads its own stores back afterwards: what only the fold needs is dead by then.  (`partial` is read low first
+// only: the scratch rows lie behind it.)
 template <int POINTS>
-FQ_HD bool frm_round_lane(const FrmleRoundArgs& g, uint32_t* a, uint32_t half, uint32_t stride, uint32_t k, uint32_t lane, const uint32_t* terms, fq acc[POINTS]) {
+FQ_HD bool frm_round_lane(const FrmleRoundArgs& g, uint32_t* a, uint32_t half, uint32_t stride, uint32_t k, uint32_t lane, const uint32_t* terms, fq acc[POINTS],
+                          uint32_t* partial = nullptr) {
   bool ok = true;
 #pragma unroll
   for (int t = 0; t < POINTS; t++) acc[t] = fq_zero();
+  const FrmRoundWhere w = frm_round_where(g, half, stride, terms);
   if (g.fold) {
 #pragma unroll 1
     for (uint32_t j = 0; j < FRMLE_E; j++) {
-      const uint32_t off = j * FRMLE_THREADS + lane, i = k * g.tile + off;
-      if (off >= g.tile || i >= half) break;
-      ok &= frm_round_fold_pair(g, a, stride, i, half);
+      const uint32_t off = j * FRMLE_THREADS + lane, i = w.first + k * g.tile + off;
+      if (off >= g.tile || i >= w.end) break;
+      ok &= frm_round_fold_pair(g, w, a, stride, i, frm_round_rows(w, a, partial));
     }
   }
 #pragma unroll 1
   for (uint32_t j = 0; j < FRMLE_E; j++) {
-    const uint32_t off = j * FRMLE_THREADS + lane, i = k * g.tile + off;
-    if (off >= g.tile || i >= half) break;
-    ok &= frm_round_pair<POINTS>(g, a, stride, i, half, terms, acc);
+    const uint32_t off = j * FRMLE_THREADS + lane, i = w.first + k * g.tile + off;
+    if (off >= g.tile || i >= w.end) break;
+    ok &= frm_round_pair<POINTS>(g, w, frm_round_rows(w, a, partial), i, terms, acc);
   }
   return ok;
 }
@@ -339,7 +405,8 @@ __global__ void __launch_bounds__(FRMLE_THREADS) k_frmle_eq(uint32_t* out, size_
   frm_eq_lane(p, (size_t)blockIdx.x * FRMLE_THREADS + threadIdx.x, n, tables, out);
 }
 
-// block = tile k; partial[t * gridDim.x + k] = the tile's sum at point t.  One kernel per number of points, 2 .. 5 (g.points says which one runs): a
+// block = tile k; partial[t * tiles + k] = the tile's sum at point t, tiles = the word FRMLE_LOW_TILES behind the terms, which the host code writes in
+// both orders (read here, at the end, not kept from the start).  One kernel per number of points, 2 .. 5 (g.points says which one runs): a
 // round of degree 2 does not carry the registers of one of degree 4.
 template <int POINTS>
 __global__ void __launch_bounds__(FRMLE_THREADS) k_frmle_round(uint32_t* a, uint32_t half, uint32_t stride, const uint32_t* terms, uint32_t* partial, const FrmleRoundArgs g,
@@ -348,7 +415,7 @@ __global__ void __launch_bounds__(FRMLE_THREADS) k_frmle_round(uint32_t* a, uint
   fq* slot = reinterpret_cast<fq*>(lds);
   const uint32_t lane = threadIdx.x;
   fq acc[POINTS];
-  if (!frm_round_lane<POINTS>(g, a, half, stride, blockIdx.x, lane, terms, acc)) atomicOr(err, 1u);
+  if (!frm_round_lane<POINTS>(g, a, half, stride, blockIdx.x, lane, terms, acc, partial)) atomicOr(err, 1u);
 #pragma unroll
   for (int t = 0; t < POINTS; t++) {
     __syncthreads();
@@ -357,7 +424,7 @@ __global__ void __launch_bounds__(FRMLE_THREADS) k_frmle_round(uint32_t* a, uint
       __syncthreads();
       if (lane < (1u << step)) frm_sum_step(slot, step, lane);
     }
-    if (lane == 0) frm_store(partial, (size_t)t * gridDim.x + blockIdx.x, slot[0]);
+    if (lane == 0) frm_store(partial, (size_t)t * terms[FRMLE_TERM_WORDS * g.num_terms + FRMLE_LOW_TILES] + blockIdx.x, slot[0]);
   }
 }
 

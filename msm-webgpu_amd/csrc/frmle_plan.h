@@ -43,8 +43,73 @@ inline std::vector<size_t> plan_levels(size_t n, uint32_t tile) {
 
 inline FrmleFoldArgs plan_fold(const Field& f, const uint8_t c[32]) {
   FrmleFoldArgs g;
+  memset(&g, 0, sizeof g);
   store_scaled(f, f.to_mont(host_fr::load32(c)), pow2(f, 261), g.c);
   return g;
+}
+
+// ---- low first (MSM_FRMLE_LOW_FIRST): the schedules ----------------------------------------------------------------------------------------------
+// Output i of a bind is a function of the elements 2 i and 2 i + 1 and, in place, is stored on slot i: an input of output i / 2.  Lanes of one
+// launch run in any order, across workgroups that do not wait for each other; launches on one stream run one after the other.  So within a
+// launch no lane may store where another lane of that launch reads.  Of the n / 2 outputs of a row,
+//   the upper half, [n / 4, n / 2), reads [n / 2, n) and stores to [n / 4, n / 2): apart, safe in place in one launch;
+//   the lower half, [0, n / 4), reads [0, n / 2) and would store to [0, n / 4): it goes to the scratch buffer instead, rows n / 4 apart.
+// The lower half runs FIRST -- it reads [n / 4, n / 2) as the row was --, the upper half second, and one device-to-device copy on the same stream
+// (not a kernel: hipMemcpy2DAsync) brings the scratch rows home.  n = 2 has one output, whose slot only its own lane reads: one launch in place.
+// The alternative, all n / 2 outputs to scratch and all copied back, moves n more elements per row where this moves n / 2.
+struct LowLaunch {
+  uint32_t first, count;  // the outputs first .. first + count - 1 of every row
+  bool to_scratch;        // stored to the scratch rows (`copy` elements apart) instead of the rows themselves
+};
+struct LowSchedule {
+  std::vector<LowLaunch> launches;  // in stream order
+  size_t copy = 0;                  // elements at the head of every row that come home from scratch afterwards
+};
+// the in-place bind of a table of n >= 2 elements to n / 2 outputs
+inline LowSchedule plan_low_in_place(size_t n) {
+  LowSchedule s;
+  const uint32_t outputs = (uint32_t)(n / 2), lower = outputs / 2;
+  if (lower) {
+    s.launches.push_back(LowLaunch{0, lower, true});
+    s.copy = lower;
+  }
+  s.launches.push_back(LowLaunch{lower, outputs - lower, false});
+  return s;
+}
+inline FrmleFoldArgs plan_fold_low(const Field& f, const uint8_t c[32], const LowLaunch& l, size_t out_stride) {
+  FrmleFoldArgs g = plan_fold(f, c);
+  g.low = 1, g.first = l.first, g.out_stride = (uint32_t)out_stride;
+  return g;
+}
+// The fused round over a table of n >= 4 elements is the same schedule over the PAIRS of the folded table: pair i (< n / 4) reads 4 i .. 4 i + 3
+// and stores the folded 2 i and 2 i + 1, so the pairs [0, n / 8) go to scratch (rows n / 4 apart) and [n / 8, n / 4) stay in place; n = 4 has one
+// pair.  Each launch has its own tiles, numbered one after the other: partials = the tiles of both.  A launch has half the round's pairs, and the
+// two run one after the other: with tiles of HALF the size (low_fused_tile) each of them has the workgroups the one top-first launch has --
+// at 2^20 and the design's tile 256, one per compute unit, where 128 would leave half the chip idle twice over.
+inline uint32_t low_fused_tile(uint32_t tile) { return tile / 2; }  // (tile >= 2)
+inline LowSchedule plan_low_fused(size_t n) {
+  LowSchedule s = plan_low_in_place(n / 2);  // (as many pairs as a table of n / 2 has outputs, split the same way)
+  s.copy *= 2;
+  return s;
+}
+inline uint32_t low_tiles(const LowLaunch& l, uint32_t tile) { return (l.count + tile - 1) / tile; }
+// the levels of a low-first fused round: the pairs, the partials of the schedule's launches (tiles of launch_tile pairs), and plain sums over
+// tiles of `tile` above them as plan_levels has them
+inline std::vector<size_t> plan_levels_low_fused(const LowSchedule& s, size_t pairs, uint32_t launch_tile, uint32_t tile) {
+  size_t partials = 0;
+  for (const LowLaunch& l : s.launches) partials += low_tiles(l, launch_tile);
+  std::vector<size_t> len(1, pairs);
+  if (partials > 1) {
+    const std::vector<size_t> above = plan_levels(partials, tile);
+    len.insert(len.end(), above.begin(), above.end());
+  }
+  return len;
+}
+// the point of eval and eq with point[j] at bit j: the top-first calls take it reversed
+inline std::vector<uint8_t> reversed_point(const uint8_t* point, int k) {
+  std::vector<uint8_t> out((size_t)k * 32);
+  for (int j = 0; j < k; j++) memcpy(out.data() + 32 * (size_t)j, point + 32 * (size_t)(k - 1 - j), 32);
+  return out;
 }
 
 // eval of a table of 2^k elements at point (k x 32 bytes; point[0] is the TOP bit's variable): level l binds the bits [l t, l t + vars) of the
@@ -121,6 +186,28 @@ inline FrmleRoundArgs plan_round(const Field& f, uint32_t tile, const Term* term
   }
   g.points = top + 1;
   return g;
+}
+// The constants of a round as k_frmle_round takes them, in either order (top first: the one launch of all pairs): for every launch of the schedule the terms (`words` as plan_round left them) and behind them the
+// FRMLE_LOW_WORDS of that launch (csrc/frmle_kernels.h) -- launch l takes its terms at word l * low_block_words(num_terms).  tiles: of all
+// launches; out_at: where the scratch rows begin, in words behind the FIRST launch's `partial` (a later launch's is moved on by 8 words per tile
+// before it, which is taken off here); the scratch rows are s.copy elements apart.
+inline size_t low_block_words(size_t num_terms) { return num_terms * FRMLE_TERM_WORDS + FRMLE_LOW_WORDS; }
+inline void plan_round_launches(FrmleRoundArgs& g, bool low, const LowSchedule& s, uint32_t tile, size_t out_at, std::vector<uint32_t>& words) {
+  g.low = low, g.tile = tile;  // (tile: of the launches -- low_fused_tile of the call's for the low-first fused round)
+  const std::vector<uint32_t> terms = words;
+  const size_t block = low_block_words(g.num_terms);
+  words.assign(block * s.launches.size(), 0);
+  uint32_t tiles = 0, before = 0;
+  for (const LowLaunch& l : s.launches) tiles += low_tiles(l, tile);
+  for (size_t k = 0; k < s.launches.size(); k++) {
+    const LowLaunch& l = s.launches[k];
+    uint32_t* w = words.data() + block * k;
+    memcpy(w, terms.data(), terms.size() * 4);
+    w += terms.size();
+    w[FRMLE_LOW_FIRST_PAIR] = l.first, w[FRMLE_LOW_END_PAIR] = l.first + l.count, w[FRMLE_LOW_TILES] = tiles;
+    w[FRMLE_LOW_TO_SCRATCH] = l.to_scratch, w[FRMLE_LOW_OUT_AT] = (uint32_t)(out_at - 8 * (size_t)before), w[FRMLE_LOW_OUT_STRIDE] = (uint32_t)s.copy;
+    before += low_tiles(l, tile);
+  }
 }
 
 }  // namespace msm_frmle

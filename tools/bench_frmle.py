@@ -14,7 +14,14 @@ Protocol: device data, every shape warmed up, then `--calls` calls timed back to
 calls and their yardsticks ALTERNATED `--rounds` times; min .. max over the rounds beside every mean.  Each shape is checked in the run: the new
 and the old results against each other, the eq table on sampled elements against Python integers.
 
-usage: tools/bench_frmle.py [--shapes bn254:16,bn254:20,bn254:24] [--calls 20] [--rounds 3] [--no-check] [--no-prover]"""
+--order low (or both) adds, for every shape, the calls of msm-webgpu_amd/multilinear.py under MSM_FRMLE_LOW_FIRST next to the same calls top first,
+alternated in the same way: the fold apart and in place, the round of degree 2 over two rows and of degree 3 over four, the fused round, and
+at 2^20 the whole proof.  The ratio low / top is reported, not judged; the bytes say parity for the fold apart and the plain round, and the copy
+of a quarter of every row for the two in-place binds.  A last line sets the in-place fold's schedule (a quarter of
+every row through scratch) against the other one put together from calls: all outputs apart, then half of every row copied home.
+--order low leaves the yardstick pairs above out.
+
+usage: tools/bench_frmle.py [--shapes bn254:16,bn254:20,bn254:24] [--calls 20] [--rounds 3] [--no-check] [--no-prover] [--order top|low|both]"""
 import argparse
 import hashlib
 import os
@@ -30,6 +37,7 @@ import torch  # noqa: E402
 
 import msm_webgpu_amd as m  # noqa: E402
 from msm_webgpu_amd import api  # noqa: E402
+from msm_webgpu_amd import multilinear as ml  # noqa: E402
 
 PROVER_LOG_N = 20
 
@@ -54,6 +62,55 @@ def report(label, name, new, ref_name, ref, rounds, calls, judged=True):
         ("MET" if mn <= mr else "NOT MET") if judged else "(reported)"), flush=True)
 
 
+def orders_section(c, label, k, r, a, rnd):
+    """the low-first calls against the same calls top first, on four rows of 2^k scalars"""
+    n = 1 << k
+    rows = c.sample_scalars(4 * n, 61)
+    work, out = torch.empty_like(rows), torch.empty_like(rows)
+    work.copy_(rows)
+    ch = rnd.randrange(2, r)
+    t2, t3 = [(1, (0, 1))], [(1, (0, 1, 2)), (r - 1, (0, 3))]
+
+    def challenge(j, values):
+        return int.from_bytes(hashlib.sha256(values).digest(), "little") % r
+
+    def prove(order):
+        work.copy_(rows)
+        return ml.sumcheck_prove(c, work, t3, 4, challenge, order=order)
+
+    def both(fn):
+        return (lambda: fn("low")), (lambda: fn("top"))
+
+    cases = [("fold apart, 4 rows", a.calls) + both(lambda o: ml.fold(c, rows, ch, batch=4, out=out, order=o)),
+             ("fold in place, 4 rows", a.calls) + both(lambda o: ml.fold(c, work, ch, batch=4, order=o)),
+             ("round, degree 2, 2 rows", a.calls) + both(lambda o: ml.sumcheck_round(c, rows[:2 * n], t2, batch=2, order=o)),
+             ("round, degree 3, 4 rows", a.calls) + both(lambda o: ml.sumcheck_round(c, rows, t3, batch=4, order=o)),
+             ("fused round, degree 3", a.calls) + both(lambda o: ml.sumcheck_round(c, work, t3, batch=4, fold=ch, order=o))]
+    if k == PROVER_LOG_N and not a.no_prover:
+        cases.append(("sumcheck_prove, %d rounds" % k, max(a.calls // 4, 1)) + both(prove))
+
+    # the schedule the library did not take, put together from calls: ALL n / 2 outputs of every row to another buffer in one launch, then n / 2
+    # scalars of every row copied home -- against the one it took (n / 4 to scratch, n / 4 in place, n / 4 copied)
+    def all_through_scratch():
+        ml.fold(c, work, ch, batch=4, out=out)
+        work.reshape(4, n, 32)[:, :n // 2].copy_(out.reshape(4, n, 32)[:, :n // 2])
+        torch.cuda.synchronize()
+
+    cases.append(("in place vs all via scratch", a.calls, lambda: ml.fold(c, work, ch, batch=4), all_through_scratch))
+    for _, _, low, top in cases:
+        low(), top()
+    t = {}
+    for _ in range(a.rounds):
+        for name, calls, low, top in cases:
+            t.setdefault(name, []).append(timed(low, calls))
+            t.setdefault(name + " / top", []).append(timed(top, calls))
+    for name, calls, _, _ in cases:
+        other = "fold apart + copy of n / 2 (low first)" if " vs " in name else "the same call top first"
+        report(label, "low: " + name, t[name], other, t[name + " / top"], a.rounds, calls, judged=False)
+    del rows, work, out
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="bn254:16,bn254:20,bn254:24")
@@ -61,6 +118,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-prover", action="store_true")
+    ap.add_argument("--order", choices=("top", "low", "both"), default="top")
     a = ap.parse_args()
     print("device: %s, %d CUs" % (torch.cuda.get_device_name(0), torch.cuda.get_device_properties(0).multi_processor_count))
     rnd = random.Random(29)
@@ -73,6 +131,10 @@ def main():
         if curve not in ctxs:
             ctxs[curve] = m.MsmContext(0, curve=curve)
         c = ctxs[curve]
+        if a.order != "top":
+            orders_section(c, "%-10s 2^%-2d" % (curve, k), k, r, a, rnd)
+            if a.order == "low":
+                continue
         point = [rnd.randrange(2, r) for _ in range(k)]
         ch = rnd.randrange(2, r)
         ab = c.sample_scalars(2 * n, 51)  # rows A and B of every round below
