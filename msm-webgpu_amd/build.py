@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 # MSM_HIP_SO: load (and build into) another file, e.g. a diagnostic variant next to the product library
 SO = os.environ.get("MSM_HIP_SO") or os.path.join(HERE, "libmsm_hip.so")
-SOURCES = ["msm_hip.hip", "curve_bn254.hip", "curve_grumpkin.hip", "curve_pallas.hip", "curve_vesta.hip", "curve_bls12_381.hip", "curve_bn254_g2.hip", "curve_bls12_381_g2.hip", "fq2.h", "bn254_g2_constants.h", "bls12_381_g2_constants.h", "fq28x14_asm.h", "bls12_381_constants.h", "curve_ops.h", "msm_layout.h", "recode.h", "sort_kernels.h", "msm_kernels.h", "g1.h", "fq29.h", "fq29_asm.h", "host_g1.h", "host_fr.h", "host_pool.h", "host_worker.h", "glv.h", "scalar_mul.h", "msm_mgpu.h", "curve_select.h", "curve_unit.h", "grumpkin_constants.h", "bn254_constants.h", "pallas_constants.h", "vesta_constants.h"]
+SOURCES = ["msm_hip.hip", "msm_plan.h", "msm_ctx.h", "msm_enqueue.h", "msm_bases.h", "msm_oneshot.h", "msm_hooks.h", "msm_mul.h", "msm_fft.h", "curve_bn254.hip", "curve_grumpkin.hip", "curve_pallas.hip", "curve_vesta.hip", "curve_bls12_381.hip", "curve_bn254_g2.hip", "curve_bls12_381_g2.hip", "fq2.h", "bn254_g2_constants.h", "bls12_381_g2_constants.h", "fq28x14_asm.h", "bls12_381_constants.h", "curve_ops.h", "msm_layout.h", "recode.h", "sort_kernels.h", "msm_kernels.h", "g1.h", "fq29.h", "fq29_asm.h", "host_g1.h", "host_fr.h", "host_pool.h", "host_worker.h", "glv.h", "scalar_mul.h", "msm_mgpu.h", "curve_select.h", "curve_unit.h", "grumpkin_constants.h", "bn254_constants.h", "pallas_constants.h", "vesta_constants.h"]
 HEADER = os.path.join(HERE, "..", "include", "msm_hip.h")
 # The scalar-field libraries (include/msm_<name>.h), each a library of its own beside libmsm_hip.so: one translation unit per scalar field, its
 # own sources and stamp.  None of them is part of libmsm_hip.so (SO, SOURCES, TRANSLATION_UNITS and the no-argument forms of the functions

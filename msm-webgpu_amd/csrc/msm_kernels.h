@@ -492,7 +492,7 @@ struct glv_split_fn {
 // The reference gives one thread one bucket, so a wave runs as long as its fullest bucket.  Here every lane owns a
 // fixed-length chunk of `chunk_len` consecutive entries of the slot-sorted list -- equal work per lane whatever the bucket
 // sizes -- and flushes its accumulator whenever the slot changes.  The host picks a chunk length (in
-// [SMVP_CHUNK_MIN, SMVP_CHUNK_MAX]; msm_hip.hip: chunk_len_for) so that about SMVP_TARGET_LANES lanes exist for n entries per window (about three rounds of 3 waves
+// [SMVP_CHUNK_MIN, SMVP_CHUNK_MAX]; msm_plan.h: chunk_len_for) so that about SMVP_TARGET_LANES lanes exist for n entries per window (about three rounds of 3 waves
 // per SIMD at 168 VGPRs, no scratch) and sizes the chunk arrays and grids with it; the length actually used is settled on the device
 // from the entries the sort produced (sort_kernels.h, smvp_chunk_len: never longer than the host's).  Runs that cross a chunk boundary leave a "tail" piece
 // (in the chunk where the run starts) and "head" pieces (in the chunks it continues into); k_smvp_stitch adds them.

@@ -1,10 +1,15 @@
 // Layout constants of the MSM pipeline that no field enters: window and bucket-grid sizes, the sort's bin structure, the shapes of the scratch
-// arrays the host allocates and the kernels index, and the bits of the device error word.  Included by the host code (msm_hip.hip), by the
+// arrays the host allocates and the kernels index, and the bits of the device error word.  Included by the host code (msm_plan.h), by the
 // curve-neutral recode and sort (recode.h, sort_kernels.h) and by every curve unit (msm_kernels.h).  No kernel and no device object lives here.
 // Sizes that follow a unit's field (CW, REC_WORDS, XYZZ_WORDS, BPR_USE_W256, the *_WAVES_PER_SIMD values) stay in msm_kernels.h and reach the
 // host through CurveOps (curve_ops.h).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#else  // plain C++: the launch planner on the CPU (msm_plan.h under tests/host_harness/msm_plan_harness.cpp)
+#define __host__
+#define __device__
+#endif
 
 #include <cstddef>
 #include <cstdint>
@@ -46,7 +51,7 @@ constexpr int WIDE_SHARE_VWIN_MAX = 4;  // shares of more virtual windows than t
 constexpr int BYTE_BINS = 256;
 constexpr int BYTE_MAXLW = MAXLW * NCOARSE / BYTE_BINS;  // local windows a byte-window launch may carry (32)
 
-// ---- SMVP chunks (msm_kernels.h: k_smvp_chunks; msm_hip.hip: chunk_len_for; sort_kernels.h: smvp_chunk_len)
+// ---- SMVP chunks (msm_kernels.h: k_smvp_chunks; msm_plan.h: chunk_len_for; sort_kernels.h: smvp_chunk_len)
 constexpr int SMVP_CHUNK_MIN_ENTRIES = 8;
 constexpr int SMVP_CHUNK_MIN = SMVP_CHUNK_MIN_ENTRIES;
 constexpr int SMVP_CHUNK_MAX = 1024;

@@ -323,7 +323,7 @@ int msm_hip_mgpu_set_bases(msm_hip_mgpu* m, const uint8_t* xy_host, size_t n, ui
     if (ms.pending) return MSM_HIP_ERR_SLOT_BUSY;
   // The mode the window-sharded launches run in follows the flags: the 8 half-length windows with the endomorphism images, the virtual windows
   // with wide tables, else the reference's 16 windows over the n plain records.  flags = 0 (the drop-in call shape) is resolved ONCE here to the
-  // plain set -- a context's own default (the endomorphism images on the prime-order curves, msm_hip.hip: resolve_base_flags) would make every
+  // plain set -- a context's own default (the endomorphism images on the prime-order curves, msm_bases.h: resolve_base_flags) would make every
   // device store 2n records and run k_endo_points for launches that then read only the first n.  Whole-MSM batches
   // (msm_hip_mgpu_run_batch) run in the mode the flags name.
   if (!(flags & (MSM_HIP_BASES_PRECOMPUTE | MSM_HIP_BASES_PRECOMPUTE_WIDE | MSM_HIP_BASES_ENDOMORPHISM | MSM_HIP_BASES_PLAIN))) flags |= MSM_HIP_BASES_PLAIN;

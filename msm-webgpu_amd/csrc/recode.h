@@ -15,7 +15,7 @@ using namespace msm_layout;
 // Window size as a parameter (the reference hard-codes c, src/cuzk/msm.rs:79-82): C-bit signed digits,
 // 2^(C-1) bucket slots per window, NWIN = ceil(255 / C) windows (254-bit scalars + one bit for the recode's carry).
 // Small MSMs are dominated by the bucket reduce of 16 x 2^15 mostly empty buckets; a smaller C trades a few more
-// additions per point for 16 x / 4 x fewer buckets.  The host picks C from n (msm_hip.hip: pick_window_bits).
+// additions per point for 16 x / 4 x fewer buckets.  The host picks C from n (msm_plan.h: pick_window_bits).
 // SW = words per scalar the recode reads: 8 (a 254-bit scalar) or 4 (one 127-bit half of the endomorphism split, csrc/glv.h:
 // magnitude in bits 0 .. 126, sign in bit 127).
 // NB != 0: narrow scalars (MSM_HIP_SCALARS_U8 .. U64, MSM_HIP_SCALAR_U128) of NB bytes, unsigned, in SW = 1 (NB <= 4), 2 (NB = 8) or 4 (NB = 16)

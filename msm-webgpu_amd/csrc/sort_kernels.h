@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256) k_scan_tiles(uint32_t* __restrict__ count
 // the consumers load that one word (deriving it per workgroup from the 16 .. 64 window totals cost every SMVP workgroup a chain of
 // scalar loads at its start: +1 % on the whole MSM).
 // (rounds 1 - 2 kept chunk lengths multiples of 4 for the index loads of that time; any length works since the SMVP loads one index per entry,
-//  and the host now picks the length by the workgroups-per-CU count it produces: msm_hip.hip, chunk_len_for)
+//  and the host now picks the length by the workgroups-per-CU count it produces: msm_plan.h, chunk_len_for)
 constexpr uint32_t SMVP_CHUNK_ROUND = 1;
 __device__ __forceinline__ uint32_t smvp_chunk_len(uint32_t mx, uint32_t chunks, uint32_t host_len) {
   uint32_t len = (uint32_t)(((uint64_t)mx + chunks - 1) / chunks);
@@ -438,7 +438,7 @@ __global__ void __launch_bounds__(256) k_byte_chunks(const uint32_t* __restrict_
 // Which C (profiles/r04_wide_tables.txt): what an MSM costs in the pipeline is sort + SMVP + the stitch / reduce work that runs beside the
 // next launch, and that grows with the bucket sets -- 20 bits (16 of them) loses to the endomorphism mode at 2^20 although its SMVP is 0.85 ms
 // alone against 0.99, and wins by 18 % at 2^24; 17 bits (2 of them) wins at 2^20.
-// The digit width C is a template parameter of the two kernels (the tables are built for it when the bases are set: msm_hip.hip picks it from
+// The digit width C is a template parameter of the two kernels (the tables are built for it when the bases are set: msm_plan.h, pick_wide_bits, picks it from
 // the number of bases -- 16 bits up to 2^16 points and 17 up to 2^20, where the bucket sets' stitch / reduce still counts, 20 beyond).
 template <int C>
 struct WideCfg {
@@ -453,7 +453,7 @@ struct WideCfg {
 // magnitudes would all fall into the lowest virtual windows, which would then carry far more entries than the others, and the SMVP's lanes are
 // as long as the fullest window makes them (first measurement at 20 bits: SMVP 1.06 ms instead of 0.85).  The top table is therefore
 // 2^(C (T - 1) - top_shift) P_i and the top digit is used as d << top_shift: the same product for any point (exact integer arithmetic: no
-// assumption on the point's order), spread over the virtual windows.  top_shift (msm_hip.hip: wide_top_shift) is the largest for which the top
+// assumption on the point's order), spread over the virtual windows.  top_shift (msm_plan.h: wide_top_shift) is the largest for which the top
 // digit of every scalar below the scalar field's modulus stays within 2^(C-1): for BN254 0 / 11 / 5 at 17 / 19 / 20 bits.  A scalar whose
 // shifted top digit passes that -- at or above the modulus -- is rejected like one that overflows the reference's recode (ERRBIT_SCALAR_CARRY).
 // signed C-bit digit of window w of the biased scalar t (WinCfg<C>::WORDS words): its magnitude 1 .. 2^(C - 1) (0: no entry) and sign

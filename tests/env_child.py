@@ -35,7 +35,7 @@ def nwin(bits, halves=False):
 
 
 def pick_window_bits(forced, n, nvec, halves):
-    """msm_hip.hip: pick_window_bits, for a forced width (the bump of grouped launches whose windows would not fit MAXLW)"""
+    """msm_plan.h: pick_window_bits, for a forced width (the bump of grouped launches whose windows would not fit MAXLW)"""
     bits = forced or ((14 if n <= 1 << 16 else 16) if nvec > 1 else (12 if n <= 1 << 12 else 16))
     while bits < 16 and nvec * nwin(bits, halves) > MAXLW:
         bits += 2

@@ -169,7 +169,7 @@ def test_wide_table_shapes_follow_the_scalar_field(built):
     """Host-only (msm_hip_wide_config): the wide fixed-base tables' digit width, table count, virtual windows and top-digit shift against an
     independent computation from every curve's scalar-field modulus: the top digit of a C-bit signed recode is at most
     ((r - 1 + bias) >> P) - 2^(C-1), P = C (T - 1), bias = the recode's constant; it must not pass 2^(C-1) (else the width cannot hold the
-    curve's scalars -- 17 bits on BLS12-381); the library's bound on it (a 64-bit fraction, msm_hip.hip: wide_top_max) must never be below the exact
+    curve's scalars -- 17 bits on BLS12-381); the library's bound on it (a 64-bit fraction, msm_plan.h: wide_top_max) must never be below the exact
     value computed here.  The top digit is used unshifted since round 5 (interleaved virtual windows)."""
     import importlib
 

@@ -2,7 +2,7 @@
 (plain, endomorphism, 16-bit tables, wide tables) x window setting (auto, 12, 14, 16) x shape (dense, sparse), through every whole-MSM entry point
 (sync host, sync device, launch + finish on a non-zero slot, and for dense vectors the host and device batch).  Nothing is sampled: every run
 reaches every cell, and after every call last_window_bits() must be the width the documented rules give (include/msm_hip.h; modelled by
-run_bits below), which proves the cell was reached.  The pairs the API rejects are asserted as rejections.
+tests/launch_model.py), which proves the cell was reached.  The pairs the API rejects are asserted as rejections.
 
 Values plant the edges of the signed recode at the width that runs (tests/edge_scalars.py); each oracle answer is computed once per (points,
 integers, indices) and shared by every cell that takes the same input.  A long-lived context then runs a seeded walk through the matrix with
@@ -18,14 +18,13 @@ import torch
 import msm_webgpu_amd as m
 from oracle import cpu
 from tests.edge_scalars import edge_vector
+from tests.launch_model import NB, batch_groups, run_bits  # the documented rules
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID_ARG = -2
 FORMATS = ["canonical", "mont256", "u8", "u16", "u32", "u64"]
-NB = {"canonical": 0, "mont256": 0, "u8": 1, "u16": 2, "u32": 4, "u64": 8}
 MODES = ["plain", "endomorphism", "tables", "wide"]
 WINDOWS = [0, 12, 14, 16]
-MAXLW, BYTE_MAXLW, BYTE_WBITS = 64, 32, 12
 NP_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
 TORCH_DTYPES = {1: torch.uint8, 2: torch.uint16, 4: torch.uint32, 8: torch.uint64}
 OTHER_CURVES = ["grumpkin", "pallas", "vesta", "bls12_381", "bn254_g2", "bls12_381_g2"]
@@ -44,52 +43,6 @@ def gpu(built):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return True
-
-
-# ---------------------------------------------------------------------------------------------------------------- the documented rules
-def nwin_of(bits, halves=False):
-    return ((127 if halves else 254) + bits) // bits
-
-
-def narrow_nwin_of(bits, nb):
-    return (8 * nb + bits) // bits
-
-
-def pick_window_bits(fixed, n, nvec, halves=False, nb=0):
-    """msm_hip.hip: the fixed width, or 12 bits up to 2^12 points and 16 beyond for one MSM per launch, 14 up to 2^16 for several; widened
-    until the launch's windows fit MAXLW"""
-    bits = fixed or ((14 if n <= 1 << 16 else 16) if nvec > 1 else (12 if n <= 1 << 12 else 16))
-    while bits < 16 and nvec * (narrow_nwin_of(bits, nb) if nb else nwin_of(bits, halves)) > MAXLW:
-        bits += 2
-    return bits
-
-
-def run_bits(fmt, mode, fixed, n, nvec=1):
-    """the window width a whole-MSM launch of nvec vectors of n points (or a sparse launch of n entries) runs at"""
-    nb = NB[fmt]
-    if nb in (1, 2):
-        return BYTE_WBITS  # byte windows
-    if nb:
-        return pick_window_bits(fixed, n, nvec, nb=nb)  # truncated signed windows, on the plain records whatever the base mode
-    if mode in ("tables", "wide"):
-        return 16  # (wide tables: everything behind the recode sees 16-bit local windows)
-    return pick_window_bits(fixed, n, nvec, halves=mode == "endomorphism")
-
-
-def batch_groups(fmt, mode, fixed, n, batch, wide_vwin=1):
-    """vectors per launch of the batch runners (msm_hip.hip: batch_group), in launch order"""
-    nb = NB[fmt]
-    if nb:
-        fit = (BYTE_MAXLW // nb) if nb <= 2 else MAXLW // narrow_nwin_of(pick_window_bits(fixed, n, 2, nb=nb), nb)
-    elif mode == "wide":
-        fit = 24 // wide_vwin
-    elif mode == "tables":
-        fit = MAXLW
-    else:
-        halves = mode == "endomorphism"
-        fit = MAXLW // nwin_of(pick_window_bits(fixed, n, 2, halves), halves)
-    g = max(1, min((1 << 20) // n, fit, batch))
-    return [min(g, batch - first) for first in range(0, batch, g)]
 
 
 def plant_bits(fmt, mode, fixed, n):

@@ -14,7 +14,8 @@ import msm_webgpu_amd as m
 from oracle import cpu
 from tests import signed_scalar_model as model
 from tests.edge_scalars import edge_vector
-from tests.test_gpu_launch_matrix import narrow_nwin_of, oracle_module, pick_window_bits, scalar_order, subgroup_points_bls12_381
+from tests.launch_model import narrow_nwin_of, pick_window_bits
+from tests.test_gpu_launch_matrix import oracle_module, scalar_order, subgroup_points_bls12_381
 
 pytestmark = pytest.mark.gpu
 ERR_INVALID_ARG = -2

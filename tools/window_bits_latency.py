@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Single-MSM latency and pipelined throughput per window size and n (chooses the thresholds of pick_window_bits, msm_hip.hip).
+"""Single-MSM latency and pipelined throughput per window size and n (chooses the thresholds of pick_window_bits, msm_plan.h).
 usage (GPU box): python tools/window_bits_latency.py > gpurun_out/r02_window_bits_latency.txt"""
 import os
 import sys
