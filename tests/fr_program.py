@@ -26,12 +26,23 @@ which uploads a vector the generator drew and calls no library.  Counts that do 
 `a` nor MISSING are refused by the Python layer (REFUSED) after the library looked: the output range is then among the step's writes -- unchanged
 for a wrong sum, with that element zero for a bad index.  An output that cuts an input or the other output is refused before the C call like a
 hash step's cut (column_cut), and like it is not flagged "overlap".  NO VALUE >= r IS PLANTED before a column step: the library does not
-compare with r, so the value would be copied into the arena and the NEXT step refused for the wrong reason."""
+compare with r, so the value would be copied into the arena and the NEXT step refused for the wrong reason.
+
+libmsm_frmle's steps "mle_fold", "mle_eval", "eq" and "round" take an ORDER: order="low" is MSM_FRMLE_LOW_FIRST (the variable x_j at bit j of the
+index; the device side calls msm_webgpu_amd.multilinear), no order argument is top first (the context's scalars_* methods), so a program printed
+before there was an order replays as it is.  The model of a low-first step is tests/frmle_low_model.py.  A low-first bind IN PLACE -- an
+mle_fold onto its input, a round with `fold` -- leaves the scalars [n / 2, n) of every row UNSPECIFIED (include/msm_frmle.h): the model keeps
+them as they were and names exactly those ranges in "rewrite", so the driver writes the model's bytes there; [0, n / 2) is compared, and [n, stride)
+and all the rest must not change, which the whole-arena compare at the end sees to.  "gemini" is multilinear.gemini_folds of one row of 2^k
+scalars, k >= 1: the folds f_1 | .. | f_k, n - 1 scalars, copied from the tensor the call returns into a range of the arena; a planted value in
+the row refuses it (ERR_NONCANONICAL) before that copy, so the range stays as it was.  Behind a top-first step the generator sometimes puts the
+same entry point low first with no step between -- on either field, small behind large and large behind small --, and behind an mle_eval a
+low-first fused round of fewer levels: the scratch rows of the round then lie where the eval's levels lay."""
 import functools
 import hashlib
 import random
 
-from tests import frcol_model, frgate_model, frhash2_model, frhash_model, frlook_model, frmat_model, frmle_model, frpoly_model, frvec_model, ntt_model
+from tests import frcol_model, frgate_model, frhash2_model, frhash_model, frlook_model, frmat_model, frmle_low_model, frmle_model, frpoly_model, frvec_model, ntt_model
 
 FIELD_R = {
     "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
@@ -64,11 +75,12 @@ ERR_INVALID_ARG, ERR_NONCANONICAL, REFUSED = -2, -4, "refused"  # MSM_HIP_ERR_*;
 HOOKS = {"fr_test_pass_bits": (0, 1, 2, 3, 5), "frvec_test_tile": (0, 2, 3, 8, 64), "frpoly_test_tile": (0, 2, 3, 8, 64), "frmle_test_tile": (0, 2, 8, 64),
          "frmat_test_tile": (0, 2, 8, 64), "frlook_test_hash_bits": (0, 1, 3, 8), "frhash_test_tile": (0, 1, 3, 4, 64), "frcol_test_tile": (0, 2, 3, 8, 64)}
 LIBRARY = {"map": "frvec", "inverse": "frvec", "scan": "frvec", "fft": "fr", "eval": "frpoly", "divide": "frpoly", "dot": "frpoly", "combine": "frpoly",
-           "powers": "frpoly", "mle_fold": "frmle", "mle_eval": "frmle", "eq": "frmle", "round": "frmle", "matrix": "frmat", "matvec": "frmat", "gate": "frgate",
+           "powers": "frpoly", "mle_fold": "frmle", "mle_eval": "frmle", "eq": "frmle", "round": "frmle", "gemini": "frmle", "matrix": "frmat", "matvec": "frmat", "gate": "frgate",
            "vanishing_inverse": "frgate", "quotient": "frgate", "table": "frlook", "mult": "frlook", "poseidon": "frhash", "poseidon2": "frhash", "permute": "frhash", "sponge": "frhash", "tree": "frhash", "expand": "frcol", "pair": "frcol", "gather": "frcol"}
 LIBRARIES = ("fr", "frvec", "frpoly", "frmle", "frmat", "frgate", "frlook", "frhash", "frcol")
-GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "matrix", "matvec", "gate", "table", "mult", "poseidon", "poseidon2", "permute", "sponge", "tree", "expand", "pair",
+GRUMPKIN_KINDS = ("mle_fold", "mle_eval", "eq", "round", "gemini", "matrix", "matvec", "gate", "table", "mult", "poseidon", "poseidon2", "permute", "sponge", "tree", "expand", "pair",
                   "gather")  # the libraries that serve its scalar field
+FRMLE_ORDERED = ("mle_fold", "mle_eval", "eq", "round")  # the steps that take an order: "low" (MSM_FRMLE_LOW_FIRST), or none, which is top first
 HASH_CALLS = ("permute", "sponge", "tree")  # the steps that call libmsm_frhash ("poseidon" and "poseidon2" touch no device)
 HASH_MAKERS = ("poseidon", "poseidon2")  # the steps that make a handle: its kind
 COLUMN_CALLS = ("expand", "pair", "gather")  # the steps that call libmsm_frcol
@@ -159,17 +171,20 @@ class Model:
         planted.clear()
         return spots
 
-    def _run(self, f, reads, writes, compute):
-        """reads: the ranges whose every scalar the call compares with r; writes: what it writes; compute() -> ([(off16, bytes), ..], host)"""
+    def _run(self, f, reads, writes, compute, loose=(), kept=False):
+        """reads: the ranges whose every scalar the call compares with r; writes: what it writes; compute() -> ([(off16, bytes), ..], host);
+        loose: ranges that the call leaves unspecified even where it succeeds (the model keeps them as they were, the driver rewrites them);
+        kept: a refused call leaves `writes` as they were (the whole-arena compare at the end sees to it) instead of unspecified"""
         if self.planted[f]:
             hit = any(_cuts((p, 1), rd) and (p - rd[0]) % 2 == 0 for p in self.planted[f] for rd in reads)
             assert hit, "a planted value must be read by the step that follows it"
-            return {"error": ERR_NONCANONICAL, "writes": [], "rewrite": [tuple(w) for w in writes] + self._heal(f, self.planted[f]), "host": None}
+            lost = [] if kept else [tuple(w) for w in writes] + [tuple(w) for w in loose]
+            return {"error": ERR_NONCANONICAL, "writes": [], "rewrite": lost + self._heal(f, self.planted[f]), "host": None}
         assert not any(_cuts((p, 1), rd) for p in self.quiet[f] for rd in reads), "a quietly planted value lies where the step that follows it does not read"
         puts, host = compute()
         for off16, data in puts:
             self.put(f, off16, data)
-        return {"error": None, "writes": [(off16, len(data) // 32) for off16, data in puts], "rewrite": self._heal(f, self.quiet[f]), "host": host}
+        return {"error": None, "writes": [(off16, len(data) // 32) for off16, data in puts], "rewrite": [tuple(w) for w in loose] + self._heal(f, self.quiet[f]), "host": host}
 
     @staticmethod
     def _fail(code):
@@ -300,36 +315,60 @@ class Model:
         v = self.plain(f, a)
         return stride, [v[k * stride:k * stride + n] for k in range(batch)], [(a[0] + 2 * k * stride, n) for k in range(batch)]
 
-    def op_mle_fold(self, f, a, c, batch, n, out):
+    @staticmethod
+    def _mle(order):
+        """the model of an order: "top" (the steps leave it out) or "low" (MSM_FRMLE_LOW_FIRST) -- the latter never with code from the package"""
+        assert order in ("top", "low")
+        return frmle_low_model if order == "low" else frmle_model
+
+    @staticmethod
+    def _upper_halves(first, batch, stride, n):
+        """the scalars [n / 2, n) of every row: what a low-first bind in place leaves unspecified (include/msm_frmle.h)"""
+        return [(first + 2 * (k * stride + n // 2), n // 2) for k in range(batch)]
+
+    def op_mle_fold(self, f, a, c, batch, n, out, order="top"):
         dst = a if out is None else out
         stride = a[1] // batch
         span = (dst[0], (batch - 1) * stride + n)
         if self._partial(span, [(a[0], span[1])]):
             return self._fail(ERR_INVALID_ARG)
         _, rows, reads = self._rows(f, a, batch, n)
+        model = self._mle(order)
+        loose = self._upper_halves(dst[0], batch, stride, n) if order == "low" and dst[0] == a[0] else []
         return self._run(f, reads, [(dst[0] + 2 * k * stride, n // 2) for k in range(batch)],
-                         lambda: ([(dst[0] + 2 * k * stride, self.enc(f, frmle_model.fold(row, c, self.r[f]))) for k, row in enumerate(rows)], None))
+                         lambda: ([(dst[0] + 2 * k * stride, self.enc(f, model.fold(row, c, self.r[f]))) for k, row in enumerate(rows)], None), loose)
 
-    def op_mle_eval(self, f, a, point, batch, n):
+    def op_mle_eval(self, f, a, point, batch, n, order="top"):
         _, rows, reads = self._rows(f, a, batch, n)
-        return self._run(f, reads, [], lambda: ([], self.enc(f, [frmle_model.evaluate(row, point, self.r[f]) for row in rows])))
+        model = self._mle(order)
+        return self._run(f, reads, [], lambda: ([], self.enc(f, [model.evaluate(row, point, self.r[f]) for row in rows])))
 
-    def op_eq(self, f, point, scale, out):
+    def op_eq(self, f, point, scale, out, order="top"):
         assert out[1] == 1 << len(point)
-        return self._run(f, [], [out], lambda: ([(out[0], self.enc(f, frmle_model.eq(point, self.r[f], scale)))], None))
+        model = self._mle(order)
+        return self._run(f, [], [out], lambda: ([(out[0], self.enc(f, model.eq(point, self.r[f], scale)))], None))
 
-    def op_round(self, f, a, terms, batch, n, fold):
+    def op_round(self, f, a, terms, batch, n, fold, order="top"):
         stride, rows, ranges = self._rows(f, a, batch, n)
         named = sorted({row for _, which in terms for row in which})
         reads = ranges if fold is not None else [ranges[k] for k in named]
+        model = self._mle(order)
 
         def compute():
             puts, cur = [], rows
             if fold is not None:
-                cur = [frmle_model.fold(row, fold, self.r[f]) for row in rows]
+                cur = [model.fold(row, fold, self.r[f]) for row in rows]
                 puts = [(a[0] + 2 * k * stride, self.enc(f, row)) for k, row in enumerate(cur)]
-            return puts, self.enc(f, frmle_model.round_values(cur, [(c, tuple(w)) for c, w in terms], self.r[f]))
-        return self._run(f, reads, [(rg[0], n // 2) for rg in ranges] if fold is not None else [], compute)
+            return puts, self.enc(f, model.round_values(cur, [(c, tuple(w)) for c, w in terms], self.r[f]))
+        loose = self._upper_halves(a[0], batch, stride, n) if order == "low" and fold is not None else []
+        return self._run(f, reads, [(rg[0], n // 2) for rg in ranges] if fold is not None else [], compute, loose)
+
+    def op_gemini(self, f, a, point, out):
+        """multilinear.gemini_folds of one row, copied into `out`: f_1 | .. | f_k; a refused call never gets as far as the copy"""
+        n = a[1]
+        assert n == 1 << len(point) and n >= 2 and out[1] == n - 1 and not _cuts(out, a)
+        return self._run(f, [a], [out], lambda: ([(out[0], self.enc(f, [x for fj in frmle_low_model.gemini_folds(self.plain(f, a), point, self.r[f]) for x in fj]))], None),
+                         kept=True)
 
     # ---- libmsm_frmat --------------------------------------------------------------------------------------------------------------------------
     def op_matrix(self, f, slot, rows, cols, row_ptr, col_idx, vseed, transpose):
@@ -504,6 +543,33 @@ class Model:
         return self._moved(f, [(out, vals)], not ok)  # (a bad index: that element zero, the others as usual, and ValueError)
 
 
+FRMLE_TILE = 1024  # csrc/frmle_kernels.h; frmle_test_tile replaces it
+
+
+def plan_levels(n, tile):
+    """csrc/frmle_plan.h's plan_levels: the values per row, level by level, until one tile holds a level"""
+    lens = [n]
+    while -(-lens[-1] // tile) > 1:
+        lens.append(-(-lens[-1] // tile))
+    return lens
+
+
+def eval_levels(n, hook=0):
+    """the levels (launches) of an mle_eval of n scalars under frmle_test_tile `hook`: levels 1 .. live in the shared scratch"""
+    return len(plan_levels(n, hook or FRMLE_TILE))
+
+
+def low_fused_partials(n, hook=0):
+    """the levels of partial sums of a low-first fused round of n >= 4 scalars under frmle_test_tile `hook`: they lie in the shared scratch between
+    `partial` and the scratch rows (csrc/frmle_plan.h: plan_low_fused, plan_levels_low_fused; csrc/frmle_host.h: rows = scratch + lv.words).  0: one
+    pair, one launch, the values go straight to the result"""
+    tile = hook or FRMLE_TILE
+    pairs, launch_tile = n // 4, tile // 2
+    lower = pairs // 2
+    partials = sum(-(-count // launch_tile) for count in (lower, pairs - lower) if count)
+    return len(plan_levels(partials, tile)) if partials > 1 else 0
+
+
 def column_cut(step):
     """is this a call of libmsm_frcol whose output shares bytes with an input or with the other output -- a same start included: the Python
     layer refuses it (REFUSED) before the C call, with nothing written"""
@@ -604,7 +670,7 @@ def sizes(steps):
             width[f, a["slot"]] = a["t"]
         if a.get("overlap") or kind not in LIBRARY or column_cut((kind, f, a)):
             continue
-        if kind in ("map", "inverse"):
+        if kind in ("map", "inverse", "gemini"):
             n = a["a"][1]
         elif kind in ("scan", "eval", "divide", "dot"):
             n = a["a"][1] // a["batch"]
@@ -631,11 +697,11 @@ def sizes(steps):
 
 
 # ---- the generator ---------------------------------------------------------------------------------------------------------------------------------
-_WEIGHT = {"map": 10, "inverse": 5, "scan": 8, "fft": 8, "eval": 4, "divide": 5, "dot": 4, "combine": 4, "powers": 4, "mle_fold": 5, "mle_eval": 4, "eq": 3,
-           "round": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "poseidon": 4, "poseidon2": 4, "permute": 10, "sponge": 9, "tree": 7,
+_WEIGHT = {"map": 10, "inverse": 5, "scan": 8, "fft": 8, "eval": 4, "divide": 5, "dot": 4, "combine": 4, "powers": 4, "mle_fold": 5, "mle_eval": 4, "eq": 5,
+           "round": 6, "gemini": 6, "matrix": 4, "matvec": 8, "gate": 7, "vanishing_inverse": 2, "quotient": 2, "table": 4, "mult": 8, "poseidon": 4, "poseidon2": 4, "permute": 10, "sponge": 9, "tree": 7,
            "expand": 7, "pair": 6, "gather": 6, "words": 4, "format": 5, "hook": 8, "close": 3, "stream": 3, "overlap": 4}
 _LEN_WEIGHT = {1: 6, 2: 6, 63: 6, 64: 6, 65: 6, 255: 3, 256: 3, 257: 3, 1023: 1.6, 1024: 1.6, 1025: 1.6, 2051: 0.9, 4097: 0.6}
-_PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "matvec", "gate", "table", "mult", "permute", "sponge", "tree")
+_PLANTABLE = ("map", "inverse", "scan", "fft", "eval", "divide", "dot", "combine", "mle_fold", "mle_eval", "round", "gemini", "matvec", "gate", "table", "mult", "permute", "sponge", "tree")
 _OVERLAPS = ("map", "inverse", "scan", "divide", "combine", "mle_fold", "matvec", "expand", "pair", "gather")  # (the last three: cuts, refused by the Python layer)
 _BAD_WORDS = 0.07  # how often a word vector drawn for a column call is one that must be refused
 
@@ -656,6 +722,10 @@ class _Gen:
         self.prev_f, self.follow = None, None  # follow: (field, kind) of a large step that a small one of the same entry point is to follow
         self.plant_ok = kinds is None or "plant" in kinds
         self.last_fft = {}  # field -> (log_n, omega) of its last transform
+        self.hooks_set = []  # the names the last hook draw set
+        self.hooks = {h: 0 for h in HOOKS}  # as the steps so far leave them
+        # what run() asks of the next frmle step: its order, a table of 2^10 or more, a fused round, a table of exactly force_n scalars
+        self.force_order, self.force_big, self.force_fold, self.force_n = None, False, False, None
 
     # ---- draws ---------------------------------------------------------------------------------------------------------------------------
     def scalar(self, f):
@@ -669,6 +739,10 @@ class _Gen:
         return self.rnd.choices(pool, [_LEN_WEIGHT[n] for n in pool])[0]
 
     def log_n(self, small, least=0, most=12):
+        if self.force_n is not None:
+            return self.force_n.bit_length() - 1
+        if self.force_big:
+            return self.rnd.choice((10, 10, 11, 12))
         if small:
             return self.rnd.randrange(least, 7)
         pool = list(range(least, most + 1))
@@ -702,9 +776,14 @@ class _Gen:
     def emit(self, kind, f, **a):
         self.steps.append((kind, f, a))
 
-    def maybe_plant(self, f, kind, spots):
+    def order(self):
+        """the order of a frmle step, drawn per step: -> the step's order argument, which a top-first step leaves out (an old printed program replays)"""
+        low = self.force_order == "low" if self.force_order else self.rnd.random() < 0.5
+        return {"order": "low"} if low else {}
+
+    def maybe_plant(self, f, kind, spots, chance=0.09):
         """before a step that reads the scalars `spots` (off16 each): sometimes plant a value >= r in one of them"""
-        if self.plant_ok and not self.no_plant and kind in _PLANTABLE and spots and self.rnd.random() < 0.09:
+        if self.plant_ok and not self.no_plant and kind in _PLANTABLE and spots and self.rnd.random() < chance:
             r = self.r[f]
             self.emit("plant", f, at=self.rnd.choice(spots), value=self.rnd.choice((r, r + 1, (1 << 256) - 1, r + self.rnd.randrange(1 << 200))))
 
@@ -848,37 +927,77 @@ class _Gen:
 
     def g_mle_fold(self, f, small, overlap=False):
         n, batch, stride = self.table_rows(small, 1, 5)
+        order = self.order()
+        wide = bool(order) and not small and not overlap and self.force_n is None and self.rnd.random() < 0.12
+        if wide:  # low first over several workgroups to a launch, rows further apart than the scratch rows: mostly in place
+            n = self.rnd.choice((1024, 1024, 2048))
+            batch, stride = (2 if n == 2048 else self.rnd.choice((2, 3))), n + self.rnd.choice((1, 3))
         a = self.place(batch * stride)
         if overlap:  # (what counts is the span from the first row's first scalar to the last row's n-th)
             span = [a[0], (batch - 1) * stride + n]
             out = self.shifted(span, batch * stride)
             a[0] = span[0]
-        else:
-            out = self.out_for([a], batch * stride, [a]) if self.rnd.random() < 0.5 else None
+        elif order and 2 * batch * n <= BANK and self.rnd.random() < 0.2:  # low first, apart: out begins on the byte behind a's last, as a Gemini fold's does
+            stride = n
+            a = self.place(2 * batch * n)
+            a[1] = batch * n
+            out = [a[0] + 2 * batch * n, batch * n]
             self.maybe_plant(f, "mle_fold", self.spots(a, self.rnd, range(batch), stride, n))
-        self.emit("mle_fold", f, a=a, c=self.scalar(f), batch=batch, n=n, out=out, **({"overlap": True} if overlap else {}))
+        else:
+            out = self.out_for([a], batch * stride, [a]) if self.rnd.random() < (0.2 if wide else 0.5) else None
+            in_place = out is None or out[0] == a[0]  # (low first in place: two launches read the row, a value is planted more often)
+            self.maybe_plant(f, "mle_fold", self.spots(a, self.rnd, range(batch), stride, n), 0.2 if order and in_place and not wide else 0.09)
+        self.emit("mle_fold", f, a=a, c=self.scalar(f), batch=batch, n=n, out=out, **order, **({"overlap": True} if overlap else {}))
         return n
 
     def g_mle_eval(self, f, small):
         n, batch, stride = self.table_rows(small, 0, 5)
+        if not small and self.force_n is None and not self.force_big and self.rnd.random() < 0.2:
+            # several levels in the shared scratch more often than log_n has them: two tiles of the design's 1024, or 2^6 and more under a small hook
+            n = self.rnd.choice((64, 256, 512) if self.hooks["frmle_test_tile"] in (2, 8) else (2048, 2048, 4096))
+            batch = self.rnd.choice((1, 2)) if 2 * n + 2 <= BANK else 1
+            stride = n + self.rnd.choice((0, 1))
         a = self.place(batch * stride)
         self.maybe_plant(f, "mle_eval", self.spots(a, self.rnd, range(batch), stride, n))
-        self.emit("mle_eval", f, a=a, point=[self.scalar(f) for _ in range(n.bit_length() - 1)], batch=batch, n=n)
+        self.emit("mle_eval", f, a=a, point=[self.scalar(f) for _ in range(n.bit_length() - 1)], batch=batch, n=n, **self.order())
         return n
 
     def g_eq(self, f, small):
         k = self.log_n(small)
-        self.emit("eq", f, point=[self.scalar(f) for _ in range(k)], scale=self.scalar(f) if self.rnd.random() < 0.5 else 1, out=self.place(1 << k))
+        if not small and self.force_n is None and self.rnd.random() < 0.12:  # (a long table more often than log_n has it: a short one is to follow it)
+            k = self.rnd.choice((10, 11, 12))
+        self.emit("eq", f, point=[self.scalar(f) for _ in range(k)], scale=self.scalar(f) if self.rnd.random() < 0.5 else 1, out=self.place(1 << k), **self.order())
         return 1 << k
 
     def g_round(self, f, small):
-        fold = self.scalar(f) if self.rnd.random() < 0.5 else None
-        n, batch, stride = self.table_rows(small, 1 if fold is None else 2, 4)
+        fold = self.scalar(f) if self.rnd.random() < 0.5 or self.force_fold else None
+        order = self.order()
+        # a low-first fused round under a hook of 2 or 8 is long enough for several levels of partial sums between `partial` and the scratch rows
+        if order and fold is not None and not small and self.force_n is None and not self.force_big and self.hooks["frmle_test_tile"] not in (2, 8) and not self.no_plant and "hook" in self.kinds and self.rnd.random() < 0.3:
+            self.hooks["frmle_test_tile"] = self.rnd.choice((2, 8))  # (the hook steps alone set it too rarely for the schedules below)
+            self.emit("hook", 0, name="frmle_test_tile", value=self.hooks["frmle_test_tile"])
+        tiled = bool(order) and fold is not None and self.hooks["frmle_test_tile"] in (2, 8) and not small
+        n, batch, stride = self.table_rows(small, 6 if tiled else 1 if fold is None else 2, 4)
+        if tiled and self.force_n is None and self.hooks["frmle_test_tile"] == 8 and self.rnd.random() < 0.4:
+            n, batch = 2048, min(batch, 2)  # tiles of four pairs: 128 partial sums, three levels of them
+            stride = n + self.rnd.choice((0, 1))
+        if order and fold is not None and self.force_n is None and not tiled and not self.force_big and self.rnd.random() < 0.3:
+            pad = stride - n
+            n = self.rnd.choice((4, 8))  # one pair in one launch; two launches of one pair
+            stride = n + pad
         terms = [[self.scalar(f), [self.rnd.randrange(batch) for _ in range(self.rnd.randrange(1, 4 if n > 256 else 5))]] for _ in range(self.rnd.randrange(1, 4))]
         a = self.place(batch * stride)
         named = sorted({row for _, which in terms for row in which})
         self.maybe_plant(f, "round", self.spots(a, self.rnd, named, stride, n))
-        self.emit("round", f, a=a, terms=terms, batch=batch, n=n, fold=fold)
+        self.emit("round", f, a=a, terms=terms, batch=batch, n=n, fold=fold, **order)
+        return n
+
+    def g_gemini(self, f, small):
+        """the folds of one table of 2^k scalars, k >= 1, into n - 1 scalars of another bank; the lengths stop at 2^10: the model folds in Python"""
+        n = 1 << self.log_n(small, 1, 10)
+        a = self.place(n)
+        self.maybe_plant(f, "gemini", self.spots(a, self.rnd))
+        self.emit("gemini", f, a=a, point=[self.scalar(f) for _ in range(n.bit_length() - 1)], out=self.place(n - 1, [a]))
         return n
 
     def g_matrix(self, f, small):
@@ -906,6 +1025,8 @@ class _Gen:
         in_len, out_len = (rows, cols) if transpose else (cols, rows)
         pad_to = self.rnd.choice((None, None, out_len + 3, 1 << (out_len - 1).bit_length()))
         y_len = pad_to or out_len
+        if not small and len(col_idx) >= LARGE and len(self.mats[f]) < 3 and min(len(m[4]) for m in self.mats[f].values()) > SMALL:
+            self.g_matrix(f, True)  # a small matrix, alive for the small product that is to follow this large one with no step between
         x = self.place(in_len)
         if overlap:  # (x and y lie apart: the same start is refused too)
             out = self.shifted(x, y_len, 0)
@@ -1267,8 +1388,10 @@ class _Gen:
 
     def g_hook(self, f, small):
         names = sorted(HOOKS)
-        for name in self.rnd.sample(names, self.rnd.choice((1, 2, 2, 3))):  # (more than one at a time: no suite sets two hooks at once)
+        self.hooks_set = self.rnd.sample(names, self.rnd.choice((1, 2, 2, 3)))
+        for name in self.hooks_set:  # (more than one at a time: no suite sets two hooks at once)
             value = self.rnd.choice(HOOKS[name])
+            self.hooks[name] = value
             self.emit("hook", 0, name=name, value=value)
 
     def g_close(self, f, small, what=None):
@@ -1289,6 +1412,29 @@ class _Gen:
 
     def serves(self, f, kind):
         return self.fields[f] != "grumpkin" or kind in GRUMPKIN_KINDS or kind not in LIBRARY
+
+    def low_behind_top(self, f, kind, n):
+        """behind a top-first frmle step of n scalars to a row, sometimes and with no step between: the same entry point low first -- on the same
+        field or the other one, small behind large or large behind small; or, behind an mle_eval, a low-first fused round of fewer levels, whose
+        scratch rows then lie where the eval's levels lay (csrc/frmle_host.h: one scratch buffer to a device).  No value is planted: the call is
+        to compute on the state the top-first call left.  -> the field of the last step"""
+        hook = self.hooks["frmle_test_tile"]
+        shorter = [m for m in (4, 8, 16, 32, 64, 128, 256) if m <= n and 1 + low_fused_partials(m, hook) < eval_levels(n, hook)] if kind == "mle_eval" and "round" in self.kinds else []
+        c = self.rnd.random()
+        if c >= (0.9 if shorter else 0.75 if n >= LARGE else 0.4):
+            return f
+        self.no_plant, self.force_order = True, "low"
+        if shorter and c >= 0.2:
+            self.force_fold, self.force_n = True, self.rnd.choice(shorter)
+            self.g_round(f, False)
+        else:
+            if len(self.fields) > 1 and self.rnd.random() < 0.5:
+                f = 1 - f
+            d = self.rnd.random()
+            self.force_big = n <= SMALL and d < 0.5
+            getattr(self, "g_" + kind)(f, n >= LARGE and d < 0.7)
+        self.no_plant, self.force_order, self.force_big, self.force_fold, self.force_n = False, None, False, False, None
+        return f
 
     # ---- the program ---------------------------------------------------------------------------------------------------------------------
     def run(self, count):
@@ -1317,6 +1463,16 @@ class _Gen:
                 # libmsm_frcol's nodes, rel, used and z only grow and are per device, not per field: a small call of the same entry point right
                 # behind one that is larger, not only behind a "large" one
                 getattr(self, "g_" + kind)(f, True)
+            elif kind == "inverse" and per_row > SMALL and not small and self.rnd.random() < 0.3:
+                self.g_inverse(f, True)  # a shorter inverse behind a longer one, not only behind a "large" one: its scratch keeps the longer one's tail
+            elif kind in FRMLE_ORDERED and "order" not in self.steps[-1][2]:
+                f = self.low_behind_top(f, kind, per_row)
+            elif kind == "hook" and "frmle_test_tile" in self.hooks_set and self.hooks["frmle_test_tile"] in (2, 8) and "round" in self.kinds and self.rnd.random() < 0.7:
+                # launch tiles of one or four pairs: a low-first fused round long enough for three levels of partial sums under its scratch rows
+                self.force_order, self.force_fold = "low", True
+                self.force_n = self.rnd.choice((64, 256, 2048) if self.hooks["frmle_test_tile"] == 8 else (64, 128, 256))
+                self.g_round(f, False)
+                self.force_order, self.force_fold, self.force_n = None, False, None
             self.prev_f = f
             if per_row is not None and per_row >= LARGE and not small:
                 self.follow = (f, kind)

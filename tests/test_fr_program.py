@@ -10,7 +10,7 @@ import os
 import pytest
 
 from tests import fr_program as P
-from tests import frhash2_model, frhash_model, frlook_model, frvec_model
+from tests import frhash2_model, frhash_model, frlook_model, frmle_low_model, frvec_model
 from tests.test_gpu_fr_fuzz import COMMITTED, SECOND
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -301,6 +301,125 @@ def test_column_refusals_stay_rare_but_present(programs):
             elif kind == "gather" and (f, a["idx"]) in words and not P.column_cut((kind, f, a)):
                 at_n_a += a["a"][1] in words[f, a["idx"]]
     assert wrapped >= 1 and off_by_one >= 3 and at_n_a >= 1, (wrapped, off_by_one, at_n_a)
+
+
+def frmle_calls(steps):
+    """the calls of libmsm_frmle of a program, in order: dicts of the step's index and kind, its field index, its order ("top" / "low"), the
+    scalars n of a row's table, batch and stride (eq, gemini: one row of n), whether it binds in place (a fold onto its input, a fused round),
+    the field's form, the stream and frmle_test_tile at the call, the step's arguments, and how it ends -- None: it computes; "planted": it
+    reads a planted value and is refused by the library (`at`: that scalar's index in its row); "overlap": refused for its output"""
+    mont, side, tile, out = {}, False, 0, []
+    for i, (kind, f, a) in enumerate(steps):
+        if kind == "format":
+            mont[f] = a["mont"]
+        elif kind == "stream":
+            side = a["side"]
+        elif kind == "hook" and a["name"] == "frmle_test_tile":
+            tile = a["value"]
+        elif P.LIBRARY.get(kind) == "frmle":
+            rows = a["a"] if "a" in a else a["out"]
+            batch = a.get("batch", 1)
+            stride = rows[1] // batch
+            n = a.get("n", rows[1])
+            c = {"index": i, "kind": kind, "f": f, "order": "low" if kind == "gemini" else a.get("order", "top"), "n": n, "batch": batch, "stride": stride, "mont": bool(mont.get(f)),
+                 "side": side, "tile": tile, "args": a, "end": "overlap" if a.get("overlap") else None, "at": None,
+                 "in_place": (kind == "mle_fold" and (a["out"] is None or a["out"][0] == a["a"][0])) or (kind == "round" and a["fold"] is not None)}
+            before = steps[i - 1]
+            if before[0] == "plant" and not before[2].get("quiet"):
+                c["end"], c["at"] = "planted", (before[2]["at"] - rows[0]) // 2 % stride
+            out.append(c)
+    return out
+
+
+def low_calls(programs, kind, **where):
+    """(fields, call) of the low-first calls of one entry point that compute, over all programs; where: in_place=.."""
+    return [(fields, c) for fields, _, _, steps in programs for c in frmle_calls(steps)
+            if c["kind"] == kind and c["order"] == "low" and c["end"] is None and all(c[k] == v for k, v in where.items())]
+
+
+def test_every_single_field_entry_draws_the_frmle_steps_in_both_orders_and_gemini(programs):
+    drawn = {}
+    for fields, _, _, steps in programs:
+        if len(fields) == 1:
+            for c in frmle_calls(steps):
+                drawn.setdefault(fields[0], set()).add((c["kind"], c["order"]))
+    want = {(kind, order) for kind in P.FRMLE_ORDERED for order in ("top", "low")} | {("gemini", "low")}
+    assert set(drawn) == {"bn254", "pallas", "vesta", "bls12_381", "grumpkin"} and all(got == want for got in drawn.values()), drawn
+
+
+def test_the_low_first_fold_in_place_runs_at_every_size_form_stream_and_alignment(programs):
+    """csrc/frmle_plan.h: n = 2 is one launch and no copy, n = 4 has a lower half of one output, n >= 1024 has several workgroups to a launch; the
+    scratch rows are n / 4 apart, the rows themselves `stride`"""
+    calls = [c for _, c in low_calls(programs, "mle_fold", in_place=True)]
+    assert sum(c["n"] == 2 for c in calls) >= 3 and sum(c["n"] == 4 for c in calls) >= 3
+    assert sum(c["n"] >= 1024 and c["batch"] >= 2 and c["stride"] > c["n"] for c in calls) >= 3
+    assert min(sum(c["mont"] == form for c in calls) for form in (False, True)) >= 5
+    assert sum(c["side"] for c in calls) >= 5
+    assert sum(c["args"]["a"][0] % 2 for c in calls) >= 5  # a start at 16 mod 32
+
+
+def test_a_low_first_fold_writes_directly_behind_its_input(programs):
+    """apart, with `out` on the byte behind the last byte of a's span: every fold of a Gemini step behind its first (multilinear.gemini_folds),
+    and mle_fold steps placed so"""
+    folds = [c for _, c in low_calls(programs, "mle_fold", in_place=False)]
+    behind = [c for c in folds if c["args"]["out"][0] == c["args"]["a"][0] + 2 * ((c["batch"] - 1) * c["stride"] + c["n"])]
+    gemini = [c for _, c in low_calls(programs, "gemini") if c["n"] >= 4]
+    assert len(behind) >= 5 and len(gemini) >= 20, (len(behind), len(gemini))
+    assert any(c["batch"] >= 2 for c in behind)
+
+
+def test_the_low_first_fused_round_runs_at_every_schedule(programs):
+    """csrc/frmle_plan.h: n = 4 is one pair, one launch and no scratch rows; n = 8 two launches of one pair; frmle_test_tile 2 gives launches tiles
+    of one pair; under a hook of 2 or 8 several levels of partial sums lie between `partial` and the scratch rows"""
+    calls = [c for _, c in low_calls(programs, "round", in_place=True)]
+    assert sum(c["n"] == 4 for c in calls) >= 3 and sum(c["n"] == 8 for c in calls) >= 3 and sum(c["n"] >= 1024 for c in calls) >= 3
+    for tile in (2, 8):
+        hooked = [c for c in calls if c["tile"] == tile and c["n"] >= 64]
+        assert len(hooked) >= 3, (tile, len(hooked))
+        assert any(P.low_fused_partials(c["n"], tile) >= 3 for c in hooked), tile  # three or more levels of partials
+    assert sum(c["batch"] >= 3 and any(c["batch"] - 1 in which for _, which in c["args"]["terms"]) for c in calls) >= 3  # a term names the last row
+
+
+def test_a_low_first_call_directly_follows_a_top_first_one_of_its_entry_point(programs):
+    """the very next step, both of them computing: on the same field; on the other field of a two-field entry; small behind large and large behind
+    small; and a low-first fused round behind an mle_eval of more levels, whose scratch rows lie where the eval's levels lay"""
+    same, other, to_small, to_large, behind_eval = set(), set(), set(), set(), 0
+    for fields, _, _, steps in programs:
+        calls = frmle_calls(steps)
+        for before, c in zip(calls, calls[1:]):
+            if c["index"] != before["index"] + 1 or c["order"] != "low" or before["order"] != "top" or c["end"] or before["end"]:
+                continue
+            if c["kind"] == before["kind"]:
+                (same if c["f"] == before["f"] else other).add(c["kind"])
+                if before["n"] >= P.LARGE and c["n"] <= P.SMALL:
+                    to_small.add(c["kind"])
+                if before["n"] <= P.SMALL and c["n"] >= P.LARGE:
+                    to_large.add(c["kind"])
+        for before, c in zip(calls, calls[1:]):  # (the eval in either order)
+            behind_eval += (c["index"] == before["index"] + 1 and before["kind"] == "mle_eval" and c["kind"] == "round" and c["order"] == "low" and c["in_place"]
+                            and not c["end"] and not before["end"] and c["f"] == before["f"] and P.eval_levels(before["n"], before["tile"]) > 1 + P.low_fused_partials(c["n"], c["tile"]))
+    every = set(P.FRMLE_ORDERED)
+    assert same == every and other == every and to_small == every and to_large == every, (same, other, to_small, to_large)
+    assert behind_eval >= 3, behind_eval
+
+
+def test_a_planted_value_reaches_both_launches_of_a_low_first_fold_in_place_and_an_overlap_is_refused(programs):
+    """[0, n / 2) of a row is read by the launch that stores to the scratch rows, [n / 2, n) by the one that stores in place (n >= 4); the call
+    is refused and the field's next step computes"""
+    lower = upper = overlaps = 0
+    for fields, _, _, steps in programs:
+        for c in frmle_calls(steps):
+            overlaps += c["kind"] == "mle_fold" and c["order"] == "low" and c["end"] == "overlap"
+            if c["kind"] == "mle_fold" and c["order"] == "low" and c["in_place"] and c["end"] == "planted" and c["n"] >= 4:
+                after = next((j for j in range(c["index"] + 1, len(steps)) if steps[j][1] == c["f"] and steps[j][0] in P.LIBRARY), None)
+                if after is not None:
+                    model = P.Model(fields)
+                    errors = [model.step(s)["error"] for s in steps[:after + 1]]
+                    assert errors[c["index"]] == P.ERR_NONCANONICAL
+                    if errors[after] is None:
+                        lower += c["at"] < c["n"] // 2
+                        upper += c["at"] >= c["n"] // 2
+    assert lower >= 1 and upper >= 1 and overlaps >= 1, (lower, upper, overlaps)
 
 
 def test_the_loop_passes_a_backend_that_is_the_model(capsys):
@@ -743,10 +862,101 @@ class OneScalarPastTheOutput(ColumnFault):
             self.fired()
 
 
+class LowFault(Faulty):
+    """a fault in a low-first call of libmsm_frmle that computes: spoil(kind, f, a, before) changes what the call left in the arena and calls
+    fired() where a byte changed; before: a copy of the model as it was"""
+
+    def spoil(self, kind, f, a, before):
+        pass
+
+    def faulty(self, kind, f, a):
+        if P.LIBRARY.get(kind) != "frmle" or (kind != "gemini" and a.get("order") != "low"):
+            return self.plain_call(kind, f, a)
+        before = copy.deepcopy(self.m)
+        host = self.plain_call(kind, f, a)  # (a refused call raises here)
+        self.spoil(kind, f, a, before)
+        return host
+
+    def replace(self, f, off16, plain):
+        """the plain values go to off16 in the field's form; fired() where that changes a byte"""
+        data = self.m.enc(f, plain)
+        if self.m.raw(f, (off16, len(plain))) != data:
+            self.m.put(f, off16, data)
+            self.fired()
+
+    @staticmethod
+    def folds_in_place(kind, a):
+        return kind == "mle_fold" and (a["out"] is None or a["out"][0] == a["a"][0])
+
+
+class OrderFlagDropped(Faulty):
+    """an eq that answers top first when asked low first; at k <= 1 the orders agree"""
+    fields_to_run = "bn254"
+
+    def faulty(self, kind, f, a):
+        if kind != "eq" or a.get("order") != "low" or len(a["point"]) < 2:
+            return self.plain_call(kind, f, a)
+        host = self.plain_call(kind, f, {k: v for k, v in a.items() if k != "order"})
+        if self.m.raw(f, a["out"]) != self.m.enc(f, frmle_low_model.eq(a["point"], self.m.r[f], a["scale"])):
+            self.fired()
+        return host
+
+
+class ScratchRowsComeHomeForTheFirstRowOnly(LowFault):
+    """a low-first fold in place whose copy brings home the first scratch row only: the rows behind it keep their old [0, n / 4)"""
+    fields_to_run = "grumpkin"
+
+    def spoil(self, kind, f, a, before):
+        if self.folds_in_place(kind, a) and a["batch"] >= 2 and a["n"] >= 4:
+            stride = a["a"][1] // a["batch"]
+            for k in range(1, a["batch"]):
+                self.replace(f, a["a"][0] + 2 * k * stride, before.plain(f, (a["a"][0] + 2 * k * stride, a["n"] // 4)))
+
+
+class LowerLaunchRunsSecond(LowFault):
+    """a low-first fold in place whose launches run the wrong way round: the outputs [n / 8, n / 4) are computed from [n / 4, n / 2) of a row that
+    already holds the upper launch's outputs"""
+    fields_to_run = "bls12_381"
+
+    def spoil(self, kind, f, a, before):
+        if self.folds_in_place(kind, a) and a["n"] >= 8:
+            n, stride = a["n"], a["a"][1] // a["batch"]
+            for k in range(a["batch"]):
+                row = a["a"][0] + 2 * k * stride
+                late = self.m.plain(f, (row + 2 * (n // 4), n // 4))  # the outputs [n / 4, n / 2)
+                self.replace(f, row + 2 * (n // 8), frmle_low_model.fold(late, a["c"], self.m.r[f]))
+
+
+class ScratchRowsOverThePartials(LowFault):
+    """a low-first fused round under a tile hook whose scratch rows begin on the first level of partial sums where there are more levels than
+    one: the first folded scalar of row 0 gives way to the first partial sum (here: the first launch tile's share of g(0))"""
+    fields_to_run = "grumpkin"
+
+    def spoil(self, kind, f, a, before):
+        hook = self.m.hooks["frmle_test_tile"]
+        if kind == "round" and a["fold"] is not None and hook and P.low_fused_partials(a["n"], hook) > 1:
+            stride, rows, _ = self.m._rows(f, a["a"], a["batch"], a["n"] // 2)
+            share = frmle_low_model.round_values([row[:hook] for row in rows], [(c, tuple(w)) for c, w in a["terms"]], self.m.r[f])[0]
+            self.replace(f, a["a"][0], [share])
+
+
+class GeminiSliceFromTheTable(LowFault):
+    """a Gemini step whose second fold reads the head of `a` in place of f_1"""
+    fields_to_run = "vesta"
+
+    def spoil(self, kind, f, a, before):
+        if kind == "gemini" and len(a["point"]) >= 2:
+            r, table = self.m.r[f], self.m.plain(f, a["a"])
+            f_1 = frmle_low_model.fold(table, a["point"][0], r)
+            rest = frmle_low_model.gemini_folds(table[:len(f_1)], a["point"][1:], r)
+            self.replace(f, a["out"][0], f_1 + [x for f_j in rest for x in f_j])
+
+
 @pytest.mark.parametrize("fault", [ScanTileBoundary, ScratchKeepsTheTail, NttReusesTheTable, TableAnswersForAnother, ErrorWordNotCleared, SecondHalfFromFurtherOn,
                                    MontComputedAsCanonical, OneByteTooMany, HandleAnswersForTheOneBefore, SpongeReadsThePadding, SpongeTakesTheOtherFormsConstants, SecondLevelFromTheLeaves,
                                    HostOutputFromTheStaleSpot, FirstTidiedWidthGoesWrong, InternalSumTakenLate, AnsweredWithTheOtherKindsCode, RunOnATileBoundaryCopiesThePreviousEntry,
-                                   FillersFromThePreviousCallsZ, MissingElementLeftAsItWas, OneScalarPastTheOutput], ids=lambda c: c.__name__)
+                                   FillersFromThePreviousCallsZ, MissingElementLeftAsItWas, OneScalarPastTheOutput, OrderFlagDropped,
+                                   ScratchRowsComeHomeForTheFirstRowOnly, LowerLaunchRunsSecond, ScratchRowsOverThePartials, GeminiSliceFromTheTable], ids=lambda c: c.__name__)
 def test_a_planted_fault_is_caught_at_its_step_and_replays(fault):
     fields = fault.fields_to_run.split(",")
     seed, cases = COMMITTED[fault.fields_to_run]

@@ -23,6 +23,17 @@ again the same way on another machine without a GPU, three runs each, the parent
 The slowest single case took 0.4 s (parent: 0.55 s).  No entry is past 3 s, so none is split further; bls12_381 has twice its cases, because its 15 did not reach every Poseidon2 width three times (t = 2: once),
 and only on that field do t = 3 and t = 12 take paths of their own.  The column steps' model copies lists and is cheap; the Poseidon2 steps are
 bounded by fr_program.HASH2_WORK as the Poseidon steps are by HASH_WORK.
+With an order on libmsm_frmle's four steps (low first through msm_webgpu_amd.multilinear) and the `gemini` step among the programs every draw
+shifted once more.  Measured the same way on a machine without a GPU, three runs each, the parent commit first, then these programs (entry, cases:
+median, least .. most):
+    bn254 30: parent 1.8 s (1.8 .. 2.0), now 2.2 s (2.0 .. 2.2); pallas 30: 2.2 s (2.2 .. 2.6), now 1.9 s; vesta 28: 1.4 s (1.4 .. 1.5), now 2.7 s
+    (2.6 .. 2.7); bls12_381 30: 1.6 s (1.6 .. 1.7), now 2.2 s (2.0 .. 2.2); grumpkin 40: 2.3 s (2.3 .. 2.4), now 2.3 s (2.3 .. 2.6);
+    bn254,bls12_381 20: 1.4 s (1.2 .. 1.5), now 1.2 s, and 12: 1.7 s, now 1.4 s (1.4 .. 1.5); pallas,vesta 20: 1.7 s (1.6 .. 2.2), now 1.9 s, and
+    12: 0.5 s, now 1.3 s (1.3 .. 1.4); bn254,grumpkin 28: 2.3 s (2.2 .. 2.5), now 1.7 s (1.7 .. 1.9), and 14: 1.0 s, now 2.2 s.
+No entry is past 3 s, so no count changes and none is split.  The low-first steps are not what moves the figures: one pass of the model over the
+30 bn254 programs (1.2 s) spends 0.07 s in them (tests/frmle_low_model.py's evaluate builds the eq table, n log n products to a row, at no more
+than 4096 scalars; a `gemini` step has at most 1024) against 0.24 s in the inverses and 0.47 s in the hashing steps, and which of those a seed
+draws is what changed.
 Nobody has measured the device side of these counts on its own: the device work is milliseconds, and a test's time is the model's on whatever
 CPU the GPU machine has."""
 import os

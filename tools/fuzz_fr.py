@@ -6,6 +6,10 @@ call, on whichever stream and under whichever form that call has; a hashing call
 one on their bytes), and with the counts and indices that a lookup call returned kept on the device for the column calls of
 msm_webgpu_amd.columns behind it.  After EVERY step each range the step wrote and each host value it returned is compared byte for byte with the model; at the end
 of a program the whole arena is.
+The four steps of libmsm_frmle carry an order: a low-first one (order="low": MSM_FRMLE_LOW_FIRST) runs through msm_webgpu_amd.multilinear, a
+top-first one, which has no order argument, through the context's scalars_* methods, so both call paths run.  A low-first bind in place leaves the
+scalars [n / 2, n) of every row unspecified: the model names them, they are rewritten from the model before the step's outputs [0, n / 2) and their
+guards are compared.  A "gemini" step is multilinear.gemini_folds of one row, its n - 1 scalars copied into the arena.
 Usage: python tools/fuzz_fr.py [cases] [seed] [field[,field]] [--case K]   (fields: bn254 pallas vesta bls12_381 grumpkin; --case K replays one case)
 FUZZ_FR_KINDS=a,b,... restricts the step kinds that are drawn (tests/fr_program.py: KINDS)."""
 import os
@@ -49,15 +53,15 @@ def run_program(steps, fields, backend):
                 raise Mismatch(i, "the call returned %r, the model predicts %r" % (err, want["error"]))
             if err is None and host != want["host"]:
                 raise Mismatch(i, "host values differ: got %r, the model predicts %r" % (host, want["host"]))
-            for off16, n in want["writes"]:
+            for off16, n in want["rewrite"]:  # (unspecified: after a predicted ERR_NONCANONICAL, behind a low-first bind in place; or the planted scalar itself)
+                backend.write(f, off16, model.raw(f, (off16, n)))
+            for off16, n in want["writes"]:  # (behind the rewrites: a guard may lie on an unspecified scalar, the first behind a low-first bind's outputs)
                 lo, hi = max(off16 - GUARD, 0), min(off16 + 2 * n + GUARD, P.ARENA16)
                 got, ref = backend.read16(f, lo, hi), bytes(model.arena[f][16 * lo:16 * hi])
                 if got != ref:
                     at = 16 * lo + _first_difference(got, ref)
                     raise Mismatch(i, "field %d (%s): byte %d of the arena differs (the step wrote [%d, %d): byte %d of it)" % (
                         f, fields[f], at, 16 * off16, 16 * off16 + 32 * n, at - 16 * off16))
-            for off16, n in want["rewrite"]:  # (unspecified after a predicted ERR_NONCANONICAL, or the planted scalar itself)
-                backend.write(f, off16, model.raw(f, (off16, n)))
         for f in range(len(fields)):
             got, ref = backend.read16(f, 0, P.ARENA16), bytes(model.arena[f])
             if got != ref:
@@ -103,8 +107,8 @@ class DeviceBackend:
         import torch
 
         import msm_webgpu_amd as m
-        from msm_webgpu_amd import api, columns
-        self.torch, self.api, self.columns, self.fields = torch, api, columns, list(fields)
+        from msm_webgpu_amd import api, columns, multilinear
+        self.torch, self.api, self.columns, self.multilinear, self.fields = torch, api, columns, multilinear, list(fields)
         for name in fields:
             r = P.FIELD_R[name]
             assert api.SCALAR_FIELDS[name] == r and (name == "grumpkin" or all(api.root_of_unity(name, k) == P.root_of_unity(r, k) for k in range(13)))
@@ -206,21 +210,36 @@ class DeviceBackend:
     def op_powers(self, f, g, n, scale, out):
         self.ctx[f].scalars_powers(g, n, scale, out=self.t(f, out))
 
+    # a top-first frmle step goes through the context's scalars_* method, a low-first one through msm_webgpu_amd.multilinear: both call paths run
     @_translated
-    def op_mle_fold(self, f, a, c, batch, n, out):
-        self.ctx[f].scalars_mle_fold(self.t(f, a), c, batch, n, out=self.t(f, out))
+    def op_mle_fold(self, f, a, c, batch, n, out, order="top"):
+        if order == "low":
+            self.multilinear.fold(self.ctx[f], self.t(f, a), c, batch, n, out=self.t(f, out), order="low")
+        else:
+            self.ctx[f].scalars_mle_fold(self.t(f, a), c, batch, n, out=self.t(f, out))
 
     @_translated
-    def op_mle_eval(self, f, a, point, batch, n):
+    def op_mle_eval(self, f, a, point, batch, n, order="top"):
+        if order == "low":
+            return self.multilinear.evaluate(self.ctx[f], self.t(f, a), point, batch, n, order="low")
         return self.ctx[f].scalars_mle_eval(self.t(f, a), point, batch, n)
 
     @_translated
-    def op_eq(self, f, point, scale, out):
-        self.ctx[f].scalars_eq(point, scale, out=self.t(f, out))
+    def op_eq(self, f, point, scale, out, order="top"):
+        if order == "low":
+            self.multilinear.eq(self.ctx[f], point, scale, out=self.t(f, out), order="low")
+        else:
+            self.ctx[f].scalars_eq(point, scale, out=self.t(f, out))
 
     @_translated
-    def op_round(self, f, a, terms, batch, n, fold):
+    def op_round(self, f, a, terms, batch, n, fold, order="top"):
+        if order == "low":
+            return self.multilinear.sumcheck_round(self.ctx[f], self.t(f, a), terms, batch, n, fold, order="low")
         return self.ctx[f].scalars_sumcheck_round(self.t(f, a), terms, batch, n, fold)
+
+    @_translated
+    def op_gemini(self, f, a, point, out):
+        self.t(f, out).copy_(self.multilinear.gemini_folds(self.ctx[f], self.t(f, a), point).view(-1))
 
     @_translated
     def op_matrix(self, f, slot, rows, cols, row_ptr, col_idx, vseed, transpose):
