@@ -1,5 +1,5 @@
 """Build libmsm_hip.so, the scalar-field libraries (FR_LIBRARIES: libmsm_fr.so ... libmsm_frhash.so) and the field-neutral ones (AUX_LIBRARIES:
-libmsm_frcol.so) in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
+libmsm_frcol.so; MEM_LIBRARIES: libmsm_frmem.so) in-tree with hipcc for gfx950 (cross-compiles without a GPU)."""
 import collections
 import os
 import subprocess
@@ -43,16 +43,26 @@ AUX_LIBRARIES = collections.OrderedDict((lib.name, lib) for lib in [
     FrLibrary("frcol", os.path.join(HERE, "libmsm_frcol.so"), ["frcol.hip"], ["frcol.hip", "frcol_kernels.h", "frcol_host.h", "frcol_plan.h", "fr_host_common.h"],
               [os.path.join(HERE, "..", "include", "msm_frcol.h"), HEADER]),  # lookup columns from counts: run expansion, halo2's permuted pair, gather
 ])
+# Libraries over integer keys, without scalars at all: a third table of the same rows.
+MEM_LIBRARIES = collections.OrderedDict((lib.name, lib) for lib in [
+    FrLibrary("frmem", os.path.join(HERE, "libmsm_frmem.so"), ["frmem.hip"], ["frmem.hip", "frmem_kernels.h", "frmem_host.h", "frmem_plan.h", "fr_host_common.h"],
+              [os.path.join(HERE, "..", "include", "msm_frmem.h"), HEADER]),  # memory arguments: stable argsort of integer keys, access counters
+])
 TEMPS = os.path.join(HERE, "..", "build", "temps" if not os.environ.get("MSM_HIP_SO") else "temps_" + os.path.basename(SO))
 
 
+def library_rows():
+    """Every row of every table, in build order: what build(), library_of(), device_asm_files() and needs_build() know of libraries beside libmsm_hip.so"""
+    return [lib for table in (FR_LIBRARIES, AUX_LIBRARIES, MEM_LIBRARIES) for lib in table.values()]
+
+
 def library_of(units):
-    """The row of FR_LIBRARIES or AUX_LIBRARIES whose units contain `units`; None for libmsm_hip.so's units (and for none at all)."""
-    return next((lib for lib in list(FR_LIBRARIES.values()) + list(AUX_LIBRARIES.values()) if units and set(units) <= set(lib.units)), None)
+    """The row (library_rows()) whose units contain `units`; None for libmsm_hip.so's units (and for none at all)."""
+    return next((lib for lib in library_rows() if units and set(units) <= set(lib.units)), None)
 
 
 def device_asm_files(lib=None):
-    """The device assembly of every translation unit of a library (lib: a row of FR_LIBRARIES or AUX_LIBRARIES; None: libmsm_hip.so), as build() leaves it behind."""
+    """The device assembly of every translation unit of a library (lib: one of library_rows(); None: libmsm_hip.so), as build() leaves it behind."""
     return [os.path.join(TEMPS, os.path.splitext(u)[0] + "-hip-amdgcn-amd-amdhsa-gfx950.s") for u in (lib.units if lib else TRANSLATION_UNITS)]
 
 
@@ -147,9 +157,9 @@ def compile_flags():
 def build(force=False, verbose=False):
     """hipcc --offload-arch=gfx950: every translation unit of csrc/ to an object (in parallel), then -shared -> msm-webgpu_amd/libmsm_hip.so and,
     from the scalar-field units, every library of FR_LIBRARIES (msm-webgpu_amd/libmsm_fr.so ... msm-webgpu_amd/libmsm_frhash.so) and of
-    AUX_LIBRARIES (msm-webgpu_amd/libmsm_frcol.so).  Each library is rebuilt only when its own sources or the flags changed."""
+    AUX_LIBRARIES and MEM_LIBRARIES (msm-webgpu_amd/libmsm_frcol.so, msm-webgpu_amd/libmsm_frmem.so).  Each library is rebuilt only when its own sources or the flags changed."""
     do_hip = force or needs_build()
-    todo = [lib for lib in list(FR_LIBRARIES.values()) + list(AUX_LIBRARIES.values()) if (force and not os.environ.get("MSM_HIP_SO")) or needs_build(lib)]
+    todo = [lib for lib in library_rows() if (force and not os.environ.get("MSM_HIP_SO")) or needs_build(lib)]
     if not do_hip and not todo:
         return SO
     if variant_flags() and not os.environ.get("MSM_HIP_SO"):
